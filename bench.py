@@ -15,7 +15,12 @@ scaling): n = 8192 * N^(1/3) rounded to the panel width, the trailing update
 sharded 1-D block-cyclic by columns with a panel broadcast per step
 (linalg_solver_amd/dist.py); N=8 gives config #4's 16384 x 16384.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and
+prints the headline (metric, value, unit, ms_per_step); --full adds everything
+else: per-kernel roofline figures from extra untimed passes, the in-run parity
+checks, the other BASELINE configs, fp32, the PCIe-inclusive path and the CPU
+baselines.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (inputs are the same from run to run for the same arguments).
 """
 from __future__ import annotations
 
@@ -34,6 +39,61 @@ HBM_PEAK_GBS = 8000.0
 
 def lu_flops(n: int) -> float:
     return 2.0 / 3.0 * n ** 3
+
+
+def resident_steps(torch, total: int, bytes_per_step: int) -> int:
+    """How many steps' inputs are generated ahead and kept resident: all of them when they fit in 3/4 of the free
+    device memory (the timed region then holds nothing but the steps), otherwise as many as fit -- the timed steps
+    then run in rounds of that many, each round's inputs generated while the clock is stopped."""
+    free = torch.cuda.mem_get_info()[0]
+    return max(1, min(total, int(0.75 * free) // max(bytes_per_step, 1)))
+
+
+def run_rounds(first: int, count: int, pool: int, held: list, regen, step, barrier) -> float:
+    """Steps first .. first+count-1, input of step s in slot s % pool; returns the seconds spent in the steps.  A slot
+    that does not hold step s's fresh input (held[slot] != s) is regenerated before the round's clock starts."""
+    dt, s, end = 0.0, first, first + count
+    while s < end:
+        e = min(end, s + pool)
+        for i in range(s, e):
+            if held[i % pool] != i:
+                regen(i)
+                held[i % pool] = i
+        barrier()
+        t0 = time.perf_counter()
+        for i in range(s, e):
+            step(i)
+            held[i % pool] = -1   # factored in place
+        barrier()
+        dt += time.perf_counter() - t0
+        s = e
+    return dt
+
+
+DUMP_SAMPLE = 1 << 21   # LU entries written by --dump-outputs: 16 MiB in fp64
+
+
+def dump_outputs(path: str, torch, LU, ipiv, info) -> None:
+    """--dump-outputs DIR: what the last timed step handed back to its caller -- the factors L\\U, the interchanges and
+    the info word -- as DIR/<name>.npy.  The factors are too large to write whole: a fixed, seeded sample of their
+    entries (lu_sample, the same positions for the same shape) and, for a square matrix, U's whole diagonal (lu_diag)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    fdt = np.float64 if LU.dtype == torch.float64 else np.float32
+    flat = LU.reshape(-1)
+    idx = np.sort(np.random.default_rng(20261015).integers(0, flat.numel(), size=min(DUMP_SAMPLE, flat.numel())))
+    outs = {"lu_sample": flat[torch.from_numpy(idx).to(LU.device)].cpu().numpy().astype(fdt)}
+    if LU.shape[0] == LU.shape[1]:
+        outs["lu_diag"] = torch.diagonal(LU).cpu().numpy().astype(fdt)
+    outs["ipiv"] = ipiv.cpu().numpy().astype(np.float64)
+    outs["info"] = info.cpu().numpy().astype(np.float64).reshape(-1)
+    for k, v in outs.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+# thread counts the LAPACK child must not inherit: its BLAS picks its own pool, which the child then limits per sweep
+LAPACK_CHILD_DROP_ENV = ("OMP_NUM_THREADS", "MKL_NUM_THREADS", "OPENBLAS_NUM_THREADS")
 
 
 def cpu_baseline(sample_n: int):
@@ -60,7 +120,7 @@ def cpu_baseline(sample_n: int):
     try:
         import subprocess
 
-        env = {k: v for k, v in os.environ.items() if k not in ("OMP_NUM_THREADS", "MKL_NUM_THREADS", "OPENBLAS_NUM_THREADS")}
+        env = {k: v for k, v in os.environ.items() if k not in LAPACK_CHILD_DROP_ENV}
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--lapack-child"], capture_output=True, text=True,
                            timeout=240, env=env)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -98,9 +158,11 @@ def lapack_child():
             from threadpoolctl import threadpool_limits
         except Exception:
             threadpool_limits = None
-        for nt in ([8, 16, 32, 64] if threadpool_limits else [0]):
-            if nt > cores:
-                continue
+        # never above the pool the BLAS started with (an inherited OPENBLAS_NUM_THREADS sets it): raising an OpenBLAS
+        # pool past its start-up size is not something to rely on
+        start = min([p["num_threads"] for p in (pools or []) if p.get("num_threads")] or [cores])
+        sizes = [t for t in (8, 16, 32, 64) if t <= min(cores, start)] or [min(cores, start)]
+        for nt in (sizes if threadpool_limits else [0]):
             best = 1e30
             ctx = threadpool_limits(limits=nt) if threadpool_limits else None
             try:
@@ -197,37 +259,47 @@ def bench_mg(args, torch):
             locs.append(loc)
         return locs
 
-    mats = [make(1 + s) for s in range(total)]
+    pool = resident_steps(torch, total, n * (sum(mg.local_cols) if rehearsal else max(mg.local_cols)) * 8)
+    mats = [make(1 + s) for s in range(pool)]
+    held = list(range(pool))
+
+    def regen(s):
+        mats[s % pool] = None
+        mats[s % pool] = make(1 + s)
 
     def sync():
         for d in sorted(set(devices)):
             torch.cuda.synchronize(d)
 
-    sync()
     res = None
-    for i in range(args.warmup):
-        res = mg.factor_(mats[i])
-    sync()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        res = mg.factor_(mats[args.warmup + i])
-    sync()
-    dt = time.perf_counter() - t0
+
+    def step(i):
+        nonlocal res
+        res = mg.factor_(mats[i % pool])
+
+    run_rounds(0, args.warmup, pool, held, regen, step, sync)
+    dt = run_rounds(args.warmup, args.steps, pool, held, regen, step, sync)
     ipiv, info = res
-    # in-run check of the last factorisation: info, |l| <= 1, the pivot vectors of all devices agree
-    LU = mats[args.warmup + args.steps - 1] if args.steps else mats[args.warmup - 1]
-    worst, infos = 0.0, []
-    for d in range(P):
-        off = 0
-        rows = torch.arange(n, device=LU[d].device).unsqueeze(1)
-        for b in mg.blocks[d]:
-            w = min(nb, n - b * nb)
-            cols = torch.arange(b * nb, b * nb + w, device=LU[d].device).unsqueeze(0)
-            worst = max(worst, float((LU[d][:, off:off + w].abs() * (rows > cols)).max()))
-            off += w
-        infos.append(int(info[d].item()))
-    same_piv = all(bool(torch.equal(ipiv[0].cpu(), ipiv[d].cpu())) for d in range(1, P))
-    ms = dt / max(args.steps, 1) * 1e3
+    LU = mats[(total - 1) % pool]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, LU[0], ipiv[0], torch.cat([i.cpu() for i in info]))
+    infos = [int(info[d].item()) for d in range(P)]
+    check = None
+    if args.full:
+        # in-run check of the last factorisation: info, |l| <= 1, the pivot vectors of all devices agree
+        worst = 0.0
+        for d in range(P):
+            off = 0
+            rows = torch.arange(n, device=LU[d].device).unsqueeze(1)
+            for b in mg.blocks[d]:
+                w = min(nb, n - b * nb)
+                cols = torch.arange(b * nb, b * nb + w, device=LU[d].device).unsqueeze(0)
+                worst = max(worst, float((LU[d][:, off:off + w].abs() * (rows > cols)).max()))
+                off += w
+        same_piv = all(bool(torch.equal(ipiv[0].cpu(), ipiv[d].cpu())) for d in range(1, P))
+        check = {"info": infos, "max_abs_multiplier": worst, "pivot_vectors_agree": same_piv,
+                 "ok": bool(all(v == 0 for v in infos) and worst <= 1.0 + 1e-12 and same_piv)}
+    ms = dt / args.steps * 1e3
     out = {"metric": "fp64_lu_gflops", "value": lu_flops(n) * args.steps / dt / 1e9, "unit": "GFLOP/s", "n_gpus": P,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -235,9 +307,7 @@ def bench_mg(args, torch):
                       "n": n, "nb": nb, "parallelism": f"1-D block-cyclic columns x{P}, panel written to every peer "
                                                        f"(hipMemcpyPeerAsync, 4 row chunks), one process",
                       "devices": devices, "devices_visible": ndev, "rehearsal_all_handles_on_gpu0": rehearsal},
-           "check": {"info": infos, "max_abs_multiplier": worst, "pivot_vectors_agree": same_piv,
-                     "ok": bool(all(v == 0 for v in infos) and worst <= 1.0 + 1e-12 and same_piv)},
-           "roofline": None, "cpu_baseline": None}
+           "info": infos, "check": check, "roofline": None, "cpu_baseline": None}
     print(json.dumps(out))
     return 0
 
@@ -258,7 +328,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip solve-latency / 4096 side measurements")
     ap.add_argument("--mg", action="store_true",
                     help="ONE process driving --gpus N devices through lsx_getrf_mg_f64 (peer copies, no torch.distributed)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline / per-phase passes, in-run checks, the other configs, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -331,17 +407,22 @@ def main():
         torch.cuda.synchronize()
 
     total = args.steps + args.warmup
+    elt = 8 if args.dtype == "f64" else 4
     if world == 1:
+        pool = resident_steps(torch, total, n * n * elt)
         mats = []
-        for s in range(total):
+        for s in range(pool):
             A = torch.empty(n, n, dtype=tdt, device="cuda")
             dev.fill_(A, gen.U11, 1 + s)
             mats.append(A)
         ipiv = torch.empty(n, dtype=torch.int32, device="cuda")
         info = torch.zeros(1, dtype=torch.int32, device="cuda")
 
+        def regen(s):
+            dev.fill_(mats[s % pool], gen.U11, 1 + s)
+
         def step(i):
-            dev.getrf_(mats[i], ipiv, info)
+            dev.getrf_(mats[i % pool], ipiv, info)
     else:
         from linalg_solver_amd.dist import ShardedLU
 
@@ -355,73 +436,86 @@ def main():
         # two consecutive column blocks per owner: inside a pair the next panel starts without waiting for a broadcast
         # (the owner goes on while its panel is still on the wire), so only every second step has one on the chain
         slu = ShardedLU(dev, n, nb, rank, world, dtype=tdt, bcast=bcast, chunks=4, dist_block=2)
-        shards = [slu.fill(gen.U11, 1 + s) for s in range(total)]
+        # every rank must run the same rounds: the smallest pool of all ranks (rehearsal: all ranks share GPU 0)
+        pool_t = torch.tensor([resident_steps(torch, total, n * max(slu.local_cols, 1) * elt * (world if rehearsal else 1))],
+                              dtype=torch.int64, device="cpu" if rehearsal else "cuda")
+        dist.all_reduce(pool_t, op=dist.ReduceOp.MIN)
+        pool = int(pool_t.item())
+        shards = [slu.fill(gen.U11, 1 + s) for s in range(pool)]
 
         last = {}
 
+        def regen(s):
+            shards[s % pool] = None
+            shards[s % pool] = slu.fill(gen.U11, 1 + s)
+
         def step(i):
-            last["ipiv"], last["info"] = slu.factor_(shards[i])
+            last["ipiv"], last["info"] = slu.factor_(shards[i % pool])
             last["i"] = i
 
-    for i in range(args.warmup):
-        step(i)
-    barrier()
-    # live HIP events over the timed region, on the launch stream, for the TIME-DOMINANT kernel only: the panel
-    # factorisation (one launch per 128 columns, on the look-ahead driver's side stream).  Bracketing every
-    # launch of every phase costs ~7 % of the step; the trailing update is measured by an extra, untimed pass of
-    # the same driver below (`roofline_update`), the full per-phase breakdown by a sequential step.
-    dev.h.prof_reset()
-    PANEL_SAMPLE = 13 if world == 1 else 1  # every 13th panel launch (13 and the 64 panels of a step are coprime:
-    dev.h.set_option("prof_sample", PANEL_SAMPLE)   # over the steps every panel height is sampled): the events sit
-    dev.h.prof_enable(buckets=("panel",))           # on the panel-to-panel chain and would cost 4 % if all were bracketed
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        step(args.warmup + i)
-    barrier()
-    dt = time.perf_counter() - t0
-    dev.h.prof_enable(False)
-    dev.h.set_option("prof_sample", 1)
-    prof = dev.h.prof_read()
-    # the trailing update under the SAME driver (look-ahead: it runs beside the next panel), untimed extra pass
-    prof_upd = None
-    if world == 1:
+    held = list(range(pool))
+    run_rounds(0, args.warmup, pool, held, regen, step, barrier)
+    PANEL_SAMPLE = 13 if world == 1 else 1
+    if args.full:
+        # live HIP events over the timed region, on the launch stream, for the TIME-DOMINANT kernel only: the panel
+        # factorisation (one launch per 128 columns, on the look-ahead driver's side stream).  Bracketing every
+        # launch of every phase costs ~7 % of the step; the trailing update is measured by an extra, untimed pass of
+        # the same driver below (`roofline_update`), the full per-phase breakdown by a sequential step.
         dev.h.prof_reset()
-        dev.fill_(mats[0], gen.U11, 1)
-        barrier()
-        dev.h.prof_enable(buckets=("gemm",))
-        step(0)
-        barrier()
-        dev.h.prof_enable(False)
-        prof_upd = dev.h.prof_read()["gemm"]
-    # Per-phase breakdown: one more, untimed step with every phase bracketed by events.  On one GPU it
-    # runs the SEQUENTIAL driver (lookahead=0): under look-ahead the panel and the update overlap and
-    # their brackets no longer add up to the step.  The same step gives the dominant kernel's duration
-    # with the chip to itself (`roofline_sequential`).
-    dev.h.prof_reset()
-    look_default = dev.h.get_option("lookahead")
-    if world == 1:
-        dev.fill_(mats[0], gen.U11, 1)
-        dev.h.set_option("lookahead", 0)
-    else:
-        shards[0] = slu.fill(gen.U11, 1)
-    barrier()
-    dev.h.prof_enable(True)
-    step(0)
-    barrier()
-    dev.h.prof_enable(False)
-    dev.h.set_option("lookahead", look_default)
-    phases = dev.h.prof_read()
+        # every 13th panel launch (13 and the 64 panels of a step are coprime: over the steps every panel height is
+        # sampled): the events sit on the panel-to-panel chain and would cost 4 % if all were bracketed
+        dev.h.set_option("prof_sample", PANEL_SAMPLE)
+        dev.h.prof_enable(buckets=("panel",))
+    dt = run_rounds(args.warmup, args.steps, pool, held, regen, step, barrier)
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     if world == 1:
         assert int(info.item()) == 0, "benchmark matrix was singular"
+    if args.dump_outputs and rank == 0:
+        if world == 1:
+            dump_outputs(args.dump_outputs, torch, mats[(total - 1) % pool], ipiv, info)
+        else:   # rank 0's column blocks of the factors, the interchanges and the info word
+            dump_outputs(args.dump_outputs, torch, shards[(total - 1) % pool], last["ipiv"], last["info"])
+    look_default = dev.h.get_option("lookahead")
     shard_check = None
-    if world > 1:
+    if args.full:
+        dev.h.prof_enable(False)
+        dev.h.set_option("prof_sample", 1)
+        prof = dev.h.prof_read()
+        # the trailing update under the SAME driver (look-ahead: it runs beside the next panel), untimed extra pass
+        prof_upd = None
+        if world == 1:
+            dev.h.prof_reset()
+            dev.fill_(mats[0], gen.U11, 1)
+            barrier()
+            dev.h.prof_enable(buckets=("gemm",))
+            step(0)
+            barrier()
+            dev.h.prof_enable(False)
+            prof_upd = dev.h.prof_read()["gemm"]
+        # Per-phase breakdown: one more, untimed step with every phase bracketed by events.  On one GPU it
+        # runs the SEQUENTIAL driver (lookahead=0): under look-ahead the panel and the update overlap and
+        # their brackets no longer add up to the step.  The same step gives the dominant kernel's duration
+        # with the chip to itself (`roofline_sequential`).
+        dev.h.prof_reset()
+        if world == 1:
+            dev.fill_(mats[0], gen.U11, 1)
+            dev.h.set_option("lookahead", 0)
+        else:
+            shards[0] = slu.fill(gen.U11, 1)
+        barrier()
+        dev.h.prof_enable(True)
+        step(0)
+        barrier()
+        dev.h.prof_enable(False)
+        dev.h.set_option("lookahead", look_default)
+        phases = dev.h.prof_read()
+    if args.full and world > 1:
         # in-run check of the last sharded factorisation (untimed): info word, interchanges in range, and the
         # partial-pivoting invariant |l_ij| <= 1 on this rank's columns, reduced over the ranks
-        Ash, piv = shards[last["i"]], last["ipiv"]
+        Ash, piv = shards[last["i"] % pool], last["ipiv"]
         rows = torch.arange(n, device="cuda").unsqueeze(1)
         worst = torch.zeros(1, dtype=torch.float64, device="cuda")
         for b in slu.my_blocks:
@@ -445,6 +539,26 @@ def main():
                                    and resid < 1e-11)}
 
     if rank != 0:
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    ms_per_step = dt / args.steps * 1e3
+    value = lu_flops(n) * args.steps / dt / 1e9
+    out = {
+        "metric": "fp64_lu_gflops" if args.dtype == "f64" else "fp32_lu_gflops",
+        "value": value, "unit": "GFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"{n}x{n} {args.dtype} LU with partial pivoting (getrf), u11 generator, resident in HBM",
+                   "n": n, "nb": nb, "panel_mode": dev.h.get_option("panel"),
+                   "lookahead": look_default if world == 1 else "depth-1, sharded driver",
+                   "parallelism": "single GPU" if world == 1 else f"1-D block-cyclic columns x{world} (2 column blocks per owner), panel broadcast (RCCL) in 4 row chunks",
+                   "resident_inputs": pool},
+    }
+    if not args.full:   # the headline alone; everything below is --full
+        out["roofline"], out["cpu_baseline"] = None, None
+        print(json.dumps(out))
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -475,8 +589,6 @@ def main():
     if world == 1 and not args.no_extras:
         sustained = dev.h.mfma_peak(args.dtype == "f32", 100000, 1)[0]
 
-    ms_per_step = dt / args.steps * 1e3
-    value = lu_flops(n) * args.steps / dt / 1e9
     pl = prof["panel"]                          # live, timed region
     g = prof_upd if prof_upd else prof["gemm"]
     gemm_tflops = (g["flops"] / (g["ms"] * 1e-3) / 1e12) if g["ms"] > 0 else 0.0
@@ -500,15 +612,7 @@ def main():
                     "xcd_scope_allgather_plus_row_us": dev.h.xchg_probe(1, 32, 8, False, 2000)[0]}
         except Exception as e:  # noqa: BLE001
             hops = {"error": str(e)}
-    out = {
-        "metric": "fp64_lu_gflops" if args.dtype == "f64" else "fp32_lu_gflops",
-        "value": value, "unit": "GFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": f"{n}x{n} {args.dtype} LU with partial pivoting (getrf), u11 generator, resident in HBM",
-                   "n": n, "nb": nb, "panel_mode": dev.h.get_option("panel"),
-                   "lookahead": look_default if world == 1 else "depth-1, sharded driver",
-                   "parallelism": "single GPU" if world == 1 else f"1-D block-cyclic columns x{world} (2 column blocks per owner), panel broadcast (RCCL) in 4 row chunks"},
+    out.update({
         # the time-dominant kernel of the step: the panel factorisation.  SURVEY 8d prices it against HBM
         # (algorithmic bytes = each panel read + written once = 2 * sizeof(T) * m * nb per launch); what actually bounds
         # it is one cross-CU pivot exchange per column -- latency, stated beside the fraction.
@@ -545,7 +649,7 @@ def main():
                             "note": "extra untimed pass of the same look-ahead driver with only these launches bracketed"},
         "phases_ms_per_step": {k: v["ms"] for k, v in phases.items()},
         "phases_note": "one extra untimed step of the sequential driver (lookahead=0) with every phase bracketed by events",
-    }
+    })
 
     if g["launches"] == 0:   # sharded run: the update is not bracketed (its per-rank share is in phases_ms_per_step)
         out["roofline_update"] = None

@@ -102,8 +102,11 @@ def test_bench_lapack_baseline_runs_in_a_child_process_and_prints_one_json_line(
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from bench import LAPACK_CHILD_DROP_ENV
+
     env = dict(os.environ, OMP_NUM_THREADS="1")   # what a rank under the launcher sees; the parent strips it for the child
-    env.pop("OMP_NUM_THREADS")
+    for k in LAPACK_CHILD_DROP_ENV:               # ... with the other thread counts, exactly as bench.py starts the child
+        env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--lapack-child"], capture_output=True, text=True,
                        timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-500:]
