@@ -83,7 +83,7 @@ const char *lsx_last_error(void);
  *   "panel"         0 = per-column launches (the fallback after an exchange time-out), 3 = one launch per panel,
  *                   device-scope pivot exchange (panels taller than one XCD holds, multi-device driver),
  *                   4 = one launch per panel on ONE XCD with the exchange in that XCD's L2 [4]
- *                   (1, 2: superseded kernels, only in `make DIAG=1` builds)
+ *                   (1, 2: superseded kernels, removed; rejected with LSX_ERR_ARG)
  *   "lookahead"     0 = sequential driver, 1 = the next panel is factored on a side stream under the trailing
  *                   update [1]
  *   "lookahead_min" smallest n that takes the look-ahead driver; 0 = the measured break-even: 2048 in fp64 and
@@ -95,9 +95,6 @@ const char *lsx_last_error(void);
  *                   in one launch at the end
  *   "getri_pairs"   inverse / many-right-hand-side solve at large regular orders: 1 = two 128-row blocks per trailing
  *                   update (depth 256, same bits, 8192^2 inverse 17.6 -> 15.8 ms) [1], 0 = one
- *   "panel_col"     XCD panels of up to 4096 rows: 0 = rows distributed over the workgroups [0], 1 = columns distributed
- *                   (an independent second implementation, slower: kept as a cross-check; "panel_col_wt" = 1 runs it
- *                   with write-through stores, lsx_get_option "panel_col_launches" counts the panels it took)
  *   "gemm_waves", "gemm_stagger", "panel_rt", "panel_nt", "hybrid", "xrows_limit", "rref_blocked",
  *   "getri_structured"                      tuning / cross-check switches, see DESIGN.md
  *   "panel_spin_limit", "trsv_spin_limit", "chain_wait_limit"   bounded-spin limits (tests inject time-outs)

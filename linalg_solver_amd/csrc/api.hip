@@ -330,15 +330,12 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
         OnSide(lsx_handle_t h_, hipStream_t s) : h(h_), keep(h_->stream) { h->stream = s; }
         ~OnSide() { h->stream = keep; }
     };
-    // one exchange area serves either XCD panel: the row-distributed one clears and uses its first area_x bytes, the
-    // column-distributed one needs its head (inside those bytes) cleared and the multiplier buffer behind it as it is
+    // exchange area of the XCD panel (kernels_panel_x.hip) sized for the tallest panel; each launch needs it all zero
     const size_t area_x = panel_x_area_bytes(h, n - k0, sizeof(T));
-    const size_t area_c = h->panel_col ? panel_c_area_bytes(h, n - k0, sizeof(T)) : 0;
-    const size_t area = area_x == 0 ? 0 : (area_c > area_x ? area_c : area_x);
     const size_t pass_bytes = pad256(256 + (size_t)nsteps * sizeof(int)), ctr_bytes = pad256((size_t)nsteps * 8 * sizeof(int));
     const size_t col0_bytes = pad256((size_t)nsteps * 2 * sizeof(int));
     const size_t words = pass_bytes + ctr_bytes + col0_bytes + pad256((size_t)nsteps * sizeof(int));
-    if (area == 0 || 3 * area + words > h->scratch_bytes) { set_error("getrf_lookahead_x: scratch"); return LSX_ERR_INTERNAL; }
+    if (area_x == 0 || 3 * area_x + words > h->scratch_bytes) { set_error("getrf_lookahead_x: scratch"); return LSX_ERR_INTERNAL; }
     LSX_TRY(grow(&h->moves_all, &h->moves_all_bytes, (size_t)nsteps * 2048));
     struct Restore {
         lsx_handle_t h; hipStream_t keep;
@@ -351,21 +348,16 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
     h->chain_info = d_info;
     JoinSide join{h, side, main_s, main_s};
     // three exchange areas in rotation (panel j uses area j % 3, cleared behind update j), then the words
-    char *wbase = (char *)h->scratch + 3 * area;
+    char *wbase = (char *)h->scratch + 3 * area_x;
     int *xcc_word = (int *)wbase;                    // 1 + XCC id of the panel's XCD (blocks = 0 mod 8 land on XCC 0)
     int *pass = (int *)(wbase + 256);                // per step: update workgroups that left the panel's XCD
     int *counters = (int *)(wbase + pass_bytes);     // per step: the update's eight strip queues
     int *col0 = (int *)(wbase + pass_bytes + ctr_bytes);   // per step: {ticket, finished tiles} of the update's tile column 0
     int *ready = (int *)(wbase + pass_bytes + ctr_bytes + col0_bytes);   // per step: block inverses finished (fused chain launch)
-    for (int s = 0; s < 3; ++s) {
-        LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)s * area, 0, area_x, main_s));
-        if (area_c && s < nsteps)   // the column-distributed kernel's flags and multiplier buffer: "unwritten"
-            LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)s * area + panel_c_ones_offset(h, sizeof(T)), 0xff,
-                                   panel_c_ones_bytes(n - k0 - s * nb, sizeof(T)), main_s));
-    }
+    for (int s = 0; s < 3; ++s) LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)s * area_x, 0, area_x, main_s));
     LSX_HIP(hipMemsetAsync(wbase, 0, words, main_s));
     LSX_HIP(hipMemsetD32Async((hipDeviceptr_t)xcc_word, 1, 1, main_s));
-    h->panel_area_stride = area;
+    h->panel_area_stride = area_x;
     h->panel_xcc_word = xcc_word;
     LSX_HIP(hipEventRecord(h->ev_start, main_s));
     LSX_HIP(hipStreamWaitEvent(side, h->ev_start, 0));
@@ -469,10 +461,7 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
         }
         // panel k is done with its exchange area and panel k+3 reuses it: cleared behind the update, off the path
         // HEAD -> update start -> panel k+1; the chain of panel k+3 waits for (a part of) update k+1, behind this
-        LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)(step % 3) * area, 0, area_x, main_s));
-        if (area_c && step + 3 < nsteps)   // ... and the multiplier buffer of the column-distributed kernel back to "unwritten"
-            LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)(step % 3) * area + panel_c_ones_offset(h, sizeof(T)), 0xff,
-                                   panel_c_ones_bytes(n - k0 - (step + 3) * nb, sizeof(T)), main_s));
+        LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)(step % 3) * area_x, 0, area_x, main_s));
         LSX_HIP(hipEventRecord(h->ev_next, main_s));
         // panel k's interchanges on the columns LEFT of it: behind the update, where this stream only waits for the next
         // HEAD (one launch for all panels at the very end was 0.3 ms of an 8192^2 factorisation, on the critical path).
@@ -522,7 +511,7 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
 int ensure_getrf_workspace(lsx_handle_t h, int n, size_t elem) {
     LSX_TRY(ensure_scratch(h, pad256(16 * ((size_t)n / 32 + 2)) + 2 * pad256(elem * 2 * (size_t)n) +
                                   ((size_t)n / 32 + 2) * 5248 + 8192 +
-                                  3 * std::max(panel_x_area_bytes(h, n, elem), h->panel_col ? panel_c_area_bytes(h, n, elem) : (size_t)0) + 16384 +
+                                  3 * panel_x_area_bytes(h, n, elem) + 16384 +
                                   ((size_t)n / 16 + 2) * 40));
     const size_t tinv_elems = (size_t)((h->nb * h->kblock + 63) / 64) * 64 * 64;
     return grow(&h->ws2, &h->ws2_bytes, 2 * pad256(tinv_elems * elem));   // x2: the look-ahead driver alternates
@@ -1055,12 +1044,10 @@ int lsx_set_option(lsx_handle_t h, const char *key, int value) {
         h->nb = value;
     } else if (!strcmp(key, "panel")) {
         LSX_ARG(value >= 0 && value <= 4);
-#ifndef LSX_DIAG_PANELS
         if (value == 1 || value == 2) {
-            set_error("panel modes 1 and 2 (superseded kernels) are only in the diagnostic build: make DIAG=1");
+            set_error("panel modes 1 and 2 (superseded kernels) were removed: use 0, 3 or 4");
             return LSX_ERR_ARG;
         }
-#endif
         h->panel_mode = value;
     } else if (!strcmp(key, "trsv")) {
         LSX_ARG(value >= 0 && value <= 2);
@@ -1110,15 +1097,6 @@ int lsx_set_option(lsx_handle_t h, const char *key, int value) {
     } else if (!strcmp(key, "trsv_spin_limit")) {   // tests: 0 makes the first unanswered poll a time-out
         LSX_ARG(value >= 0);
         h->spin_limit = value;
-    } else if (!strcmp(key, "panel_xcd")) {
-        LSX_ARG(value == 0 || value == 1);
-        h->panel_xcd = value;
-    } else if (!strcmp(key, "panel_col")) {   // XCD panel up to 4096 rows: 1 = columns over the workgroups (kernels_panel_c.hip; cross-check), 0 = rows
-        LSX_ARG(value == 0 || value == 1);
-        h->panel_col = value;
-    } else if (!strcmp(key, "panel_col_wt")) {   // tests: the column-distributed panel as if its workgroups were on several XCDs
-        LSX_ARG(value == 0 || value == 1);
-        h->panel_col_wt = value;
     } else if (!strcmp(key, "getri_pairs")) {   // 0: the inverse with one 128-row block per trailing update (cross-check: same bits)
         LSX_ARG(value == 0 || value == 1);
         h->getri_pairs = value;
@@ -1162,24 +1140,13 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value) {
     else if (!strcmp(key, "gemm_stagger")) *value = h->gemm_stagger;
     else if (!strcmp(key, "trsv")) *value = h->trsv_mode;
     else if (!strcmp(key, "panel_nt")) *value = h->panel_nt;
-    else if (!strcmp(key, "panel_xcd")) *value = h->panel_xcd;
     else if (!strcmp(key, "chain_wait_limit")) *value = h->chain_wait_limit;
     else if (!strcmp(key, "rref_first_fast")) *value = h->rref_first_fast;
     else if (!strcmp(key, "chain_fused")) *value = h->chain_fused;
     else if (!strcmp(key, "left_per_step")) *value = h->left_per_step;
     else if (!strcmp(key, "getri_pairs")) *value = h->getri_pairs;
-    else if (!strcmp(key, "panel_col")) *value = h->panel_col;
-    else if (!strcmp(key, "panel_col_launches")) *value = (int)(h->panel_col_launches & 0x7fffffff);
-    else if (!strcmp(key, "panel_col_wt")) *value = h->panel_col_wt;
     else if (!strcmp(key, "rref_first_used")) *value = h->rref_first_used;
     else if (!strcmp(key, "panel_fallbacks")) *value = h->panel_fallbacks;
-    else if (!strcmp(key, "diag_panels")) {
-#ifdef LSX_DIAG_PANELS
-        *value = 1;
-#else
-        *value = 0;
-#endif
-    }
     else if (!strcmp(key, "num_cu")) *value = h->num_cu;
     else { set_error("unknown option '%s'", key); return LSX_ERR_ARG; }
     return LSX_OK;
@@ -1655,8 +1622,7 @@ int lsx_panel_f64_dev(lsx_handle_t h, int m, int jb, double *dP, int ldp, int ro
                       int *d_info) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && m >= 1 && jb >= 1 && jb <= 256 && dP && d_ipiv && ldp >= jb);
-    LSX_TRY(ensure_scratch(h, std::max({pad256(16 * ((size_t)m / 32 + 2)) + ((size_t)m / 32 + 2) * 5248 + 8192, panel_x_area_bytes(h, m, 8) + 4096,
-                                        h->panel_col ? panel_c_area_bytes(h, m, 8) + 8192 : (size_t)0})));
+    LSX_TRY(ensure_scratch(h, std::max(pad256(16 * ((size_t)m / 32 + 2)) + ((size_t)m / 32 + 2) * 5248 + 8192, panel_x_area_bytes(h, m, 8) + 4096)));
     return launch_panel<double>(h, m, jb, dP, ldp, row0, d_ipiv, d_info);
 }
 int lsx_laswp_f64_dev(lsx_handle_t h, int ncols, double *dA, int lda, int row0, int jb,

@@ -82,16 +82,14 @@ struct lsx_handle_s {
     hipStream_t stream = nullptr;  // stream in use (own or borrowed)
     hipStream_t side_stream = nullptr;  // high-priority stream for the look-ahead panel
     hipEvent_t ev_panel = nullptr, ev_next = nullptr, ev_start = nullptr, ev_done = nullptr;
-    // look-ahead with a CU partition (lookahead = 2): the trailing update runs on a stream masked to
-    // one set of CUs, the panel on a stream masked to the others, so both are resident at once
     // tunables
     int nb = 128;        // panel width (<= 128)
     int kblock = 1;      // panels per trailing update: update depth K = kblock * nb
-    int panel_mode = 4;  // 0 = per-column launches, 1 = cooperative, 2 = blocked (experimental), 3 = pipelined (device-scope exchange), 4 = XCD-scope exchange on one XCD (taller panels than an XCD holds: 3)
-    int lookahead = 1;   // 0: off; 1: panel k+1 on a high-priority side stream under the update of step k (fp64 n >= 7168, fp32 n >= 10240; bit-identical); 2: the variant with the update and the panel on disjoint CU sets; 3 = 1
+    int panel_mode = 4;  // 0 = per-column launches, 3 = pipelined (device-scope exchange), 4 = XCD-scope exchange on one XCD (taller panels than an XCD holds: 3)
+    int lookahead = 1;   // 0: off; 1: panel k+1 on a high-priority side stream under the update of step k (fp64 n >= 7168, fp32 n >= 10240; bit-identical)
     int lookahead_min = 0; // smallest n the look-ahead driver takes (0 = measured default: 7168 fp64, 10240 fp32)
-    int panel_rt = 4;     // rows per thread in the cooperative panel
-    int panel_nt = 0;     // threads per workgroup in the cooperative panel (0 = choose by panel height)
+    int panel_rt = 4;     // rows per thread in the pipelined panel (mode 3)
+    int panel_nt = 0;     // threads per workgroup in the pipelined panel (0 = choose by panel height)
     int trsv_mode = 2;    // few-RHS solve: 2 = 128-row steps + helper workgroups (default), 1 = one cooperative launch per direction with 64-row steps, 0 = one launch per 128-row step
     int gemm_stagger = 0; // trailing update: start delay of every second resident workgroup, units of 8128 clocks
     int gemm_waves = 0;   // waves per workgroup in the trailing-update kernel (0 = auto; 4: 64x64 per wave, 8: 64x32)
@@ -102,10 +100,6 @@ struct lsx_handle_s {
     int *gemm_counters = nullptr; // gemm_counter_sets x 8 ints in scratch, zeroed by the driver
     int gemm_counter_sets = 0, gemm_counter_set = 0;
     int *gemm_pass_word = nullptr;   // incremented by every workgroup that leaves because it sits on the avoided XCD
-    long long panel_col_launches = 0;   // how many panels the column-distributed kernel took (tests: it really ran)
-    int panel_col_wt = 0;            // tests: 1 = run it as if its workgroups were on several XCDs (write-through stores)
-    int panel_col = 0;               // XCD panel up to 4096 rows: 1 = columns distributed over the workgroups (kernels_panel_c.hip: an independent
-                                     // second implementation, slower -- DESIGN 5 -- kept as a cross-check), 0 = rows (kernels_panel_x.hip)
     int gemm_kshift = 0;             // next gemm launches: the k index starts at this offset and wraps (getri_dev)
     int getri_pairs = 1;             // inverse: two 128-row blocks per trailing update (K = 256), same bits
     int left_per_step = 1;           // XCD look-ahead driver: a panel's interchanges left of it trail its step (0: all at the end)
@@ -120,7 +114,6 @@ struct lsx_handle_s {
     int gemm_queue_used = 0;         // set by the last launch_gemm_*: 1 = its interior went through the queue
     void *moves_all = nullptr;       // look-ahead driver with the XCD-scope panel: one gather list per panel
     size_t moves_all_bytes = 0;
-    int panel_xcd = 0;    // 1: pipelined panel with the exchange at XCD scope (<= 32 workgroups on one XCD)
     int panel_debug = 0;  // 1: stamped diagnostic panel kernel (tools/kbench.py)
     // set by the LU drivers: updates narrower than 16 columns also take the MFMA kernel, so that a column sees the
     // same summation order whichever driver (sequential / look-ahead) splits the trailing matrix around it
@@ -173,9 +166,6 @@ namespace lsx {
 
 int ensure_ws(lsx_handle_t h, size_t bytes);
 int ensure_getrf_workspace(lsx_handle_t h, int n, size_t elem);
-size_t panel_c_area_bytes(lsx_handle_t h, int m, size_t elem);   // exchange area of the column-distributed XCD panel (contains the row-distributed one's)
-size_t panel_c_ones_offset(lsx_handle_t h, size_t elem);          // where its 0xff-filled part starts ...
-size_t panel_c_ones_bytes(int m, size_t elem);                    // ... and how long it is for a panel of m rows
 // XCD-scope panel under the reference's first-non-zero pivot rule (kernels_panel_x.hip); 1 = shape not served
 int panel_xcd_first(lsx_handle_t h, int m, int jb, double *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, double tol);
 template <typename T>

@@ -153,21 +153,11 @@ int panel_percolumn(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
 }
 
 template <typename T>
-int panel_cooperative(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0,
-                      int32_t *d_ipiv, int *d_info);
-template <typename T>
-int panel_blocked(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv,
-                  int *d_info);
-
-template <typename T>
 int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv,
                     int *d_info);
 
 template <typename T>
 int panel_xcd(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info);
-
-template <typename T>
-int panel_col(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info);
 
 template <typename T>
 int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t *d_ipiv,
@@ -177,27 +167,13 @@ int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t
     ProfScope ps(h, LSX_PROF_PANEL, 0, 2.0 * sizeof(T) * m * (double)jb);
     // the panel's first column is global column row0 (square LU: panel starts on the diagonal)
     if (h->panel_mode == 4) {   // one XCD; taller panels than it holds take the device-scope kernel
-        if (h->panel_col && !h->panel_debug) {   // columns distributed over the workgroups (kernels_panel_c.hip)
-            const int rc = panel_col<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);
-            if (rc != 1) return rc;
-        }
         const int r = panel_xcd<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);   // rows distributed, pivot exchange in the L2
         if (r != 1) return r;
     }
     if (h->panel_mode >= 3) {
         const int r = panel_pipelined<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);
-        if (r != 1) return r;  // 1 = shape not supported: try the older cooperative kernel
+        if (r != 1) return r;  // 1 = shape not supported: per-column launches
     }
-#ifdef LSX_DIAG_PANELS   // make DIAG=1: the superseded cooperative / blocked kernels as cross-checks
-    if (h->panel_mode == 2) {
-        const int r = panel_blocked<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);
-        if (r != 1) return r;  // 1 = shape not supported: try the unblocked cooperative kernel
-    }
-    if (h->panel_mode >= 1) {
-        const int r = panel_cooperative<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);
-        if (r != 1) return r;  // 1 = shape not supported by the cooperative kernel
-    }
-#endif
     return panel_percolumn<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);
 }
 

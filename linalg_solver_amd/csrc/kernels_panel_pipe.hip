@@ -1,5 +1,5 @@
 // Pipelined cooperative panel factorisation: the same one-launch, register-resident,
-// implicit-pivoting scheme as kernels_panel_coop.hip, re-cut so that the chain that limits a
+// implicit-pivoting scheme as round 1's cooperative panel, re-cut so that the chain that limits a
 // column -- header visible -> winner known -> pivot row fetched -> multipliers -> next column
 // updated -> next candidate -> next header stored -- runs inside ONE wave with no LDS round
 // trip and no barrier on it.
@@ -42,17 +42,12 @@ constexpr int XLOAD = 16;  // sc1: device scope
 constexpr int PP_STAGGER = 4;  // s_sleep units (64 clk) between the two shots at a block start
 
 // KS = header slots per polling lane (G <= 64 * KS)
-// XCD = true: the exchange runs at XCD scope.  Only the workgroups with blockIdx.x % 8 == 0 take part (round-robin
-// dispatch puts them on one XCD); their header / granule stores are PLAIN stores, which stay in that XCD's L2,
-// and the polling loads bypass L1 only (`sc1`), so one hop costs an L2 round trip instead of a trip through
-// the fabric.  Placement is verified, never assumed: every participant publishes its XCC id device-scope
-// before column 0 and a panel whose participants do not share one id runs the device-scope protocol instead.
-template <typename T, int RT, int NT, int KS, bool DBG, bool XCD>
+template <typename T, int RT, int NT, int KS, bool DBG>
 __device__ __forceinline__ void panel_pipe_body(const int G, const int g, int m, int jb, T *__restrict__ P, int ldp,
                                                 int row0, int col0, int32_t *__restrict__ ipiv,
                                                 int *__restrict__ info, char *hdr, XGran *xrow, int *status,
                                                 unsigned long long *dbg, int2 *__restrict__ moves) {
-    constexpr int XSTORE = XCD ? 0 : 16;   // cache policy of the exchange stores: plain (L2) or sc1 (write-through)
+    constexpr int XSTORE = 16;   // cache policy of the exchange stores: sc1 (write-through)
     constexpr int NTY = NT / 16;   // thread rows; the owners of one column are NTY consecutive lanes
     constexpr int RB = NTY * RT;   // panel rows per workgroup
     constexpr int NONE = 0x7fffffff;
@@ -183,8 +178,8 @@ __device__ __forceinline__ void panel_pipe_body(const int G, const int g, int m,
     // after its last shot are exactly the 8 granule stores of publish_row (always 8, see there), so
     // "at most 8 outstanding" means both shots are complete without waiting for the stores'
     // acknowledgements.  Nothing touches the shot registers between the asm loads and this wait (the
-    // "+v" operands tie them in place); the bit-identity tests against panel mode 1 on the GPU are
-    // the regression check for this hand-scheduled section.
+    // "+v" operands tie them in place); the bit-identity tests against panel modes 0 and 4 on the GPU
+    // are the regression check for this hand-scheduled section.
     auto shots_wait = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int k = 0; k < KS; ++k) asm volatile("s_waitcnt vmcnt(8)" : "+v"(hA[k]), "+v"(hB[k]));
@@ -222,12 +217,8 @@ __device__ __forceinline__ void panel_pipe_body(const int G, const int g, int m,
                         const int offc = off + 16 * c;
                         // s_nop: a store wider than 64 bits reads its data registers for two more
                         // cycles (hipcc pads its own stores; it does not look inside asm)
-                        if (XCD)
-                            asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1"
-                                         : : "v"(v), "v"(offc), "s"(d_row));
-                        else
-                            asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen sc1\n\ts_nop 1"
-                                         : : "v"(v), "v"(offc), "s"(d_row));
+                        asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen sc1\n\ts_nop 1"
+                                     : : "v"(v), "v"(offc), "s"(d_row));
                     }
                 }
         }
@@ -516,55 +507,14 @@ __global__ __launch_bounds__(NT, NT / 256) void panel_pipe_kernel(int m, int jb,
                                                                   XGran *xrow, int *status,
                                                                   unsigned long long *dbg,
                                                                   int2 *__restrict__ moves) {
-    panel_pipe_body<T, RT, NT, KS, DBG, false>(gridDim.x, blockIdx.x, m, jb, P, ldp, row0, col0, ipiv, info, hdr, xrow,
-                                               status, dbg, moves);
+    panel_pipe_body<T, RT, NT, KS, DBG>(gridDim.x, blockIdx.x, m, jb, P, ldp, row0, col0, ipiv, info, hdr, xrow,
+                                        status, dbg, moves);
 }
 
-// The XCD-scope launch: 8 * G workgroups, the G with blockIdx.x % 8 == 0 take part.  `xcc` (G words, zero at
-// launch) is the placement handshake: participant g stores 1 + its XCC id write-through, everybody reads all G
-// (bounded spin) and takes the XCD-scope protocol only if all ids agree -- the decision is a function of the
-// same G words for every participant, so they all take the same branch.
-template <typename T, int RT, int NT, int KS, bool DBG>
-__global__ __launch_bounds__(NT, NT / 256) void panel_pipe_xcd_kernel(int m, int jb, T *__restrict__ P, int ldp,
-                                                                      int row0, int col0,
-                                                                      int32_t *__restrict__ ipiv,
-                                                                      int *__restrict__ info, char *hdr,
-                                                                      XGran *xrow, int *status,
-                                                                      unsigned long long *dbg,
-                                                                      int2 *__restrict__ moves, int *xcc) {
-    if (blockIdx.x & 7) return;
-    const int G = gridDim.x >> 3, g = blockIdx.x >> 3;
-    __shared__ int s_same;
-    if (threadIdx.x < 64) {
-        unsigned id;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(id));
-        const int lane = threadIdx.x;
-        if (lane == 0) __hip_atomic_store(&xcc[g], (int)id + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        bool pend = lane < G, same = true;
-        int spins = 0;
-        while (__any(pend)) {
-            const int v = __hip_atomic_load(&xcc[lane < G ? lane : 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (pend && v != 0) { pend = false; same = v == (int)id + 1; }
-            if (++spins > SPIN_LIMIT) { same = false; break; }
-        }
-        const bool all_same = !__any(!same);
-        if (lane == 0) {
-            s_same = all_same ? 1 : 0;
-            if (DBG && dbg) dbg[g * 8 + 7] = ((unsigned long long)id << 8) | (all_same ? 1u : 0u);
-        }
-    }
-    __syncthreads();
-    if (s_same)
-        panel_pipe_body<T, RT, NT, KS, DBG, true>(G, g, m, jb, P, ldp, row0, col0, ipiv, info, hdr, xrow, status, dbg, moves);
-    else
-        panel_pipe_body<T, RT, NT, KS, DBG, false>(G, g, m, jb, P, ldp, row0, col0, ipiv, info, hdr, xrow, status, dbg, moves);
-}
-
-template <typename T, int RT, int NT, int KS, bool XCDL>
+template <typename T, int RT, int NT, int KS>
 static int panel_pipe_launch(lsx_handle_t h, int G, int m, int jb, T *P, int ldp, int row0, int col0,
                              int32_t *d_ipiv, int *d_info) {
-    // exchange area in scratch: status (+ the XCC handshake words at +64) | headers[2][G] (HDR_STRIDE apart) |
-    // granule rows[2][G][128]
+    // exchange area in scratch: status | headers[2][G] (HDR_STRIDE apart) | granule rows[2][G][128]
     const size_t hdr_bytes = (size_t)2 * G * HDR_STRIDE;
     const size_t need = 256 + hdr_bytes + (size_t)2 * G * PC_COLS * sizeof(XGran);
     const size_t dbg_off = (need + 255) & ~(size_t)255;
@@ -577,28 +527,18 @@ static int panel_pipe_launch(lsx_handle_t h, int G, int m, int jb, T *P, int ldp
     }
     char *base = (char *)h->scratch + base_off;
     int *status = (int *)base;
-    int *xcc = (int *)(base + 64);
     char *hdr = base + 256;
     XGran *xrow = (XGran *)(base + 256 + hdr_bytes);
     // status word, headers AND granules are zero at EVERY launch (epoch 0 never matches): cleared here, or
     // by the look-ahead driver beside the previous panel so that the memset is not on the panel-to-panel chain
     if (!driver_clears) LSX_HIP(hipMemsetAsync(base, 0, h->panel_debug ? total : need, h->stream));
     unsigned long long *dbg = h->panel_debug ? (unsigned long long *)(base + dbg_off) : nullptr;
-    if constexpr (XCDL) {
-        if (h->panel_debug)
-            hipLaunchKernelGGL((panel_pipe_xcd_kernel<T, RT, NT, KS, true>), dim3(8 * G), dim3(NT), 0, h->stream, m, jb, P,
-                               ldp, row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)h->moves, xcc);
-        else
-            hipLaunchKernelGGL((panel_pipe_xcd_kernel<T, RT, NT, KS, false>), dim3(8 * G), dim3(NT), 0, h->stream, m, jb, P,
-                               ldp, row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)h->moves, xcc);
-    } else {
-      if (h->panel_debug) {
+    if (h->panel_debug) {
         hipLaunchKernelGGL((panel_pipe_kernel<T, RT, NT, KS, true>), dim3(G), dim3(NT), 0, h->stream, m, jb, P, ldp,
                            row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)h->moves);
-      } else {
+    } else {
         hipLaunchKernelGGL((panel_pipe_kernel<T, RT, NT, KS, false>), dim3(G), dim3(NT), 0, h->stream, m, jb, P, ldp,
                            row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)h->moves);
-      }
     }
     LSX_HIP(hipGetLastError());
     h->moves_valid = true;
@@ -616,19 +556,6 @@ int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
     int nt = h->panel_nt, rt = h->panel_rt;
     auto rows = [](int nt_, int rt_) { return nt_ / 16 * rt_; };
     auto wgs = [&](int nt_, int rt_) { return (m + rows(nt_, rt_) - 1) / rows(nt_, rt_); };
-    // XCD-scope exchange (option panel_xcd): at most 32 workgroups, one per CU of one XCD -- 256-row slices
-    // (512 threads x 8 rows) above 4096 rows, 128-row slices (512 x 4) down to 2048, 64-row slices below
-    if (h->panel_xcd && m <= 32 * 256) {
-        int xnt = 512, xrt = 8;
-        if (m <= 32 * 64) { xnt = 256; xrt = 4; }
-        else if (m <= 32 * 128) { xnt = 512; xrt = 4; }
-        const int G = wgs(xnt, xrt);
-#define LSX_PPX(RT_, NT_)                          \
-        if (xrt == RT_ && xnt == NT_)              \
-            return panel_pipe_launch<T, RT_, NT_, 1, true>(h, G, m, jb, P, ldp, row0, col0, d_ipiv, d_info);
-        LSX_PPX(8, 512) LSX_PPX(4, 512) LSX_PPX(4, 256)
-#undef LSX_PPX
-    }
     if (h->panel_nt == 0) {  // measured: one header per polling lane (<= 64 workgroups) wins
         nt = 256, rt = 4;
         if (wgs(nt, rt) > 64) nt = 512;
@@ -640,7 +567,7 @@ int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
     const int ks = G <= 64 ? 1 : (G <= 128 ? 2 : 4);
 #define LSX_PP(RT_, NT_, KS_)                     \
     if (rt == RT_ && nt == NT_ && ks == KS_)      \
-        return panel_pipe_launch<T, RT_, NT_, KS_, false>(h, G, m, jb, P, ldp, row0, col0, d_ipiv, d_info);
+        return panel_pipe_launch<T, RT_, NT_, KS_>(h, G, m, jb, P, ldp, row0, col0, d_ipiv, d_info);
     LSX_PP(4, 256, 1) LSX_PP(4, 256, 2) LSX_PP(4, 256, 4)
     LSX_PP(4, 512, 1) LSX_PP(4, 512, 2) LSX_PP(4, 512, 4)
     LSX_PP(8, 512, 1) LSX_PP(8, 512, 2) LSX_PP(8, 512, 4)

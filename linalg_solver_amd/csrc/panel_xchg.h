@@ -1,6 +1,6 @@
 // Shared pieces of the one-launch panel kernels: the cross-CU exchange record formats and the
-// cross-lane (DPP / readlane) reductions.  Included by kernels_panel_coop.hip,
-// kernels_panel_pipe.hip and kernels_trsv.hip.
+// cross-lane (DPP / readlane) reductions.  Included by kernels_panel_pipe.hip, kernels_panel_x.hip,
+// kernels_trsv.hip and kernels_diag.hip.
 #pragma once
 #include "common.h"
 
@@ -40,21 +40,6 @@ template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v) {
     const int lo = dpp_i<CTRL>(__double2loint(v)), hi = dpp_i<CTRL>(__double2hiint(v));
     return __hiloint2double(hi, lo);
-}
-#define LSX_DPP_STEP(CTRL, v, i)                                         \
-    {                                                                    \
-        const double ov_ = dpp_d<CTRL>(v);                               \
-        const int oi_ = dpp_i<CTRL>(i);                                  \
-        const bool b_ = (ov_ > v) | ((ov_ == v) & (oi_ < i));            \
-        v = b_ ? ov_ : v;                                                \
-        i = b_ ? oi_ : i;                                                \
-    }
-// arg-max (largest v, lowest i on ties) over each 16-lane row
-__device__ __forceinline__ void row16_argmax(double &v, int &i) {
-    LSX_DPP_STEP(0xB1, v, i)   // quad_perm [1,0,3,2]
-    LSX_DPP_STEP(0x4E, v, i)   // quad_perm [2,3,0,1]
-    LSX_DPP_STEP(0x141, v, i)  // row_half_mirror
-    LSX_DPP_STEP(0x140, v, i)  // row_mirror
 }
 __device__ __forceinline__ double readlane_d(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),

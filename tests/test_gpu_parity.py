@@ -155,8 +155,7 @@ def test_getrf_matches_cpu_twin(la, n):
 def test_getrf_cooperative_panel_matches_cpu_twin(la, n):
     """The one-launch cooperative panels against the CPU twin, and against each other bit for bit: pipelined
     (mode 3, device-scope exchange) in every workgroup shape, XCD-scope (mode 4, the default) alone and under its
-    look-ahead schedule, update depth 256 -- and, in the diagnostic build (make DIAG=1), the two superseded
-    kernels (modes 1 and 2), which perform the same fused multiply-adds in the same order."""
+    look-ahead schedule, update depth 256."""
     from linalg_solver_amd import dense, gen
 
     h = la.default_handle()
@@ -180,11 +179,6 @@ def test_getrf_cooperative_panel_matches_cpu_twin(la, n):
             LUx, ipivx, infox = run(panel=4, lookahead=look)
             assert infox == 0 and np.array_equal(ipivx, base[1]) and np.array_equal(LUx, base[0]), \
                 f"XCD-scope panel lookahead={look} differs"
-        if h.get_option("diag_panels"):
-            for mode, rt, nt in ((1, 4, 256), (1, 8, 512), (1, 2, 1024), (2, 4, 0)):
-                LUd, ipivd, infod = run(panel=mode, panel_rt=rt, panel_nt=nt, lookahead=0)
-                assert infod == 0 and np.array_equal(ipivd, base[1]) and np.array_equal(LUd, base[0]), \
-                    f"superseded panel mode {mode} rt={rt} nt={nt} differs"
         # the update depth (K = 128 vs 256) changes summation order only
         deep = run(panel=3, panel_nt=0, panel_rt=4, lookahead=0, kblock=2)
     finally:
@@ -200,14 +194,12 @@ def test_getrf_cooperative_panel_matches_cpu_twin(la, n):
     assert relerr(LU, oLU) < TOL64
 
 
-@pytest.mark.parametrize("mode", [1, 2, 3, 4])
+@pytest.mark.parametrize("mode", [0, 3, 4])
 @pytest.mark.parametrize("n", [16, 200, 513])
 def test_getrf_cooperative_panel_integer_and_singular(la, n, mode):
     from linalg_solver_amd import dense, gen
 
     h = la.default_handle()
-    if mode in (1, 2) and not h.get_option("diag_panels"):
-        pytest.skip("superseded panel kernels are only in the diagnostic build (make DIAG=1)")
     h.set_option("panel", mode)
     try:
         A, _ = gen.system(gen.INT5, 60 + n, n)
@@ -1124,15 +1116,15 @@ def test_two_blocks_per_update_in_the_block_sweeps_keep_the_bits(la, dev, n, dt)
     assert float((A0 @ outs[1][1] - B0).abs().max()) < tol * 10
 
 
-@pytest.mark.parametrize("wt", [0, 1])
-def test_column_distributed_panel_is_a_second_implementation_with_the_same_bits(la, dev, wt):
-    """kernels_panel_c.hip (option panel_col = 1): the XCD panel cut the other way -- a workgroup owns four COLUMNS of all
-    rows, left-looking inside the panel, multipliers handed on through an all-ones-initialised buffer in the L2 -- shares no
-    exchange code with kernels_panel_x.hip and must reproduce its factors, pivots, info and gather list bit for bit:
-    ragged heights and widths, the reference's tie-rich integer distribution, a zero column (the slow path of the pivot
-    search), one to sixteen rows per lane, plain and write-through stores (wt), and whole factorisations under the
-    look-ahead driver (which hands panels above 4096 rows to the row-distributed kernel).  It is slower and off by
-    default: this test is what it is kept for."""
+def test_xcd_panel_matches_the_two_reference_panels_bit_for_bit(la, dev):
+    """The default XCD panel (mode 4, kernels_panel_x.hip) against the two independent implementations kept beside it:
+    the device-scope pipelined panel (mode 3) and the per-column launches (mode 0, the fallback after an exchange
+    time-out), on ragged heights and widths.  Modes 4 and 3 agree bit for bit in factors, pivots, info and gather list
+    (mode 0 emits none), also on the reference's tie-rich integer distribution with a zero column (the slow path of the
+    pivot search).  Mode 0 agrees with them bit for bit, ties included, except on a column with no non-zero candidate:
+    it keeps the diagonal row there (as LAPACK does) where modes 3 and 4 record another, equally valid, zero row.  With the
+    zero column planted, mode 0 is held to the same info and the same pivots before that column.  Whole factorisations:
+    the default driver against mode 3 without look-ahead."""
     import torch
 
     from linalg_solver_amd import gen
@@ -1141,47 +1133,48 @@ def test_column_distributed_panel_is_a_second_implementation_with_the_same_bits(
     shapes = [(4096, 128), (4000, 100), (2500, 128), (2049, 5), (1025, 4), (1000, 3), (384, 128), (257, 100), (129, 128),
               (100, 17), (64, 1), (5, 5), (1, 1)]
     try:
-        h.set_option("panel_col_wt", wt)
         for m, jb in shapes:
             for kind in (gen.U11, gen.INT5):
                 P0 = torch.empty(m, jb, dtype=torch.float64, device="cuda")
                 dev.fill_(P0, kind, 3)
-                if kind == gen.INT5 and m >= 100:
-                    P0[:, min(3, jb - 1)] = 0
+                zc = min(3, jb - 1) if kind == gen.INT5 and m >= 100 else None
+                if zc is not None:
+                    P0[:, zc] = 0
                 outs = []
-                for pc in (0, 1):
-                    h.set_option("panel_col", pc)
-                    before = h.get_option("panel_col_launches")
+                for mode in (4, 3, 0):
+                    h.set_option("panel", mode)
                     P = P0.clone()
                     ipiv = torch.zeros(jb, dtype=torch.int32, device="cuda")
                     info = torch.zeros(1, dtype=torch.int32, device="cuda")
                     dev.panel_(P, 0, ipiv, info)
                     mv = torch.zeros(512, dtype=torch.int32, device="cuda")
-                    assert dev.panel_moves_(mv)
+                    listed = dev.panel_moves_(mv)
                     torch.cuda.synchronize()
-                    assert h.get_option("panel_col_launches") - before == pc, "the wrong kernel took the panel"
+                    assert listed == (mode != 0), (m, jb, kind, mode)
                     outs.append((P, ipiv, int(info.item()), mv))
-                assert outs[0][2] == outs[1][2], (m, jb, kind)
-                assert torch.equal(outs[0][1], outs[1][1]), (m, jb, kind)
-                assert torch.equal(outs[0][0], outs[1][0]), (m, jb, kind)
+                for k, mode in ((1, 3), (2, 0)):
+                    assert outs[0][2] == outs[k][2], (m, jb, kind, mode)
+                    if mode == 0 and zc is not None:
+                        assert torch.equal(outs[0][1][:zc], outs[k][1][:zc]), (m, jb, kind, mode)
+                        continue
+                    assert torch.equal(outs[0][1], outs[k][1]), (m, jb, kind, mode)
+                    assert torch.equal(outs[0][0], outs[k][0]), (m, jb, kind, mode)
                 assert torch.equal(outs[0][3], outs[1][3]), (m, jb, kind)
         for n, dt in ((1000, torch.float64), (2304, torch.float64), (5000, torch.float64), (3000, torch.float32)):
             A0 = torch.empty(n, n, dtype=dt, device="cuda")
             dev.fill_(A0, gen.U11, 77 + n)
             res = []
-            for pc in (0, 1):
-                h.set_option("panel_col", pc)
-                before = h.get_option("panel_col_launches")
+            for mode, look in ((DEFAULT_PANEL, 1), (3, 0)):
+                h.set_option("panel", mode)
+                h.set_option("lookahead", look)
                 A = A0.clone()
                 ipiv, info = dev.getrf_(A)
                 torch.cuda.synchronize()
-                took = h.get_option("panel_col_launches") - before
-                assert (took > 0) == (pc == 1)
                 res.append((A, ipiv, int(info.item())))
             assert res[0][2] == res[1][2] == 0 and torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][0], res[1][0]), n
     finally:
-        h.set_option("panel_col", 0)
-        h.set_option("panel_col_wt", 0)
+        h.set_option("panel", DEFAULT_PANEL)
+        h.set_option("lookahead", 1)
 
 
 def test_chain_wait_timeout_reaches_info_and_the_host_entry_point_recovers(la, dev):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel | lu [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -97,33 +97,13 @@ def main():
                     tmin, tmed = timeit(run, reps=5, warm=2)
                     tcopy, _ = timeit(lambda: P.copy_(P0), reps=5, warm=2)
                     t = tmin - tcopy
-                    print(f"panel3 m={m} nt={nt} rt={rt}: {t * 1e3:.1f} us  ({t * 1e3 / args.nb:.2f} us/col) info={int(info.item())} fallbacks(diag)={dev.h.get_option('diag_panels')}", flush=True)
+                    print(f"panel3 m={m} nt={nt} rt={rt}: {t * 1e3:.1f} us  ({t * 1e3 / args.nb:.2f} us/col) info={int(info.item())}", flush=True)
                 except Exception as e:
                     print(f"panel3 m={m} nt={nt} rt={rt}: failed ({e})", flush=True)
         dev.h.set_option("panel_nt", 0); dev.h.set_option("panel_rt", 4); dev.h.set_option("panel", 4)
-    if "panel" in args.what:
-        for mode, nt, rt in ((1, 256, 4), (1, 512, 4)):
-            dev.h.set_option("panel", mode)
-            dev.h.set_option("panel_rt", rt)
-            dev.h.set_option("panel_nt", nt)
-            for m in (args.n, args.n // 2, args.n // 8, 256):
-                P0 = torch.empty(m, args.nb, dtype=torch.float64, device="cuda")
-                dev.fill_(P0, gen.U11, 3)
-                ipiv = torch.zeros(args.nb, dtype=torch.int32, device="cuda")
-                info = torch.zeros(1, dtype=torch.int32, device="cuda")
-                P = P0.clone()
-
-                def run():
-                    P.copy_(P0)
-                    dev.panel_(P, 0, ipiv, info)
-                tmin, tmed = timeit(run, reps=5, warm=1)
-                tcopy, _ = timeit(lambda: P.copy_(P0), reps=5, warm=1)
-                t = tmin - tcopy
-                print(f"panel mode={mode} nt={nt} rt={rt} m={m} nb={args.nb}: {t * 1e3:.1f} us  ({t * 1e3 / args.nb:.2f} us/col)  "
-                      f"{2 * 8 * m * args.nb / t / 1e6:.1f} GB/s", flush=True)
     if "panel3" in args.what:
         import numpy as np
-        # pipelined panel (mode 3): bitwise check against mode 1, timing, then the stamped build
+        # pipelined panel (mode 3): bitwise check against mode 4, timing, then the stamped build
         dev.h.set_option("panel_rt", 4)
         for m in (args.n, args.n // 2, 1024, 384, 128, 100):
             for nbw in (args.nb, 100):
@@ -198,8 +178,8 @@ def main():
                       f"failures={nf}  xcc ids={sorted(set(ids))} (participant 0 on {ids[0]}, 1 on {ids[1]})", flush=True)
     if "panelx" in args.what or "pstamps" in args.what:
         import numpy as np
-        # device-scope pipelined panel (panel=3) / the same with XCD-scope stores (panel_xcd=1) / XCD kernel (panel=4)
-        variants = (("p3", 3, 0), ("p3x", 3, 1), ("p4", 4, 0))
+        # device-scope pipelined panel (panel=3) / XCD kernel (panel=4)
+        variants = (("p3", 3), ("p4", 4))
         dev.h.set_option("panel_nt", 0)
         dev.h.set_option("panel_rt", 4)
         dt = torch.float32 if args.f32 else torch.float64
@@ -209,23 +189,18 @@ def main():
                     P0 = torch.empty(m, nbw, dtype=dt, device="cuda")
                     dev.fill_(P0, kind, 3)
                     outs = []
-                    for nm, mode, xcd in variants:
+                    for nm, mode in variants:
                         dev.h.set_option("panel", mode)
-                        dev.h.set_option("panel_xcd", xcd)
                         P = P0.clone()
                         ipiv = torch.zeros(nbw, dtype=torch.int32, device="cuda")
                         info = torch.zeros(1, dtype=torch.int32, device="cuda")
                         dev.panel_(P, 0, ipiv, info)
                         torch.cuda.synchronize()
                         outs.append((P, ipiv.clone(), int(info.item())))
-                    res = []
-                    for k in (1, 2):
-                        same = torch.equal(outs[0][0], outs[k][0]) and torch.equal(outs[0][1], outs[k][1]) and outs[0][2] == outs[k][2]
-                        res.append(f"{variants[k][0]}={'same' if same else 'MISMATCH'}(info {outs[k][2]})")
-                    print(f"panelx check m={m} jb={nbw} kind={kind}: " + " ".join(res), flush=True)
-        for nm, mode, xcd in variants if "panelx" in args.what else ():
+                    same = torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]) and outs[0][2] == outs[1][2]
+                    print(f"panelx check m={m} jb={nbw} kind={kind}: p4={'same' if same else 'MISMATCH'}(info {outs[1][2]})", flush=True)
+        for nm, mode in variants if "panelx" in args.what else ():
             dev.h.set_option("panel", mode)
-            dev.h.set_option("panel_xcd", xcd)
             for m in (8192, 6144, 4096, 2048, 1024, 256):
                 P0 = torch.empty(m, args.nb, dtype=dt, device="cuda")
                 dev.fill_(P0, gen.U11, 3)
@@ -243,7 +218,6 @@ def main():
         names = ["own: headers+winner", "own: multipliers+granules", "own: update+choose+announce", "own: barrier",
                  "next wave: barrier wait", "next wave: far granules+update", "next wave: publish", "own: second block behind the barrier"]
         dev.h.set_option("panel", 4)
-        dev.h.set_option("panel_xcd", 0)
         dev.h.set_option("panel_debug", 1)
         for m in (8192, 4096, 2048, 256):
             rows = 64 * (1 if m <= 2048 else 2 if m <= 4096 else 4 if (m <= 8192 or not args.f32) else 8)
@@ -382,55 +356,6 @@ def main():
             dev.panel_(P, 0, ipiv, info)
         torch.cuda.synchronize()
         print(f"pmcpanel workload done: panel {m} x {args.nb}, bytes one way = {m * args.nb * 8}; calibration copy {m * m * 8} one way")
-    if "stamps" in args.what:
-        import numpy as np
-        names = ["1:col update+cand", "barrier A", "2:reduce+publish", "3:bulk update", "4a:poll headers",
-                 "4b:row granules", "barrier C", "5:multipliers"]
-        dev.h.set_option("panel", 1)
-        dev.h.set_option("panel_debug", 1)
-        for nt, rt, m in ((256, 4, args.n), (512, 4, args.n), (256, 4, 1024), (256, 4, 128)):
-            dev.h.set_option("panel_rt", rt)
-            dev.h.set_option("panel_nt", nt)
-            P = torch.empty(m, args.nb, dtype=torch.float64, device="cuda")
-            ipiv = torch.zeros(args.nb, dtype=torch.int32, device="cuda")
-            info = torch.zeros(1, dtype=torch.int32, device="cuda")
-            for rep in range(2):
-                dev.fill_(P, gen.U11, 3)
-                dev.panel_(P, 0, ipiv, info)
-            torch.cuda.synchronize()
-            G = (m + nt // 16 * rt - 1) // (nt // 16 * rt)
-            need = 256 + 2 * G * 512 + 2 * G * 128 * 16
-            off = (need + 255) & ~255
-            raw = np.frombuffer(dev.h.read_scratch(off, G * 64), dtype=np.uint64).reshape(G, 8).astype(np.float64)
-            us = raw / 100.0 / args.nb  # 100 MHz ticks -> us per column
-            print(f"stamps nt={nt} rt={rt} m={m} G={G}: per-column us (mean over WGs | max)   total {us.sum(1).mean():.2f}")
-            for i, nm in enumerate(names):
-                print(f"   {nm:22s} {us[:, i].mean():7.3f} | {us[:, i].max():7.3f}")
-        dev.h.set_option("panel_debug", 0)
-    if "stamps2" in args.what:
-        import numpy as np
-        names = ["1:candidates", "barrier A", "2:reduce+publish", "3:poll records", "3b:winner reduce+bcast",
-                 "barrier C", "4:multipliers+block update", "block end (per block/8)"]
-        dev.h.set_option("panel", 2)
-        dev.h.set_option("panel_debug", 1)
-        for m in (args.n, 1024, 128):
-            P = torch.empty(m, args.nb, dtype=torch.float64, device="cuda")
-            ipiv = torch.zeros(args.nb, dtype=torch.int32, device="cuda")
-            info = torch.zeros(1, dtype=torch.int32, device="cuda")
-            for rep in range(2):
-                dev.fill_(P, gen.U11, 3)
-                dev.panel_(P, 0, ipiv, info)
-            torch.cuda.synchronize()
-            G = (m + 127) // 128
-            need = 256 + 2 * G * 256 + 2 * 8 * 128 * 16
-            off = (need + 255) & ~255
-            raw = np.frombuffer(dev.h.read_scratch(off, G * 64), dtype=np.uint64).reshape(G, 8).astype(np.float64)
-            us = raw / 100.0 / args.nb
-            print(f"stamps2 (blocked) m={m} G={G}: per-column us (mean | max)   total {us.sum(1).mean():.2f}")
-            for i, nm in enumerate(names):
-                print(f"   {nm:28s} {us[:, i].mean():7.3f} | {us[:, i].max():7.3f}")
-        dev.h.set_option("panel_debug", 0)
-        dev.h.set_option("panel", 1)
     if "lu" in args.what:
         n = args.n
         A0 = torch.empty(n, n, dtype=torch.float32 if args.f32 else torch.float64, device="cuda")
