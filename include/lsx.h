@@ -185,6 +185,55 @@ int lsx_getrs_f32(lsx_handle_t h, int n, int nrhs, const float *LU, int lda,
 int lsx_gesv_f32(lsx_handle_t h, int n, int nrhs, const float *A, int lda, float *B, int ldb,
                  int *info, double *pivot_ratio);
 
+/* ---- transposed solves, norms and the condition estimate from the factors ---- */
+/* matrix norms of lsx_lange_* / lsx_gecon_* / lsx_rcond_*: max absolute column sum, max absolute row sum */
+enum { LSX_NORM_ONE = 0, LSX_NORM_INF = 1 };
+/* Solve A^T X = B (equivalently x A = b for rows) from the factors of A: U^T Y = B, L^T Z = Y, X[perm] = Z -- no
+ * second factorisation.  B (n x nrhs, row-major) is overwritten by X.  Arguments are validated as in lsx_getrs_*;
+ * right-hand sides are processed in groups of up to 8 columns (one launch per 128-row block step and group: the
+ * few-right-hand-side path, correct but not a throughput path for many columns).  Deterministic: two calls give
+ * identical bits. */
+int lsx_getrs_t_f64(lsx_handle_t h, int n, int nrhs, const double *LU, int lda, const int32_t *ipiv,
+                    double *B, int ldb);
+int lsx_getrs_t_f32(lsx_handle_t h, int n, int nrhs, const float *LU, int lda, const int32_t *ipiv,
+                    float *B, int ldb);
+/* The same on device pointers, asynchronous on the handle's stream. */
+int lsx_getrs_t_f64_dev(lsx_handle_t h, int n, int nrhs, const double *dLU, int lda, const int32_t *d_ipiv,
+                        double *dB, int ldb);
+int lsx_getrs_t_f32_dev(lsx_handle_t h, int n, int nrhs, const float *dLU, int lda, const int32_t *d_ipiv,
+                        float *dB, int ldb);
+/* *d_out (device double) = max absolute column sum (LSX_NORM_ONE) or row sum (LSX_NORM_INF) of the m x n matrix at
+ * dA (device pointer).  Sums are accumulated in fp64 in a fixed order (two passes, no floating-point atomics): two
+ * calls give identical bits; a NaN entry gives NaN.  m == 0 or n == 0 gives 0.  Asynchronous. */
+int lsx_lange_f64_dev(lsx_handle_t h, int norm, int m, int n, const double *dA, int lda, double *d_out);
+int lsx_lange_f32_dev(lsx_handle_t h, int norm, int m, int n, const float *dA, int lda, double *d_out);
+/* Reciprocal condition number *rcond = 1 / (anorm * est||A^-1||) in the 1- or the infinity-norm from the factors of
+ * A; anorm is that norm of the UNFACTORED matrix (LAPACK's gecon contract; lsx_lange_*).  The estimate is the
+ * iteration of LAPACK's lacn2 step for step: start x = 1/n, at most 5 iterations, the same stopping tests (sign
+ * vector unchanged; estimate not increased; x_jlast == |x_j|), the same final test with the alternating vector, the
+ * first index on ties -- 4 to 11 single-right-hand-side solves with A and A^T (for LSX_NORM_INF the two swap roles;
+ * the option "gecon_solves" reads back how many the last call took).  As in gecon the solves run on L and U alone:
+ * the interchanges permute the columns of the inverse and change neither norm, so ipiv is only checked for presence.
+ * fp32 factors: solves in fp32, norms and the estimate accumulated in fp64.  The estimate is a LOWER bound of
+ * ||A^-1||, so *rcond can exceed the true value, in practice by a small factor.
+ * Numerical outcomes are values, not statuses: n == 0 gives 1; anorm == 0, an exactly zero U_ii or a non-finite
+ * estimate give 0.  A NaN or negative anorm is LSX_ERR_ARG.  The host drives the iteration and reads one small record
+ * per step, so ALL FOUR forms synchronise the handle's stream (the solves and the vector steps run on it); *rcond is
+ * a host double in all four.  A time-out of the cooperative solve inside is LSX_ERR_INTERNAL, as from lsx_getrs_*,
+ * never a condition number. */
+int lsx_gecon_f64(lsx_handle_t h, int norm, int n, const double *LU, int lda, const int32_t *ipiv,
+                  double anorm, double *rcond);
+int lsx_gecon_f32(lsx_handle_t h, int norm, int n, const float *LU, int lda, const int32_t *ipiv,
+                  double anorm, double *rcond);
+int lsx_gecon_f64_dev(lsx_handle_t h, int norm, int n, const double *dLU, int lda, const int32_t *d_ipiv,
+                      double anorm, double *rcond);
+int lsx_gecon_f32_dev(lsx_handle_t h, int norm, int n, const float *dLU, int lda, const int32_t *d_ipiv,
+                      double anorm, double *rcond);
+/* One call for a host matrix: norm, factorisation, estimate; A is not modified.  *info as lsx_getrf_* (k + 1 for an
+ * exactly zero pivot: then *rcond = 0). */
+int lsx_rcond_f64(lsx_handle_t h, int norm, int n, const double *A, int lda, double *rcond, int *info);
+int lsx_rcond_f32(lsx_handle_t h, int norm, int n, const float *A, int lda, double *rcond, int *info);
+
 /* ---- device-pointer entry points (asynchronous on the handle's stream) ---- */
 /* d_info: device int (may be NULL).  d_ipiv: device int32[n].
  * *d_info < 0 after the call means the in-kernel pivot exchange timed out (LSX_ERR_INTERNAL

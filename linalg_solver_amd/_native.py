@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("LSX_LIB_OVERRIDE") or os.path.join(_HERE, "liblsx.so"
 PROF_BUCKETS = {"panel": 0, "laswp": 1, "trsm": 2, "gemm": 3, "other": 4, "gemm_skinny": 5}
 FILL_INT5, FILL_U11 = 0, 1
 PIVOT_FIRST, PIVOT_MAX = 0, 1
+NORM_ONE, NORM_INF = 0, 1
 
 
 class LsxError(RuntimeError):
@@ -64,6 +65,18 @@ _SIGS = {
     "lsx_getrf_f32_dev": [_vp, _i, _vp, _i, _vp, _vp],
     "lsx_getrs_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, _i],
     "lsx_rref_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, C.c_double, _i],
+    "lsx_getrs_t_f64": [_vp, _i, _i, _dp, _i, _ip, _dp, _i],
+    "lsx_getrs_t_f32": [_vp, _i, _i, _fp, _i, _ip, _fp, _i],
+    "lsx_getrs_t_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_getrs_t_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_lange_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp],
+    "lsx_lange_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp],
+    "lsx_gecon_f64": [_vp, _i, _i, _dp, _i, _ip, C.c_double, _dp],
+    "lsx_gecon_f32": [_vp, _i, _i, _fp, _i, _ip, C.c_double, _dp],
+    "lsx_gecon_f64_dev": [_vp, _i, _i, _vp, _i, _vp, C.c_double, _dp],
+    "lsx_gecon_f32_dev": [_vp, _i, _i, _vp, _i, _vp, C.c_double, _dp],
+    "lsx_rcond_f64": [_vp, _i, _i, _dp, _i, _dp, C.POINTER(_i)],
+    "lsx_rcond_f32": [_vp, _i, _i, _fp, _i, _dp, C.POINTER(_i)],
     "lsx_panel_f64_dev": [_vp, _i, _i, _vp, _i, _i, _vp, _vp],
     "lsx_laswp_f64_dev": [_vp, _i, _vp, _i, _i, _i, _vp],
     "lsx_trsm_lu_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _i],

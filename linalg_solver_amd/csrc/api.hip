@@ -901,6 +901,175 @@ static int gesv_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, T *B,
     return LSX_OK;
 }
 
+
+// ---------------------------------------------------------------- transposed solve, norms, condition estimate
+// A^T X = B from the factors (kernels_trsvt.hip).  Work space as in getrs_dev, so the two share what they grow.
+template <typename T>
+static int getrs_t_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, const int32_t *d_ipiv, T *B, int ldb) {
+    LSX_ARG(n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs && LU && d_ipiv && B);
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    if (n <= 128)   // one workgroup, interchanges included: no work space
+        return lu_solve_transposed<T>(h, n, nrhs, LU, lda, d_ipiv, nullptr, B, ldb, (T *)nullptr, (T *)nullptr,
+                                      (T *)nullptr, (T *)nullptr, (T *)nullptr);
+    const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
+    const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
+    const size_t vec = pad256(sizeof(T) * (size_t)n * 8);
+    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(int32_t) * n) + 3 * vec));
+    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, 2 * b64 + 2 * b128));
+    LSX_TRY(ensure_scratch(h, 8 * (size_t)n + 256));   // index arrays of the permutation conversion
+    int32_t *perm = (int32_t *)h->ws3;
+    T *W = (T *)((char *)h->ws3 + pad256(sizeof(int32_t) * n));
+    char *w2 = (char *)h->ws2;
+    LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
+    return lu_solve_transposed<T>(h, n, nrhs, LU, lda, d_ipiv, perm, B, ldb, (T *)w2, (T *)(w2 + b64), (T *)(w2 + 2 * b64),
+                                  (T *)(w2 + 2 * b64 + b128), W);
+}
+
+template <typename T>
+static int getrs_t_host(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, const int32_t *ipiv, T *B, int ldb) {
+    LSX_ARG(h && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs);
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(LU && ipiv && B);
+    const int ld = ld_for(n), ldx = ld_for(nrhs);
+    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(T) * (size_t)n * ldx) +
+                             pad256(sizeof(int32_t) * n) + 512));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    T *dB = c.take<T>((size_t)n * ldx);
+    int32_t *dp = c.take<int32_t>(n);
+    LSX_TRY(h2d<T>(h, n, n, LU, lda, dA, ld));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
+    LSX_HIP(hipMemcpyAsync(dp, ipiv, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+    LSX_TRY(getrs_t_dev<T>(h, n, nrhs, dA, ld, dp, dB, ldx));
+    LSX_TRY(d2h<T>(h, n, nrhs, dB, ldx, B, ldb));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+template <typename T>
+static int lange_dev(lsx_handle_t h, int norm, int m, int n, const T *dA, int lda, double *d_out) {
+    LSX_ARG((norm == LSX_NORM_ONE || norm == LSX_NORM_INF) && m >= 0 && n >= 0 && lda >= n && d_out);
+    LSX_ARG(m == 0 || n == 0 || dA);
+    LSX_TRY(ensure_scratch(h, lange_work_bytes(norm, m, n) + 256));
+    return launch_lange<T>(h, norm, m, n, dA, lda, (double *)h->scratch, d_out);
+}
+
+// LAPACK's gecon: lacn2's iteration (dlacn2.f, the states JUMP = 1..5) around single-right-hand-side solves with
+// L U and its transpose.  The vector steps run on the device (kernels_trsvt.hip); the host reads one record after
+// each and decides.  Synchronises the handle's stream.
+template <typename T>
+static int gecon_dev(lsx_handle_t h, int norm, int n, const T *LU, int lda, const int32_t *d_ipiv, double anorm,
+                     double *rcond) {
+    LSX_ARG((norm == LSX_NORM_ONE || norm == LSX_NORM_INF) && n >= 0 && lda >= n && rcond);
+    *rcond = 1.0;
+    h->gecon_solves = 0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(LU && d_ipiv);
+    if (anorm != anorm || anorm < 0) {
+        set_error("bad argument: anorm must be a norm of the unfactored matrix, not NaN or negative");
+        return LSX_ERR_ARG;
+    }
+    *rcond = 0.0;
+    if (anorm == 0) return LSX_OK;
+    const size_t xb = pad256(sizeof(T) * (size_t)n), ib = pad256(sizeof(int32_t) * (size_t)n), sb = pad256((size_t)n);
+    LSX_TRY(grow(&h->ws7, &h->ws7_bytes, xb + ib + sb + 256));
+    T *x = (T *)h->ws7;
+    int32_t *ident = (int32_t *)((char *)h->ws7 + xb);            // no interchange: the solves work on L U alone
+    signed char *isgn = (signed char *)((char *)h->ws7 + xb + ib);
+    double *rec = (double *)((char *)h->ws7 + xb + ib + sb);     // 8 doubles; rec[5] = min |U_ii|
+    double r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto read = [&]() -> int {
+        LSX_HIP(hipMemcpyAsync(r, rec, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        return LSX_OK;
+    };
+    // kase 1: x <- inv(A) x, kase 2: x <- inv(A^T) x; the infinity-norm of A is the 1-norm of A^T
+    auto solve = [&](const int kase) -> int {
+        h->gecon_solves += 1;
+        const bool plain = (kase == 1) == (norm == LSX_NORM_ONE);
+        return plain ? getrs_dev<T>(h, n, 1, LU, lda, ident, x, 1) : getrs_t_dev<T>(h, n, 1, LU, lda, ident, x, 1);
+    };
+    LSX_HIP(hipMemsetAsync(isgn, 0, (size_t)n, h->stream));
+    LSX_TRY(launch_diag_minabs<T>(h, n, LU, lda, rec + 4));      // writes its second slot: rec[5]
+    LSX_TRY(launch_est_fill<T>(h, n, 0, x, ident));
+    LSX_TRY(read());
+    if (!(r[5] > 0)) return LSX_OK;                               // an exactly zero (or NaN) pivot: singular, rcond = 0
+    double est = 0;
+    LSX_TRY(solve(1));
+    LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec));         // JUMP 1
+    LSX_TRY(read());
+    est = r[0];
+    if (n > 1) {
+        LSX_TRY(solve(2));
+        LSX_TRY(launch_est_amax_unit<T>(h, n, x, -1, rec));       // JUMP 2: j, x <- e_j
+        LSX_TRY(read());
+        int j = (int)r[1];
+        for (int iter = 2;; ++iter) {
+            LSX_TRY(solve(1));
+            LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec)); // JUMP 3
+            LSX_TRY(read());
+            const double estold = est;
+            est = r[0];
+            if (r[4] != 0.0 || est <= estold) break;              // repeated sign vector, or no increase
+            LSX_TRY(solve(2));
+            LSX_TRY(launch_est_amax_unit<T>(h, n, x, j, rec));    // JUMP 4
+            LSX_TRY(read());
+            j = (int)r[1];
+            if (!(r[3] != r[2] && iter < 5)) break;
+        }
+        LSX_TRY(launch_est_fill<T>(h, n, 1, x, (int32_t *)nullptr));   // the alternating vector
+        LSX_TRY(solve(1));
+        LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec));     // JUMP 5
+        LSX_TRY(read());
+        const double temp = 2.0 * (r[0] / (3.0 * n));
+        if (temp > est) est = temp;
+    }
+    LSX_TRY(check_dev_status(h));                                 // a timed-out solve is a failure, not an estimate
+    if (est > 0 && est - est == 0) *rcond = (1.0 / est) / anorm;  // non-finite estimate: 0
+    return LSX_OK;
+}
+
+template <typename T>
+static int gecon_host(lsx_handle_t h, int norm, int n, const T *LU, int lda, const int32_t *ipiv, double anorm,
+                      double *rcond) {
+    LSX_ARG(h && (norm == LSX_NORM_ONE || norm == LSX_NORM_INF) && n >= 0 && lda >= n && rcond);
+    if (n == 0) { *rcond = 1.0; return LSX_OK; }
+    LSX_ARG(LU && ipiv);
+    const int ld = ld_for(n);
+    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(int32_t) * n) + 512));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    int32_t *dp = c.take<int32_t>(n);
+    LSX_TRY(h2d<T>(h, n, n, LU, lda, dA, ld));
+    LSX_HIP(hipMemcpyAsync(dp, ipiv, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+    return gecon_dev<T>(h, norm, n, dA, ld, dp, anorm, rcond);
+}
+
+template <typename T>
+static int rcond_host(lsx_handle_t h, int norm, int n, const T *A, int lda, double *rcond, int *info) {
+    LSX_ARG(h && (norm == LSX_NORM_ONE || norm == LSX_NORM_INF) && n >= 0 && lda >= n && rcond);
+    if (info) *info = 0;
+    *rcond = 1.0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A);
+    const int ld = ld_for(n);
+    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(int32_t) * n) + 1024));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    int32_t *dp = c.take<int32_t>(n);
+    int *dinfo = c.take<int>(1);
+    double *dnorm = c.take<double>(1);
+    LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
+    LSX_TRY(lange_dev<T>(h, norm, n, n, dA, ld, dnorm));
+    double anorm = 0;
+    LSX_HIP(hipMemcpyAsync(&anorm, dnorm, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    int hinfo = 0;
+    LSX_TRY(factor_from_host<T>(h, n, A, lda, dA, ld, dp, dinfo, &hinfo));   // synchronises: anorm is there
+    if (info) *info = hinfo;
+    if (hinfo != 0) { *rcond = 0.0; return LSX_OK; }
+    return gecon_dev<T>(h, norm, n, dA, ld, dp, anorm, rcond);
+}
+
 }  // namespace lsx
 
 using namespace lsx;
@@ -991,6 +1160,7 @@ int lsx_destroy(lsx_handle_t h) {
     if (h->ws3) (void)hipFree(h->ws3);
     if (h->ws4) (void)hipFree(h->ws4);
     if (h->ws6) (void)hipFree(h->ws6);
+    if (h->ws7) (void)hipFree(h->ws7);
     if (h->xchg) (void)hipFree(h->xchg);
     if (h->ws5) (void)hipFree(h->ws5);
     if (h->scratch) (void)hipFree(h->scratch);
@@ -1148,6 +1318,7 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value) {
     else if (!strcmp(key, "rref_first_used")) *value = h->rref_first_used;
     else if (!strcmp(key, "panel_fallbacks")) *value = h->panel_fallbacks;
     else if (!strcmp(key, "num_cu")) *value = h->num_cu;
+    else if (!strcmp(key, "gecon_solves")) *value = h->gecon_solves;
     else { set_error("unknown option '%s'", key); return LSX_ERR_ARG; }
     return LSX_OK;
 }
@@ -1516,6 +1687,68 @@ int lsx_rref_f32(lsx_handle_t h, int m, int n, int bar_col, const float *A, int 
                  int ldr, int32_t *pivots, int *rank, double tol, int pivot_rule) {
     LSX_DEVICE_GUARD(h);
     return rref_host<float>(h, m, n, bar_col, A, lda, R, ldr, pivots, rank, tol, pivot_rule);
+}
+
+// ---- transposed solves, norms, condition estimate
+int lsx_getrs_t_f64(lsx_handle_t h, int n, int nrhs, const double *LU, int lda, const int32_t *ipiv, double *B, int ldb) {
+    LSX_DEVICE_GUARD(h);
+    return getrs_t_host<double>(h, n, nrhs, LU, lda, ipiv, B, ldb);
+}
+int lsx_getrs_t_f32(lsx_handle_t h, int n, int nrhs, const float *LU, int lda, const int32_t *ipiv, float *B, int ldb) {
+    LSX_DEVICE_GUARD(h);
+    return getrs_t_host<float>(h, n, nrhs, LU, lda, ipiv, B, ldb);
+}
+int lsx_getrs_t_f64_dev(lsx_handle_t h, int n, int nrhs, const double *dLU, int lda, const int32_t *d_ipiv, double *dB,
+                        int ldb) {
+    LSX_DEVICE_GUARD(h);
+    LSX_ARG(h);
+    return getrs_t_dev<double>(h, n, nrhs, dLU, lda, d_ipiv, dB, ldb);
+}
+int lsx_getrs_t_f32_dev(lsx_handle_t h, int n, int nrhs, const float *dLU, int lda, const int32_t *d_ipiv, float *dB,
+                        int ldb) {
+    LSX_DEVICE_GUARD(h);
+    LSX_ARG(h);
+    return getrs_t_dev<float>(h, n, nrhs, dLU, lda, d_ipiv, dB, ldb);
+}
+int lsx_lange_f64_dev(lsx_handle_t h, int norm, int m, int n, const double *dA, int lda, double *d_out) {
+    LSX_DEVICE_GUARD(h);
+    LSX_ARG(h);
+    return lange_dev<double>(h, norm, m, n, dA, lda, d_out);
+}
+int lsx_lange_f32_dev(lsx_handle_t h, int norm, int m, int n, const float *dA, int lda, double *d_out) {
+    LSX_DEVICE_GUARD(h);
+    LSX_ARG(h);
+    return lange_dev<float>(h, norm, m, n, dA, lda, d_out);
+}
+int lsx_gecon_f64(lsx_handle_t h, int norm, int n, const double *LU, int lda, const int32_t *ipiv, double anorm,
+                  double *rcond) {
+    LSX_DEVICE_GUARD(h);
+    return gecon_host<double>(h, norm, n, LU, lda, ipiv, anorm, rcond);
+}
+int lsx_gecon_f32(lsx_handle_t h, int norm, int n, const float *LU, int lda, const int32_t *ipiv, double anorm,
+                  double *rcond) {
+    LSX_DEVICE_GUARD(h);
+    return gecon_host<float>(h, norm, n, LU, lda, ipiv, anorm, rcond);
+}
+int lsx_gecon_f64_dev(lsx_handle_t h, int norm, int n, const double *dLU, int lda, const int32_t *d_ipiv, double anorm,
+                      double *rcond) {
+    LSX_DEVICE_GUARD(h);
+    LSX_ARG(h);
+    return gecon_dev<double>(h, norm, n, dLU, lda, d_ipiv, anorm, rcond);
+}
+int lsx_gecon_f32_dev(lsx_handle_t h, int norm, int n, const float *dLU, int lda, const int32_t *d_ipiv, double anorm,
+                      double *rcond) {
+    LSX_DEVICE_GUARD(h);
+    LSX_ARG(h);
+    return gecon_dev<float>(h, norm, n, dLU, lda, d_ipiv, anorm, rcond);
+}
+int lsx_rcond_f64(lsx_handle_t h, int norm, int n, const double *A, int lda, double *rcond, int *info) {
+    LSX_DEVICE_GUARD(h);
+    return rcond_host<double>(h, norm, n, A, lda, rcond, info);
+}
+int lsx_rcond_f32(lsx_handle_t h, int norm, int n, const float *A, int lda, double *rcond, int *info) {
+    LSX_DEVICE_GUARD(h);
+    return rcond_host<float>(h, norm, n, A, lda, rcond, info);
 }
 
 // ---- device-pointer entry points

@@ -142,6 +142,9 @@ struct lsx_handle_s {
     int rref_first_used = 0; // read-only option: 1 if the last LSX_PIVOT_FIRST reduction took the blocked form
     void *ws4 = nullptr;     // residual / correction of the mixed-precision solve
     size_t ws4_bytes = 0;
+    void *ws7 = nullptr;     // condition estimate: the iteration vector, its sign vector, the record, an identity interchange list
+    size_t ws7_bytes = 0;
+    int gecon_solves = 0;    // read-only option: single-right-hand-side solves of the last condition estimate
     // small fixed device scratch: pivot search partials, flags, info words
     void *moves = nullptr;      // int2[256]: gather list emitted by the cooperative panel kernel (current buffer)
     void *moves_buf[2] = {nullptr, nullptr};  // the look-ahead driver alternates between two lists
@@ -295,6 +298,22 @@ int lu_solve_few_rhs2(lsx_handle_t h, int n, int nrhs, int nr, const T *LU, int 
 template <typename T>
 int lu_solve_few_rhs(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, T *B, int ldb, T *X, T *inv64L,
                      T *inv64U, T *inv128L, T *inv128U);
+// block inverses of both triangles, 128 x 128, natural orientation (kernels_trsv.hip), and the transposed solve,
+// the norms and the estimator's vector steps built on them (kernels_trsvt.hip)
+template <typename T>
+int launch_inv128_natural(lsx_handle_t h, int n, const T *LU, int lda, T *inv64L, T *inv64U, T *inv128L, T *inv128U);
+template <typename T>
+int lu_solve_transposed(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, const int32_t *d_ipiv, const int32_t *perm,
+                        T *B, int ldb, T *inv64L, T *inv64U, T *inv128L, T *inv128U, T *W);
+size_t lange_work_bytes(int norm, int m, int n);
+template <typename T>
+int launch_lange(lsx_handle_t h, int norm, int m, int n, const T *A, int lda, double *d_work, double *d_out);
+template <typename T>
+int launch_est_fill(lsx_handle_t h, int n, int mode, T *x, int32_t *ident);
+template <typename T>
+int launch_est_asum_sign(lsx_handle_t h, int n, T *x, signed char *isgn, double *rec);
+template <typename T>
+int launch_est_amax_unit(lsx_handle_t h, int n, T *x, int jlast, double *rec);
 int diag_mfma_peak(lsx_handle_t h, int is_f32, int iters, int blocks_per_cu, double *tflops, double *clock_mhz);
 int diag_cu_mask_probe(lsx_handle_t h, const uint32_t *mask_words, int nwords, int nblocks, unsigned *out_host);
 int getrf_mg_f64(lsx_handle_t *hs, int P, int n, double *const *dA, const int *lda, int32_t *const *d_ipiv,

@@ -60,10 +60,12 @@ __device__ void v_gemm64(const T *A, const T *B, T *D, T alpha, int wave, int la
         for (int r = 0; r < 4; ++r) D[(i0 + MfmaV<T>::crow(lane, r)) * VLD + 16 * t + lc] = alpha * acc[t][r];
 }
 
-// inv128T[blk][c][r] = inv(T_blk)[r][c] for every 128-block of the n x n triangle.
+// inv128T[blk][c][r] = inv(T_blk)[r][c] for every 128-block of the n x n triangle; natural != 0 stores
+// inv(T_blk)[c][r] there instead (the transposed solve of kernels_trsvt.hip reads the other orientation coalesced).
 template <typename T>
 __global__ __launch_bounds__(256) void merge128_kernel(int lower, int n, const T *__restrict__ Tm, int ldt,
-                                                       const T *__restrict__ inv64, T *__restrict__ inv128T) {
+                                                       const T *__restrict__ inv64, T *__restrict__ inv128T,
+                                                       int natural) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     T *X11 = (T *)smem, *X22 = X11 + VH * VLD, *OFF = X22 + VH * VLD, *W = OFF + VH * VLD;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void merge128_kernel(int lower, int n, const T
     __syncthreads();
     T *out = inv128T + (size_t)blk * VB * VB;
     for (int e = tid; e < VB * VB; e += 256) {
-        const int c = e / VB, r = e % VB;  // out[c][r] = inv[r][c]
+        const int c = natural ? e % VB : e / VB, r = natural ? e / VB : e % VB;  // out[c][r] = inv[r][c]; natural: out[r][c]
         T v;
         if (r < VH && c < VH) v = X11[r * VLD + c];
         else if (r >= VH && c >= VH) v = X22[(r - VH) * VLD + c - VH];
@@ -970,8 +972,8 @@ int lu_solve_few_rhs(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, T *B
             case 8: return trsv_coop_run<T, 8>(h, n, LU, lda, B, ldb, X, inv64L, inv64U);
         }
     }
-    hipLaunchKernelGGL(merge128_kernel<T>, dim3(nblk), dim3(256), shm_m, h->stream, 1, n, LU, lda, inv64L, inv128L);
-    hipLaunchKernelGGL(merge128_kernel<T>, dim3(nblk), dim3(256), shm_m, h->stream, 0, n, LU, lda, inv64U, inv128U);
+    hipLaunchKernelGGL(merge128_kernel<T>, dim3(nblk), dim3(256), shm_m, h->stream, 1, n, LU, lda, inv64L, inv128L, 0);
+    hipLaunchKernelGGL(merge128_kernel<T>, dim3(nblk), dim3(256), shm_m, h->stream, 0, n, LU, lda, inv64U, inv128U, 0);
     switch (nrhs) {
         case 1: return trsv_run<T, 1>(h, n, LU, lda, B, ldb, X, inv128L, inv128U);
         case 2: return trsv_run<T, 2>(h, n, LU, lda, B, ldb, X, inv128L, inv128U);
@@ -981,6 +983,23 @@ int lu_solve_few_rhs(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, T *B
     set_error("lu_solve_few_rhs: nrhs must be 1, 2, 4 or 8");
     return LSX_ERR_ARG;
 }
+
+// inv(T_kk) of every 128 x 128 diagonal block of both triangles in the NATURAL orientation, out[blk][r][c] =
+// inv(T_blk)[r][c]: what the transposed solve (kernels_trsvt.hip) streams row by row.  Two launches behind the
+// 64 x 64 block inverses.
+template <typename T>
+int launch_inv128_natural(lsx_handle_t h, int n, const T *LU, int lda, T *inv64L, T *inv64U, T *inv128L, T *inv128U) {
+    const int nblk = (n + VB - 1) / VB;
+    const size_t shm_m = (size_t)4 * VH * VLD * sizeof(T);
+    LSX_HIP(hipFuncSetAttribute((const void *)merge128_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_m));
+    LSX_TRY(launch_trtri_both<T>(h, n, LU, lda, inv64L, inv64U));
+    hipLaunchKernelGGL(merge128_kernel<T>, dim3(nblk), dim3(256), shm_m, h->stream, 1, n, LU, lda, inv64L, inv128L, 1);
+    hipLaunchKernelGGL(merge128_kernel<T>, dim3(nblk), dim3(256), shm_m, h->stream, 0, n, LU, lda, inv64U, inv128U, 1);
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
+}
+template int launch_inv128_natural<double>(lsx_handle_t, int, const double *, int, double *, double *, double *, double *);
+template int launch_inv128_natural<float>(lsx_handle_t, int, const float *, int, float *, float *, float *, float *);
 
 template int lu_solve_few_rhs<double>(lsx_handle_t, int, int, const double *, int, double *, int, double *, double *,
                                       double *, double *, double *);

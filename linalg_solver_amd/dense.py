@@ -48,7 +48,24 @@ def lu_factor(a, handle: Optional[N.Handle] = None, dtype=np.float64) -> Tuple[n
     return LU, ipiv[:n], info.value
 
 
-def lu_solve(LU: np.ndarray, ipiv: np.ndarray, b, handle: Optional[N.Handle] = None) -> np.ndarray:
+def _norm_code(which) -> int:
+    """1 / "1" / "one" -> the 1-norm (max column sum); inf / "inf" / "I" -> the infinity-norm (max row sum)."""
+    if which in (1, "1", "one", "O", "o"):
+        return N.NORM_ONE
+    if which in (np.inf, math.inf, "inf", "I", "i"):
+        return N.NORM_INF
+    raise ValueError(f"norm must be 1 or inf, got {which!r}")
+
+
+def lu_solve(LU: np.ndarray, ipiv: np.ndarray, b, handle: Optional[N.Handle] = None, trans: bool = False) -> np.ndarray:
+    """Solve A X = B from the factors of A; trans=True solves A^T X = B from the same factors (lsx_getrs_t_*)."""
+    LU = np.asarray(LU)
+    if LU.ndim != 2 or LU.shape[0] != LU.shape[1]:
+        raise ValueError("lu_solve needs the square factor matrix")
+    if LU.dtype not in (np.float64, np.float32):
+        raise TypeError("dtype must be float64 or float32")
+    if np.shape(b)[:1] != (LU.shape[0],):
+        raise ValueError("right-hand side has the wrong number of rows")
     h = _h(handle)
     dt = LU.dtype
     LU = np.ascontiguousarray(LU)
@@ -60,28 +77,48 @@ def lu_solve(LU: np.ndarray, ipiv: np.ndarray, b, handle: Optional[N.Handle] = N
     if X.shape[0] != n:
         raise ValueError("right-hand side has the wrong number of rows")
     ipiv = np.ascontiguousarray(ipiv, dtype=np.int32)
-    if dt == np.float64:
-        N.check(h.lib.lsx_getrs_f64(h.ptr, n, X.shape[1], _ptr(LU, C.c_double), n, _ptr(ipiv, C.c_int32),
-                                    _ptr(X, C.c_double), X.shape[1]), "lsx_getrs_f64")
-    else:
-        N.check(h.lib.lsx_getrs_f32(h.ptr, n, X.shape[1], _ptr(LU, C.c_float), n, _ptr(ipiv, C.c_int32),
-                                    _ptr(X, C.c_float), X.shape[1]), "lsx_getrs_f32")
+    ct, sfx = _ct(dt)
+    name = f"lsx_getrs_t_{sfx}" if trans else f"lsx_getrs_{sfx}"
+    N.check(getattr(h.lib, name)(h.ptr, n, X.shape[1], _ptr(LU, ct), n, _ptr(ipiv, C.c_int32), _ptr(X, ct),
+                                 X.shape[1]), name)
     return X[:, 0].copy() if vec else X
 
 
-def solve(a, b, handle: Optional[N.Handle] = None, dtype=np.float64):
-    """Solve A X = B.  Returns (X, info, pivot_ratio); X is None when info != 0."""
-    h = _h(handle)
+def _solve_trans(h, A, X, dtype):
+    """A^T X = B: factor A once, then the transposed solve from its factors; pivot_ratio as lsx_gesv_* computes it."""
+    n = A.shape[0]
+    if n == 0:
+        return 0, 1.0
+    LU, ipiv, info = lu_factor(A, h, dtype)
+    amax = float(np.max(np.abs(A)))
+    ratio = float(np.min(np.abs(np.diagonal(LU)))) / amax if amax > 0 else 0.0
+    if info == 0 and X.shape[1] > 0:
+        X[:, :] = lu_solve(LU, ipiv, X, h, trans=True)
+    return info, ratio
+
+
+def solve(a, b, handle: Optional[N.Handle] = None, dtype=np.float64, trans: bool = False):
+    """Solve A X = B (trans=True: A^T X = B, from the factors of A -- no transposed copy, no second
+    factorisation).  Returns (X, info, pivot_ratio); X is None when info != 0."""
     A = np.ascontiguousarray(a, dtype=dtype)
     n = A.shape[0]
     if A.ndim != 2 or A.shape[1] != n:
         raise ValueError("solve needs a square matrix")
+    if np.shape(b)[:1] != (n,):
+        raise ValueError("right-hand side has the wrong number of rows")
+    h = _h(handle)
     X = np.array(b, dtype=dtype, order="C", copy=True)
     vec = X.ndim == 1
     if vec:
         X = X.reshape(n, 1).copy()
     if X.shape[0] != n:
         raise ValueError("right-hand side has the wrong number of rows")
+    if trans:
+        _ct(dtype)
+        tinfo, tratio = _solve_trans(h, A, X, dtype)
+        if tinfo != 0:
+            return None, tinfo, tratio
+        return (X[:, 0].copy() if vec else X), 0, tratio
     info, ratio = C.c_int(0), C.c_double(1.0)
     if dtype == np.float64:
         N.check(h.lib.lsx_gesv_f64(h.ptr, n, X.shape[1], _ptr(A, C.c_double), n, _ptr(X, C.c_double), X.shape[1],
@@ -100,6 +137,68 @@ def _ct(dtype):
     if dtype == np.float32:
         return C.c_float, "f32"
     raise TypeError("dtype must be float64 or float32")
+
+
+def norm(a, which=1, handle: Optional[N.Handle] = None, dtype=np.float64) -> float:
+    """Max absolute column sum (which=1) or row sum (which=inf) of a 2-D array, computed on the GPU
+    (lsx_lange_*_dev; sums in fp64, fixed order)."""
+    code = _norm_code(which)
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    if A.ndim != 2:
+        raise ValueError("norm needs a 2-D array")
+    if A.size == 0:
+        return 0.0
+    import torch
+
+    h = _h(handle)
+    dev = torch.device("cuda", h.device)
+    dA = torch.from_numpy(A).to(dev)
+    out = torch.zeros(1, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    N.check(getattr(h.lib, f"lsx_lange_{sfx}_dev")(h.ptr, code, A.shape[0], A.shape[1], dA.data_ptr(), A.shape[1],
+                                                    out.data_ptr()), f"lsx_lange_{sfx}_dev")
+    h.synchronize()
+    return float(out.item())
+
+
+def rcond(a, norm=1, dtype=np.float64, handle: Optional[N.Handle] = None) -> Tuple[float, int]:
+    """Reciprocal condition number of a square matrix in the 1- or infinity-norm: norm, factorisation and LAPACK's
+    gecon estimate in one call (lsx_rcond_*).  Returns (rcond, info); info > 0 is an exactly zero pivot (rcond 0)."""
+    code = _norm_code(norm)
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("rcond needs a square matrix")
+    h = _h(handle)
+    n = A.shape[0]
+    rc, info = C.c_double(0.0), C.c_int(0)
+    N.check(getattr(h.lib, f"lsx_rcond_{sfx}")(h.ptr, code, n, _ptr(A, ct) if n else None, max(n, 1), C.byref(rc),
+                                                C.byref(info)), f"lsx_rcond_{sfx}")
+    return rc.value, info.value
+
+
+def lu_rcond(LU: np.ndarray, ipiv: np.ndarray, anorm: float, norm=1, handle: Optional[N.Handle] = None) -> float:
+    """gecon from existing factors: anorm is the 1- (or infinity-) norm of the UNFACTORED matrix (lsx_gecon_*)."""
+    code = _norm_code(norm)
+    LU = np.asarray(LU)
+    if LU.ndim != 2 or LU.shape[0] != LU.shape[1]:
+        raise ValueError("lu_rcond needs the square factor matrix")
+    ct, sfx = _ct(LU.dtype)
+    n = LU.shape[0]
+    if len(ipiv) < n:
+        raise ValueError("ipiv is shorter than the matrix order")
+    anorm = float(anorm)
+    if math.isnan(anorm) or anorm < 0:
+        raise ValueError("anorm must be a norm of the unfactored matrix (not NaN, not negative)")
+    h = _h(handle)
+    LU = np.ascontiguousarray(LU)
+    ipiv = np.ascontiguousarray(ipiv, dtype=np.int32)
+    rc = C.c_double(0.0)
+    N.check(getattr(h.lib, f"lsx_gecon_{sfx}")(h.ptr, code, n, _ptr(LU, ct) if n else None, max(n, 1),
+                                                _ptr(ipiv, C.c_int32) if n else None, anorm, C.byref(rc)),
+            f"lsx_gecon_{sfx}")
+    return rc.value
 
 
 def solve_refined(a, b, sweeps: int = 3, handle: Optional[N.Handle] = None):

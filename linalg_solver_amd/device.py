@@ -61,14 +61,56 @@ class DeviceSolver:
         N.check(fn(self.h.ptr, n, A.data_ptr(), A.stride(0), ipiv.data_ptr(), info.data_ptr()), "getrf_dev")
         return ipiv, info
 
-    def getrs_(self, LU: torch.Tensor, ipiv: torch.Tensor, B: torch.Tensor):
-        """B <- A^-1 B in place (B: n x nrhs)."""
+    def getrs_(self, LU: torch.Tensor, ipiv: torch.Tensor, B: torch.Tensor, trans: bool = False):
+        """B <- A^-1 B in place (B: n x nrhs); trans=True: B <- A^-T B from the same factors (lsx_getrs_t_*_dev)."""
         _rowmajor(LU, "getrs_")
         _rowmajor(B, "getrs_")
-        fn = getattr(self.lib, f"lsx_getrs_{self._suffix(LU)}_dev")
-        N.check(fn(self.h.ptr, LU.shape[0], B.shape[1], LU.data_ptr(), LU.stride(0), ipiv.data_ptr(),
-                   B.data_ptr(), B.stride(0)), "getrs_dev")
+        if LU.shape[0] != LU.shape[1] or B.shape[0] != LU.shape[0]:
+            raise ValueError("getrs_: need square factors and a right-hand side with as many rows")
+        if B.dtype != LU.dtype:
+            raise TypeError("getrs_: factors and right-hand side must have the same dtype")
+        name = f"lsx_getrs_t_{self._suffix(LU)}_dev" if trans else f"lsx_getrs_{self._suffix(LU)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, LU.shape[0], B.shape[1], LU.data_ptr(), LU.stride(0), ipiv.data_ptr(),
+                                        B.data_ptr(), B.stride(0)), name)
         return B
+
+    @staticmethod
+    def _norm_code(which) -> int:
+        if which in (1, "1", "one", "O", "o"):
+            return N.NORM_ONE
+        if which in (float("inf"), "inf", "I", "i"):
+            return N.NORM_INF
+        raise ValueError(f"norm must be 1 or inf, got {which!r}")
+
+    def norm(self, A: torch.Tensor, which=1) -> torch.Tensor:
+        """Max absolute column sum (which=1) or row sum (which=inf) of a tensor in HBM: a device double[1], no host
+        sync (lsx_lange_*_dev)."""
+        code = self._norm_code(which)
+        _rowmajor(A, "norm")
+        out = torch.zeros(1, dtype=torch.float64, device=A.device)
+        name = f"lsx_lange_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, code, A.shape[0], A.shape[1], A.data_ptr(), A.stride(0),
+                                        out.data_ptr()), name)
+        return out
+
+    def rcond(self, LU: torch.Tensor, ipiv: torch.Tensor, anorm, norm=1) -> float:
+        """Reciprocal condition number from factors in HBM (lsx_gecon_*_dev); anorm: that norm of the UNFACTORED
+        matrix, a float or the tensor `norm` returned.  Synchronises the stream: the result is a host float."""
+        import ctypes as C
+        import math
+
+        code = self._norm_code(norm)
+        _rowmajor(LU, "rcond")
+        if LU.shape[0] != LU.shape[1]:
+            raise ValueError("rcond needs square factors")
+        anorm = float(anorm.item()) if hasattr(anorm, "item") else float(anorm)
+        if math.isnan(anorm) or anorm < 0:
+            raise ValueError("anorm must be a norm of the unfactored matrix (not NaN, not negative)")
+        rc = C.c_double(0.0)
+        name = f"lsx_gecon_{self._suffix(LU)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, code, LU.shape[0], LU.data_ptr(), LU.stride(0), ipiv.data_ptr(),
+                                        anorm, C.byref(rc)), name)
+        return rc.value
 
     def getri(self, LU: torch.Tensor, ipiv: torch.Tensor, out: Optional[torch.Tensor] = None):
         _rowmajor(LU, "getri")

@@ -225,7 +225,7 @@ class Matrix:
         ipiv, info = dev.getrf_(LU)
         return LU, ipiv, info
 
-    def _solve_device(self, rhs):
+    def _solve_device(self, rhs, trans: bool = False):
         import torch
 
         from .device import DeviceSolver
@@ -246,7 +246,7 @@ class Matrix:
             if B.shape[0] != n:
                 raise ValueError("Matrix dimensions must match")
             X = B.reshape(n, -1).contiguous().clone()
-            dev.getrs_(LU, ipiv, X)
+            dev.getrs_(LU, ipiv, X, trans=trans)
             if vec:
                 X = X[:, 0]
         # singular to working precision: the same test as the host path (smallest |pivot| against the largest entry)
@@ -274,12 +274,13 @@ class Matrix:
             raise IndexError("list index out of range")
         return R, pivots
 
-    def solve_array(self, rhs) -> "np.ndarray | Matrix.NoSolution":
+    def solve_array(self, rhs, trans: bool = False) -> "np.ndarray | Matrix.NoSolution":
         """Unique solution(s) of self * X = rhs for a square matrix (rhs: vector or matrix) as an ndarray;
         NoSolution() when the matrix is singular to working precision (use find_preimage_of for the
-        general affine answer)."""
+        general affine answer).  trans=True solves self^T * X = rhs (x * self = rhs^T for rows) from the factors of
+        self: no transposed copy, no second factorisation."""
         if getattr(self, "_dev", None) is not None and self._items is None:
-            return self._solve_device(rhs)   # operands in HBM: the result is a device tensor too
+            return self._solve_device(rhs, trans)   # operands in HBM: the result is a device tensor too
         A = self._array()
         if A.shape[0] != A.shape[1]:
             raise ValueError("solve_array needs a square matrix")
@@ -287,10 +288,40 @@ class Matrix:
         vec = B.ndim == 1
         if B.shape[0] != A.shape[0]:
             raise ValueError("Matrix dimensions must match")
-        X, info, ratio = dense.solve(A, B.reshape(A.shape[0], -1))
+        X, info, ratio = dense.solve(A, B.reshape(A.shape[0], -1), trans=trans)
         if info != 0 or not (ratio > dense.EPS64 * A.shape[0]):
             return Matrix.NoSolution()
         return X[:, 0] if vec else X
+
+    def rcond(self, norm=1) -> float:
+        """Reciprocal condition number 1 / (||A|| ||A^-1||) in the 1-norm (norm=1) or the infinity-norm
+        (norm=inf): LAPACK's gecon estimate from the LU factors (lsx_rcond_f64 / lsx_gecon_f64_dev).  0.0 for a
+        matrix with an exactly zero pivot.  Unlike the pivot ratio behind NoSolution it sees ill-conditioning that
+        leaves every pivot large."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            if A.shape[0] != A.shape[1]:
+                raise ValueError("rcond needs a square matrix")
+            dev = DeviceSolver(self._dev.device.index)
+            anorm = dev.norm(A, norm)
+            LU = A.clone()
+            ipiv, info = dev.getrf_(LU)
+            code = int(info.item())
+            if code < 0:
+                dev.h.check_status()
+                raise RuntimeError(f"device factorisation failed (info = {code})")
+            return 0.0 if code != 0 else dev.rcond(LU, ipiv, anorm, norm)
+        A = self._array()
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("rcond needs a square matrix")
+        return dense.rcond(A, norm)[0]
+
+    def cond(self, norm=1) -> float:
+        """Estimated condition number 1 / rcond(norm); inf when rcond is 0."""
+        r = self.rcond(norm)
+        return float("inf") if r == 0.0 else 1.0 / r
 
     def inverse_array(self) -> "np.ndarray | Matrix.NoSolution":
         if getattr(self, "_dev", None) is not None and self._items is None:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | gecon [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -356,6 +356,56 @@ def main():
             dev.panel_(P, 0, ipiv, info)
         torch.cuda.synchronize()
         print(f"pmcpanel workload done: panel {m} x {args.nb}, bytes one way = {m * args.nb * 8}; calibration copy {m * m * 8} one way")
+    if "trsvt" in args.what:
+        # few-right-hand-side solves from the factors: transposed (one launch per 128-row step) against the plain
+        # solve in the same form (trsv=0: it streams the same n^2 elements once per sweep) and in its default form
+        HBM = 8.0e12   # bytes / s (MI355X data sheet)
+        for dt in (torch.float64, torch.float32):
+            for n in (1024, 4096, 8192):
+                A = torch.empty(n, n, dtype=dt, device="cuda")
+                dev.fill_(A, gen.U11, 1)
+                ipiv, info = dev.getrf_(A)
+                for nrhs in (1, 8):
+                    B0 = torch.empty(n, nrhs, dtype=dt, device="cuda")
+                    dev.fill_(B0, gen.U11, 2)
+                    B = B0.clone()
+                    res = {}
+                    for rnd in range(2):          # two alternating rounds: the spread of the same command
+                        for name, trans, mode in (("transposed", True, 2), ("plain trsv=0", False, 0), ("plain trsv=2", False, 2)):
+                            dev.h.set_option("trsv", mode)
+                            res.setdefault(name, []).append(timeit(lambda: dev.getrs_(A, ipiv, B, trans=trans), reps=21, warm=3)[1])
+                    dev.h.set_option("trsv", 2)
+                    by = A.element_size() * float(n) * n
+                    print(f"solve {str(dt)[6:]} n={n} nrhs={nrhs}: " + "  ".join(
+                        f"{k} {min(v) * 1e3:.1f} us (rounds {v[0] * 1e3:.1f} / {v[1] * 1e3:.1f}; {by / min(v) / 1e-3 / HBM * 100:.1f} % of HBM)"
+                        for k, v in res.items()), flush=True)
+    if "gecon" in args.what:
+        # the condition estimate beside the factorisation it follows (fp64, 1-norm; medians)
+        for n in (1024, 4096, 8192):
+            A0 = torch.empty(n, n, dtype=torch.float64, device="cuda")
+            dev.fill_(A0, gen.U11, 1)
+            A = A0.clone()
+            ipiv = torch.zeros(n, dtype=torch.int32, device="cuda")
+            info = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+            def factor():
+                A.copy_(A0)
+                dev.getrf_(A, ipiv, info)
+            t_lu = timeit(factor, reps=7, warm=2)[1] - timeit(lambda: A.copy_(A0), reps=7, warm=2)[1]
+            factor()                      # the copy timing left the unfactored matrix in A
+            t_nrm = timeit(lambda: dev.norm(A0, 1), reps=11, warm=2)[1]
+            anorm = float(dev.norm(A0, 1).item())
+            for _ in range(2):
+                rc = dev.rcond(A, ipiv, anorm)
+            ts = []
+            for _ in range(9):            # synchronous call: host clock around it
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                rc = dev.rcond(A, ipiv, anorm)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            t_con = sorted(ts)[len(ts) // 2]
+            print(f"gecon f64 n={n}: getrf {t_lu:.3f} ms  lange {t_nrm:.3f} ms  gecon {t_con:.3f} ms "
+                  f"({dev.h.get_option('gecon_solves')} solves, {t_con / t_lu * 100:.1f} % of getrf)  rcond {rc:.3e}", flush=True)
     if "lu" in args.what:
         n = args.n
         A0 = torch.empty(n, n, dtype=torch.float32 if args.f32 else torch.float64, device="cuda")
