@@ -274,7 +274,13 @@ int lsx_laswp_f64_dev(lsx_handle_t h, int ncols, double *dA, int lda, int row0, 
  * row pairs relative to row0, -1 = unused).  lsx_panel_moves_dev copies the list of the LAST
  * lsx_panel_f64_dev call into d_moves (512 int32; *valid = 0 if that panel used the per-column
  * kernels and produced no list); lsx_laswp_moves_f64_dev applies such a list to ncols columns.
- * The multi-GPU driver ships the list inside the panel broadcast. */
+ * The multi-GPU driver ships the list inside the panel broadcast.
+ * Requirements of lsx_laswp_moves_f64_dev: d_moves holds 512 int32 and is 8-byte aligned (it is read as 256 pairs);
+ * the destinations of the used pairs are distinct; dA is the address of row 0 of the columns to move, row pair
+ * (dst, src) means row row0 + dst <- row row0 + src, all sources read before any destination is written.  dA and lda
+ * may have any alignment and ncols any value >= 0: 16-byte moves are used when dA is 16-byte aligned and lda and ncols
+ * are even, element-wise moves otherwise, with the same result.  (The fused head of the look-ahead chain behind
+ * lsx_diag_chain_head_* has the 16-byte form only and answers LSX_ERR_ARG to anything else.) */
 int lsx_panel_moves_dev(lsx_handle_t h, int32_t *d_moves, int *valid);
 int lsx_laswp_moves_f64_dev(lsx_handle_t h, int ncols, double *dA, int lda, int row0, const int32_t *d_moves);
 /* dB (jb x ncols) <- inv(L11) * dB with L11 the unit-lower jb x jb block at dL. */

@@ -226,6 +226,10 @@ def test_getrf_integer_matrices(la, n):
     oLU, oipiv, oinfo = capi.getrf(A)
     assert info == oinfo
     if info == 0:
+        # no column without a non-zero candidate occurred (the one place where the cooperative panels may record
+        # another row than the twin: test_xcd_panel_matches_the_two_reference_panels_bit_for_bit), so every tie
+        # must have gone to the lowest row, as in the twin
+        assert np.array_equal(ipiv, oipiv), f"first differing column {int(np.nonzero(ipiv != oipiv)[0][0])}"
         assert _plu_residual(A, LU, ipiv) < 50 * n * 2.3e-16
         assert np.max(np.abs(np.tril(LU, -1))) <= 1.0
         x = dense.lu_solve(LU, ipiv, b)
