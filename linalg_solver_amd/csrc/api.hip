@@ -1460,7 +1460,10 @@ static int rref_first_fast(lsx_handle_t h, int m, int n, int bar, double *R, int
     LSX_HIP(hipMemcpyAsync(&r, d_rank, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     LSX_HIP(hipMemcpyAsync(&hmax, amax, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     LSX_HIP(hipStreamSynchronize(h->stream));
-    if (r <= 0) { h->rref_first_used = 1; return LSX_OK; }      // nothing to pivot on: R is its own reduced form
+    if (r <= 0) {   // nothing to pivot on: every entry left of the bar is at or below the tolerance and counts as zero
+        h->rref_first_used = 1;
+        return launch_rref_finish<T>(h, m, bar, R, ldr, d_pivots, 0);
+    }
     if (r == m) {   // every row is a pivot row: the result does not depend on the rule
         h->rref_first_used = 1;
         return launch_copy2d<T>(h, m, n, W, ldw, R, ldr);

@@ -38,7 +38,7 @@ struct RrefState {
     int skip;     // 1: current column has no pivot
     int pad[3];
     double tol;        // fixed tolerance (user) or < 0: eps_scale * amax, re-evaluated per column
-    double amax;       // running max |entry| of the working matrix (grows with elimination)
+    double amax;       // running max |entry| of the working matrix left of the bar (grows with elimination)
     double eps_scale;  // eps * max(m, n)
 };
 
@@ -125,9 +125,11 @@ __global__ __launch_bounds__(256) void rref_pivot_kernel(int m, int n, int pj, i
 
 // One wave per row.  Row pi receives the normalised pivot row; the row that
 // held the pivot (p) receives the displaced row, eliminated; every other row
-// with a non-zero entry in column pj is eliminated in place.
+// with a non-zero entry in column pj is eliminated in place.  The running maximum behind the default tolerance is
+// taken over the columns left of `bar` only, as the blocked forms take it: the carried-along columns are updated but
+// do not count, or a large right-hand side would raise the tolerance above the pivots of the left block.
 template <typename T>
-__global__ __launch_bounds__(256) void rref_sweep_kernel(int m, int n, int pj, T *__restrict__ R,
+__global__ __launch_bounds__(256) void rref_sweep_kernel(int m, int n, int bar, int pj, T *__restrict__ R,
                                                          int ldr, RrefState *st,
                                                          const T *__restrict__ prow,
                                                          const T *__restrict__ orow) {
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(256) void rref_sweep_kernel(int m, int n, int pj, T
     for (int c = pj + lane; c < n; c += 64) {
         const T v = src[c] - f * prow[c];
         row[c] = v;
-        vmax = fmax(vmax, fabs((double)v));
+        if (c < bar) vmax = fmax(vmax, fabs((double)v));
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) vmax = fmax(vmax, __shfl_down(vmax, off, 64));
@@ -193,8 +195,8 @@ int launch_rref(lsx_handle_t h, int m, int n, int bar, T *R, int ldr, int32_t *d
     for (int pj = 0; pj < bar; ++pj) {
         hipLaunchKernelGGL(rref_pivot_kernel<T>, dim3(1), dim3(256), 0, h->stream, m, n, pj, pivot_rule,
                            R, ldr, st, d_pivots, prow, orow);
-        hipLaunchKernelGGL(rref_sweep_kernel<T>, dim3((m + 3) / 4), dim3(256), 0, h->stream, m, n, pj,
-                           R, ldr, st, prow, orow);
+        hipLaunchKernelGGL(rref_sweep_kernel<T>, dim3((m + 3) / 4), dim3(256), 0, h->stream, m, n, bar,
+                           pj, R, ldr, st, prow, orow);
     }
     hipLaunchKernelGGL(rref_finish_kernel, dim3(1), dim3(1), 0, h->stream, st, d_rank);
     LSX_HIP(hipGetLastError());
