@@ -117,11 +117,12 @@ struct Carver {
 
 static size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// row interchanges of the panel that was just factored, applied to `ncols` columns at Acols
+// row interchanges of the panel that was just factored, applied to `ncols` columns at Acols: from its gather list,
+// or (moves null: the panel emitted none) from its pivots
 template <typename T>
-static int apply_panel_swaps(lsx_handle_t h, int ncols, T *Acols, int lda, int row0, int jb,
+static int apply_panel_swaps(lsx_handle_t h, const int2 *moves, int ncols, T *Acols, int lda, int row0, int jb,
                              const int32_t *d_ipiv) {
-    if (h->moves_valid) return launch_laswp_moves<T>(h, ncols, Acols, lda, row0);
+    if (moves) return launch_laswp_moves<T>(h, moves, ncols, Acols, lda, row0);
     return launch_laswp<T>(h, ncols, Acols, lda, row0, jb, d_ipiv);
 }
 
@@ -146,7 +147,6 @@ struct JoinSide {
         if (!armed) return;
         if (hipEventRecord(h->ev_done, side) == hipSuccess) (void)hipStreamWaitEvent(main_s, h->ev_done, 0);
         if (caller != main_s && hipEventRecord(h->ev_start, main_s) == hipSuccess) (void)hipStreamWaitEvent(caller, h->ev_start, 0);
-        h->moves_valid = false;
     }
 };
 
@@ -154,32 +154,24 @@ struct JoinSide {
 // front of the panel that starts at column k_stop (trailing matrix fully updated, that panel not yet factored):
 // the XCD-scope driver takes over from there.
 template <typename T>
-static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int *d_info, T *Tinv,
+static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int *d_info, T *Tinv, PanelArgs pa,
                            int k0, int k_stop = 0) {
     const int nb = h->nb;
-    struct OnSide {  // launches inside this scope go to the given stream
-        lsx_handle_t h; hipStream_t keep;
-        OnSide(lsx_handle_t h_, hipStream_t s) : h(h_), keep(h_->stream) { h->stream = s; }
-        ~OnSide() { h->stream = keep; }
-    };
-    hipStream_t caller = h->stream;
-    hipStream_t main_s = h->stream, side = h->side_stream;
-    struct Restore {  // the handle's stream is the update stream while this driver runs
-        lsx_handle_t h; hipStream_t keep; int nt, rt, mode;
-        ~Restore() { h->stream = keep; h->panel_nt = nt; h->panel_rt = rt; h->panel_mode = mode; h->panel_area_stride = 0; h->panel_area = 0; }
-    } restore{h, caller, h->panel_nt, h->panel_rt, h->panel_mode};
-    JoinSide join{h, side, main_s, caller};
+    hipStream_t main_s = h->stream, side = h->side_stream;   // the handle's stream is the update stream
+    JoinSide join{h, side, main_s, main_s};
+    GemmPlan mfma;   // every update of an LU: see GemmPlan
+    mfma.mfma_only = true;
     // this schedule shares the CUs between the panel and the update: the XCD-scope panel (which fills an XCD) has
     // its own driver, getrf_lookahead_x; here it would stall every launch beside it
-    if (h->panel_mode == 4) h->panel_mode = 3;
+    if (pa.mode == 4) pa.mode = 3;
     // Panels taller than one XCD holds (the phase in front of getrf_lookahead_x): 256-row slices, i.e. half as many
     // workgroups of the device-scope panel.  Its time per column does not depend on the slicing (2.5-2.6 us, kbench
     // panel3tall), but every CU it holds is one the update -- the bottleneck of this phase -- does not have:
     // 16384^2 fp64 77.8 -> 74.6 ms, 12288^2 38.5 -> 37.9 ms, same bits (tools/lu_tall.py).
-    if (sizeof(T) == 8 && k_stop > 0 && h->panel_nt == 0 && n - k0 > 8192) { h->panel_nt = 512; h->panel_rt = 8; }
+    if (sizeof(T) == 8 && k_stop > 0 && pa.nt == 0 && n - k0 > 8192) { pa.nt = 512; pa.rt = 8; }
     // Exchange areas of the pipelined panel: two, used alternately, and cleared HERE on the main stream as
     // soon as their panel has finished -- a clear in front of every panel launch sits on the chain.
-    size_t area = panel_pipe_area_bytes(h, n - k0);
+    size_t area = panel_pipe_area_bytes(h, pa.mode, pa.nt, pa.rt, n - k0);
     if (2 * area > h->scratch_bytes) area = 0;
     if (area) LSX_HIP(hipMemsetAsync(h->scratch, 0, 2 * area, main_s));
     // Counted first tile column of the big update (fp64, this driver as the phase in front of getrf_lookahead_x): the
@@ -192,18 +184,17 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
         c0words = (int *)((char *)h->scratch + 2 * area);
         LSX_HIP(hipMemsetAsync(c0words, 0, (size_t)nst * sizeof(int), main_s));
     }
-    struct ClearCol0 { lsx_handle_t h; ~ClearCol0() { h->gemm_col0_static = nullptr; } } clear_col0{h};
     bool prev_counted = false;
     int prev_tiles = 0;
-    h->panel_area_stride = area;
-    h->panel_area = 0;
+    pa.area_bytes = area;
     // the side stream starts after everything already queued on the main stream (info memset, fills)
     LSX_HIP(hipEventRecord(h->ev_start, main_s));
     LSX_HIP(hipStreamWaitEvent(side, h->ev_start, 0));
     // The gather list of panel p lives in moves_buf[p & 1]: panel p+1 (side stream) writes the other
     // buffer while the update stream still applies panel p's interchanges to the left-hand columns,
     // which nothing later depends on and which therefore run AFTER the big update, in its slack.
-    struct KeepMoves { lsx_handle_t h; ~KeepMoves() { h->moves = h->moves_buf[0]; } } keep_moves{h};
+    // (A panel that took the per-column form emits no list: null here, and its interchanges come from the pivots.)
+    auto list = [&](int p, bool has) { return has ? (const int2 *)h->moves_buf[p & 1] : nullptr; };
     // The whole chain panel k -> panel k+1 stays on the side stream (no cross-stream hop on the critical
     // path): inverse of panel k's diagonal blocks, then interchanges / U12 / update of the next panel's own
     // column block, then panel k+1.  The main stream follows one event behind with the other columns.  The
@@ -214,23 +205,24 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
     int step = 0;
     T *Tinv2[2] = {Tinv, Tinv + (size_t)((nb + 63) / 64) * 4096};
     {
-        OnSide g(h, side);
+        OnStream g(h, side);
         const int jb0 = (n - k0) < nb ? (n - k0) : nb;
-        h->moves = h->moves_buf[step & 1];
-        LSX_TRY(launch_panel<T>(h, n - k0, jb0, A + (size_t)k0 * lda + k0, lda, k0, d_ipiv + k0, d_info));
+        pa.list = h->moves_buf[0];
+        pa.area_off = 0;
+        LSX_TRY(launch_panel<T>(h, n - k0, jb0, A + (size_t)k0 * lda + k0, lda, k0, d_ipiv + k0, d_info, pa));
     }
+    bool listed = pa.listed;    // panel k came with a gather list
     bool have_update = false;   // ev_next holds the end of the previous step's update
     for (int k = k0; k < n; k += nb, ++step) {
         const int jb = (n - k < nb) ? n - k : nb;
         T *Akk = A + (size_t)k * lda + k;
         T *Ti = Tinv2[step & 1];
-        const bool mv_valid = h->moves_valid;
+        const int2 *mv = list(step, listed);   // panel k's list
         const int rest = n - k - jb;
         if (rest <= 0) {
             LSX_HIP(hipEventRecord(h->ev_panel, side));
             LSX_HIP(hipStreamWaitEvent(main_s, h->ev_panel, 0));  // the last panel is factored
-            h->moves = h->moves_buf[step & 1];
-            LSX_TRY(apply_panel_swaps<T>(h, k, A, lda, k, jb, d_ipiv + k));
+            LSX_TRY(apply_panel_swaps<T>(h, mv, k, A, lda, k, jb, d_ipiv + k));
             break;
         }
         T *A12 = A + (size_t)k * lda + k + jb;
@@ -239,68 +231,62 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
         if (k_stop > 0 && k + jb >= k_stop) {   // last step here: no panel ahead, the whole step on the main stream
             LSX_HIP(hipEventRecord(h->ev_panel, side));
             LSX_HIP(hipStreamWaitEvent(main_s, h->ev_panel, 0));
-            h->moves = h->moves_buf[step & 1];
-            h->moves_valid = mv_valid;
             LSX_TRY(launch_trtri<T>(h, 1, jb, Akk, lda, Ti));
-            LSX_TRY(apply_panel_swaps<T>(h, rest, A + k + jb, lda, k, jb, d_ipiv + k));
+            LSX_TRY(apply_panel_swaps<T>(h, mv, rest, A + k + jb, lda, k, jb, d_ipiv + k));
             LSX_TRY(launch_trsm_block<T>(h, 1, jb, rest, Akk, lda, Ti, A12, lda));
-            LSX_TRY(launch_gemm_sub<T>(h, rest, rest, jb, L21, lda, A12, lda, A22, lda));
-            LSX_TRY(apply_panel_swaps<T>(h, k, A, lda, k, jb, d_ipiv + k));
+            LSX_TRY(launch_gemm_sub<T>(h, rest, rest, jb, L21, lda, A12, lda, A22, lda, mfma));
+            LSX_TRY(apply_panel_swaps<T>(h, mv, k, A, lda, k, jb, d_ipiv + k));
             break;
         }
         const int jb2 = rest < nb ? rest : nb;  // width of the next panel
-        bool next_valid;
         {
-            OnSide g(h, side);
-            h->moves = h->moves_buf[step & 1];
+            OnStream g(h, side);
             // block inverses and the next block's interchanges in one launch (the main stream starts behind the
             // chain anyway: the CUs are shared)
             if (have_update && !prev_counted) LSX_HIP(hipStreamWaitEvent(side, h->ev_next, 0));
-            const int fused = launch_chain_head<T>(h, jb, Akk, lda, Ti, jb2, A + k + jb, lda, k,
+            // (no info word for the waits of this schedule: a time-out is recorded in the status word alone)
+            const int fused = launch_chain_head<T>(h, mv, nullptr, jb, Akk, lda, Ti, jb2, A + k + jb, lda, k,
                                                    prev_counted ? c0words + (step - 1) : nullptr, prev_tiles);
             if (fused < 0) return fused;
-            if (fused == 1 && prev_counted) LSX_TRY(launch_wait_count(h, c0words + (step - 1), prev_tiles));
+            if (fused == 1 && prev_counted) LSX_TRY(launch_wait_count(h, c0words + (step - 1), prev_tiles, nullptr));
             if (fused == 1) {
                 LSX_TRY(launch_trtri<T>(h, 1, jb, Akk, lda, Ti));
-                LSX_TRY(apply_panel_swaps<T>(h, jb2, A + k + jb, lda, k, jb, d_ipiv + k));
+                LSX_TRY(apply_panel_swaps<T>(h, mv, jb2, A + k + jb, lda, k, jb, d_ipiv + k));
             }
             LSX_TRY(launch_trsm_block<T>(h, 1, jb, jb2, Akk, lda, Ti, A12, lda));
-            LSX_TRY(launch_gemm_sub<T>(h, rest, jb2, jb, L21, lda, A12, lda, A22, lda));
+            LSX_TRY(launch_gemm_sub<T>(h, rest, jb2, jb, L21, lda, A12, lda, A22, lda, mfma));
             // Sharing the CUs, the big update would take the slots these small launches need (measured:
             // the chain doubles); the main stream therefore starts behind the chain.
             LSX_HIP(hipEventRecord(h->ev_panel, side));
             // panel k+1 writes the gather list and exchange area that step k-1 used: behind ALL of update k-1 and its
             // left-hand interchanges (with the counted column the chain above no longer waited for them)
             if (have_update && prev_counted) LSX_HIP(hipStreamWaitEvent(side, h->ev_next, 0));
-            h->moves = h->moves_buf[(step + 1) & 1];
-            h->panel_area = (step + 1) & 1;
-            LSX_TRY(launch_panel<T>(h, rest, jb2, A22, lda, k + jb, d_ipiv + k + jb, d_info));
-            next_valid = h->moves_valid;
+            pa.list = h->moves_buf[(step + 1) & 1];
+            pa.area_off = (size_t)((step + 1) & 1) * area;
+            LSX_TRY(launch_panel<T>(h, rest, jb2, A22, lda, k + jb, d_ipiv + k + jb, d_info, pa));
         }
         LSX_HIP(hipStreamWaitEvent(main_s, h->ev_panel, 0));
         bool cur_counted = false;
         int cur_tiles = 0;
         // panel k is done with its exchange area; panel k+2 reuses it, behind ev_next below
         if (area) LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)(step & 1) * area, 0, area, main_s));
-        h->moves = h->moves_buf[step & 1];   // panel k's list
-        h->moves_valid = mv_valid;
         if (rest > jb2) {
-            LSX_TRY(apply_panel_swaps<T>(h, rest - jb2, A + k + jb + jb2, lda, k, jb, d_ipiv + k));
+            LSX_TRY(apply_panel_swaps<T>(h, mv, rest - jb2, A + k + jb + jb2, lda, k, jb, d_ipiv + k));
             LSX_TRY(launch_trsm_block<T>(h, 1, jb, rest - jb2, Akk, lda, Ti, A12 + jb2, lda));
-            h->gemm_col0_static = c0words ? c0words + step : nullptr;
-            const int rg = launch_gemm_sub<T>(h, rest, rest - jb2, jb, L21, lda, A12 + jb2, lda, A22 + jb2, lda);
-            cur_counted = c0words && h->gemm_col0_complete;
-            cur_tiles = h->gemm_col0_tiles;
-            h->gemm_col0_static = nullptr;
-            LSX_TRY(rg);
+            GemmPlan plan = mfma;
+            plan.col0_static = c0words ? c0words + step : nullptr;
+            GemmDone did;
+            LSX_TRY(launch_gemm_sub<T>(h, rest, rest - jb2, jb, L21, lda, A12 + jb2, lda, A22 + jb2, lda, plan, &did));
+            cur_counted = c0words && did.col0_complete;
+            cur_tiles = did.col0_tiles;
         }
         // panel k's interchanges on the columns left of it, in the slack after the update
-        LSX_TRY(apply_panel_swaps<T>(h, k, A, lda, k, jb, d_ipiv + k));
+        LSX_TRY(apply_panel_swaps<T>(h, mv, k, A, lda, k, jb, d_ipiv + k));
         // recorded after the last reader of panel k's gather list: panel k+2 (launched by the side stream
         // behind its wait on this event) writes the same buffer
         LSX_HIP(hipEventRecord(h->ev_next, main_s));
         have_update = true;
-        h->moves_valid = next_valid;
+        listed = pa.listed;
         prev_counted = cur_counted;
         prev_tiles = cur_tiles;
     }
@@ -321,31 +307,20 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
 //   for the whole factorisation by one launch at the end (one gather list per panel is kept).
 // Factors and pivots are bit-identical to the other drivers (same kernels per element, tests).
 template <typename T>
-static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int *d_info, T *Tinv, int k0) {
+static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int *d_info, T *Tinv, PanelArgs pa,
+                             int k0) {
     const int nb = h->nb;
     const int nsteps = (n - k0 + nb - 1) / nb;
     hipStream_t main_s = h->stream, side = h->side_stream;
-    struct OnSide {
-        lsx_handle_t h; hipStream_t keep;
-        OnSide(lsx_handle_t h_, hipStream_t s) : h(h_), keep(h_->stream) { h->stream = s; }
-        ~OnSide() { h->stream = keep; }
-    };
+    GemmPlan mfma;   // every update of an LU: see GemmPlan
+    mfma.mfma_only = true;
     // exchange area of the XCD panel (kernels_panel_x.hip) sized for the tallest panel; each launch needs it all zero
-    const size_t area_x = panel_x_area_bytes(h, n - k0, sizeof(T));
+    const size_t area_x = panel_x_area_bytes(h, pa.mode, n - k0, sizeof(T));
     const size_t pass_bytes = pad256(256 + (size_t)nsteps * sizeof(int)), ctr_bytes = pad256((size_t)nsteps * 8 * sizeof(int));
     const size_t col0_bytes = pad256((size_t)nsteps * 2 * sizeof(int));
     const size_t words = pass_bytes + ctr_bytes + col0_bytes + pad256((size_t)nsteps * sizeof(int));
     if (area_x == 0 || 3 * area_x + words > h->scratch_bytes) { set_error("getrf_lookahead_x: scratch"); return LSX_ERR_INTERNAL; }
     LSX_TRY(grow(&h->moves_all, &h->moves_all_bytes, (size_t)nsteps * 2048));
-    struct Restore {
-        lsx_handle_t h; hipStream_t keep;
-        ~Restore() {
-            h->stream = keep; h->panel_area_stride = 0; h->panel_area = 0; h->moves = h->moves_buf[0];
-            h->gemm_queue = 0; h->gemm_counters = nullptr; h->gemm_avoid_word = nullptr; h->gemm_pass_word = nullptr;
-            h->gemm_col0 = nullptr; h->panel_xcc_word = nullptr; h->chain_info = nullptr;
-        }
-    } restore{h, main_s};
-    h->chain_info = d_info;
     JoinSide join{h, side, main_s, main_s};
     // three exchange areas in rotation (panel j uses area j % 3, cleared behind update j), then the words
     char *wbase = (char *)h->scratch + 3 * area_x;
@@ -357,18 +332,18 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
     for (int s = 0; s < 3; ++s) LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)s * area_x, 0, area_x, main_s));
     LSX_HIP(hipMemsetAsync(wbase, 0, words, main_s));
     LSX_HIP(hipMemsetD32Async((hipDeviceptr_t)xcc_word, 1, 1, main_s));
-    h->panel_area_stride = area_x;
-    h->panel_xcc_word = xcc_word;
+    pa.area_bytes = area_x;
+    pa.xcc_word = xcc_word;
     LSX_HIP(hipEventRecord(h->ev_start, main_s));
     LSX_HIP(hipStreamWaitEvent(side, h->ev_start, 0));
-    auto list = [&](int s) { return (void *)((char *)h->moves_all + (size_t)s * 2048); };
+    auto list = [&](int s) { return (int2 *)((char *)h->moves_all + (size_t)s * 2048); };   // one gather list per panel
     T *Tinv2[2] = {Tinv, Tinv + (size_t)((nb + 63) / 64) * 4096};
     {
-        OnSide g(h, side);
-        h->moves = list(0);
-        h->panel_area = 0;
-        LSX_TRY(launch_panel<T>(h, n - k0, (n - k0) < nb ? (n - k0) : nb, A + (size_t)k0 * lda + k0, lda, k0, d_ipiv + k0, d_info));
-        if (!h->moves_valid) { set_error("getrf_lookahead_x: panel without a gather list"); return LSX_ERR_INTERNAL; }
+        OnStream g(h, side);
+        pa.list = list(0);
+        pa.area_off = 0;
+        LSX_TRY(launch_panel<T>(h, n - k0, (n - k0) < nb ? (n - k0) : nb, A + (size_t)k0 * lda + k0, lda, k0, d_ipiv + k0, d_info, pa));
+        if (!pa.listed) { set_error("getrf_lookahead_x: panel without a gather list"); return LSX_ERR_INTERNAL; }
     }
     // What the chain of step k needs from the main stream is update k-1 on the NEXT panel's columns only.  When that
     // update went through the work queue with no edge launches, its kernel does those columns (tile column 0) first
@@ -398,25 +373,23 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
         const int jb2 = rest < nb ? rest : nb;  // width of the next panel
         bool fused_all = false;
         {
-            OnSide g(h, side);
+            OnStream g(h, side);
             // update k-1 wrote the next panel's columns: its column-0 count (waited for inside the chain head), or the
             // event behind all of it
             const bool counted = step > 0 && prev_col0;
             if (step > 0 && !counted) LSX_HIP(hipStreamWaitEvent(side, h->ev_next, 0));
-            h->moves = list(step);
-            h->moves_valid = true;
             // block inverses, interchanges and U12 of the next panel's columns in one launch where the shapes allow it
-            const int all = launch_chain_fused<T>(h, jb, Akk, lda, Ti, jb2, A + k + jb, lda, k,
+            const int all = launch_chain_fused<T>(h, list(step), d_info, jb, Akk, lda, Ti, jb2, A + k + jb, lda, k,
                                                   counted ? col0 + 2 * (step - 1) + 1 : nullptr, prev_tiles, ready + step);
             if (all < 0) return all;
             if (all == 1) {
-                const int fused = launch_chain_head<T>(h, jb, Akk, lda, Ti, jb2, A + k + jb, lda, k,
+                const int fused = launch_chain_head<T>(h, list(step), d_info, jb, Akk, lda, Ti, jb2, A + k + jb, lda, k,
                                                        counted ? col0 + 2 * (step - 1) + 1 : nullptr, prev_tiles);
                 if (fused < 0) return fused;
                 if (fused == 1) {
-                    if (counted) LSX_TRY(launch_wait_count(h, col0 + 2 * (step - 1) + 1, prev_tiles));
+                    if (counted) LSX_TRY(launch_wait_count(h, col0 + 2 * (step - 1) + 1, prev_tiles, d_info));
                     LSX_TRY(launch_trtri<T>(h, 1, jb, Akk, lda, Ti));
-                    LSX_TRY(launch_laswp_moves<T>(h, jb2, A + k + jb, lda, k));
+                    LSX_TRY(launch_laswp_moves<T>(h, list(step), jb2, A + k + jb, lda, k));
                 }
             }
             // HEAD: block inverses of panel k are there.  The fused launch counts them in a device word the main stream
@@ -427,38 +400,26 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
                 LSX_HIP(hipEventRecord(h->ev_panel, side));
                 LSX_TRY(launch_trsm_block<T>(h, 1, jb, jb2, Akk, lda, Ti, A12, lda));
             }
-            LSX_TRY(launch_gemm_sub<T>(h, rest, jb2, jb, L21, lda, A12, lda, A22, lda));
+            LSX_TRY(launch_gemm_sub<T>(h, rest, jb2, jb, L21, lda, A12, lda, A22, lda, mfma));
         }
         // main stream, behind HEAD.  Measured alternatives (8192^2 / 4096^2, ms): this order 18.2 / 7.6; interchanges
         // ahead of HEAD and the area cleared by the update's idle workgroups, so that the update starts earlier,
         // 18.5 / 7.9 (its resident workgroups take the CUs the next panel's small update needs: 27 instead of 17 us);
         // the update ordered behind that small update by an event 19.0 / 8.0 (a cross-stream hop on the chain).
-        if (fused_all) LSX_TRY(launch_wait_count(h, ready + step, 2));
+        if (fused_all) LSX_TRY(launch_wait_count(h, ready + step, 2, d_info));
         else LSX_HIP(hipStreamWaitEvent(main_s, h->ev_panel, 0));
-        int queued = 0;
-        bool cur_col0 = false;
-        int cur_tiles = 0;
+        GemmDone did;   // of the big update
         if (rest > jb2) {
-            h->moves = list(step);
-            h->moves_valid = true;
-            LSX_TRY(launch_laswp_moves<T>(h, rest - jb2, A + k + jb + jb2, lda, k));
+            LSX_TRY(launch_laswp_moves<T>(h, list(step), rest - jb2, A + k + jb + jb2, lda, k));
             LSX_TRY(launch_trsm_block<T>(h, 1, jb, rest - jb2, Akk, lda, Ti, A12 + jb2, lda));
-            h->gemm_queue = 1;
-            h->gemm_counters = counters + 8 * step;
-            h->gemm_counter_sets = 1;
-            h->gemm_counter_set = 0;
-            h->gemm_avoid_word = xcc_word;
-            h->gemm_pass_word = pass + step;
-            h->gemm_col0 = use_col0 ? col0 + 2 * step : nullptr;
-            const int rq = launch_gemm_sub<T>(h, rest, rest - jb2, jb, L21, lda, A12 + jb2, lda, A22 + jb2, lda);
-            queued = h->gemm_queue_used;
-            cur_col0 = queued && h->gemm_col0_complete;
-            cur_tiles = h->gemm_col0_tiles;
-            h->gemm_queue = 0;
-            h->gemm_counters = nullptr;
-            h->gemm_col0 = nullptr;
-            LSX_TRY(rq);
+            GemmPlan plan = mfma;
+            plan.counters = counters + 8 * step;
+            plan.avoid_word = xcc_word;
+            plan.pass_word = pass + step;
+            plan.col0 = use_col0 ? col0 + 2 * step : nullptr;
+            LSX_TRY(launch_gemm_sub<T>(h, rest, rest - jb2, jb, L21, lda, A12 + jb2, lda, A22 + jb2, lda, plan, &did));
         }
+        const bool cur_col0 = did.queued && did.col0_complete;
         // panel k is done with its exchange area and panel k+3 reuses it: cleared behind the update, off the path
         // HEAD -> update start -> panel k+1; the chain of panel k+3 waits for (a part of) update k+1, behind this
         LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)(step % 3) * area_x, 0, area_x, main_s));
@@ -474,28 +435,24 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
                 LSX_TRY(launch_laswp_left_all<T>(h, A, lda, k0 + left_done * nb, nb, step - left_done, list(left_done)));
                 left_done = step;
             }
-            if (k > 0) {
-                h->moves = list(step);
-                h->moves_valid = true;
-                LSX_TRY(launch_laswp_moves<T>(h, k, A, lda, k));
-            }
+            if (k > 0) LSX_TRY(launch_laswp_moves<T>(h, list(step), k, A, lda, k));
             left_done = step + 1;
         }
         {
-            OnSide g(h, side);
+            OnStream g(h, side);
             // The gate (panel k+1 not before update k has started) is still wanted while the panel takes nearly every
             // CU of its XCD: launched earlier, it starves the main stream's small kernels in front of the update of
             // their eighth of workgroups dealt to that XCD (8192^2, steps 2-7: 640 instead of 455 us per step).
             // (fp32 panels above 8192 rows keep 512 rows per workgroup: 25 of 32 CUs at 12800 rows)
             const bool tall = (rest > 6400 && (sizeof(T) == 8 || rest <= 8192)) || rest > 12800;
-            if (queued && (!cur_col0 || tall)) LSX_TRY(launch_gate(h, pass + step, 2 * h->num_cu / 8));
-            h->moves = list(step + 1);
-            h->panel_area = (step + 1) % 3;
-            LSX_TRY(launch_panel<T>(h, rest, jb2, A22, lda, k + jb, d_ipiv + k + jb, d_info));
-            if (!h->moves_valid) { set_error("getrf_lookahead_x: panel without a gather list"); return LSX_ERR_INTERNAL; }
+            if (did.queued && (!cur_col0 || tall)) LSX_TRY(launch_gate(h, pass + step, 2 * h->num_cu / 8));
+            pa.list = list(step + 1);
+            pa.area_off = (size_t)((step + 1) % 3) * area_x;
+            LSX_TRY(launch_panel<T>(h, rest, jb2, A22, lda, k + jb, d_ipiv + k + jb, d_info, pa));
+            if (!pa.listed) { set_error("getrf_lookahead_x: panel without a gather list"); return LSX_ERR_INTERNAL; }
         }
         prev_col0 = cur_col0;
-        prev_tiles = cur_tiles;
+        prev_tiles = did.col0_tiles;
     }
     // the last panel is factored; every panel's interchanges on the columns left of it
     LSX_HIP(hipEventRecord(h->ev_panel, side));
@@ -511,19 +468,24 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
 int ensure_getrf_workspace(lsx_handle_t h, int n, size_t elem) {
     LSX_TRY(ensure_scratch(h, pad256(16 * ((size_t)n / 32 + 2)) + 2 * pad256(elem * 2 * (size_t)n) +
                                   ((size_t)n / 32 + 2) * 5248 + 8192 +
-                                  3 * panel_x_area_bytes(h, n, elem) + 16384 +
+                                  3 * panel_x_area_bytes(h, h->panel_mode, n, elem) + 16384 +
                                   ((size_t)n / 16 + 2) * 40));
     const size_t tinv_elems = (size_t)((h->nb * h->kblock + 63) / 64) * 64 * 64;
     return grow(&h->ws2, &h->ws2_bytes, 2 * pad256(tinv_elems * elem));   // x2: the look-ahead driver alternates
 }
 
 // ---------------------------------------------------------------- blocked LU driver
+// percolumn: the host fall-back after an exchange time-out -- per-column panel launches (mode 0: no workgroup waits
+// for another) in the sequential driver, whatever the handle's options say.
 template <typename T>
-static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int *d_info) {
+static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int *d_info, bool percolumn = false) {
     LSX_ARG(n >= 0 && lda >= n && A && d_ipiv);
     if (n == 0) return LSX_OK;
     const int nb = h->nb;
-    struct MfmaOnly { lsx_handle_t h; MfmaOnly(lsx_handle_t h_) : h(h_) { h->gemm_mfma_only = true; } ~MfmaOnly() { h->gemm_mfma_only = false; } } mfma_only(h);
+    PanelArgs pa(h, h->moves_buf[0]);
+    if (percolumn) pa.mode = 0;
+    GemmPlan mfma;   // every update of an LU: see GemmPlan
+    mfma.mfma_only = true;
     LSX_TRY(ensure_getrf_workspace(h, n, sizeof(T)));
     T *Tinv = (T *)h->ws2;
     if (!d_info) d_info = h->dev_status + 2;   // a time-out must be recorded somewhere: lsx_check_status reads it
@@ -535,14 +497,10 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
     int LOOKAHEAD_MIN = sizeof(T) == 8 ? 7168 : 10240;   // fp32: the update is half as long, break-even higher
     // XCD-scope panel and its own schedule.  Measured against the sequential driver: fp64 1536 0 %, 2048 +2 %, 2560 +4.5 %,
     // 3072 +7 %; fp32 (short updates) 3072 -1 %, 4096 0 %, 5120 +3 %, 6144 +7 %, 7168 +12 %.
-    if (h->panel_mode == 4) LOOKAHEAD_MIN = sizeof(T) == 8 ? 2048 : 4096;
+    if (pa.mode == 4) LOOKAHEAD_MIN = sizeof(T) == 8 ? 2048 : 4096;
     if (h->lookahead_min > 0) LOOKAHEAD_MIN = h->lookahead_min;                  // option (tests, tuning)
-    if (const char *e = getenv("LSX_LOOKAHEAD_MIN")) {   // diagnostics
-        const int v = atoi(e);
-        if (v > 0) LOOKAHEAD_MIN = v;
-    }
     int k_end = n;  // the sequential driver below handles columns [0, k_end)
-    if (h->lookahead && n >= LOOKAHEAD_MIN && h->kblock == 1) k_end = 0;
+    if (h->lookahead && !percolumn && n >= LOOKAHEAD_MIN && h->kblock == 1) k_end = 0;
     const int W = nb * h->kblock;
     for (int k = 0; k < k_end; k += W) {
         const int w = (n - k < W) ? n - k : W;  // width of this super-block
@@ -550,12 +508,12 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
             const int c = k + j;                      // first column of this panel
             const int jb = (w - j < nb) ? w - j : nb;
             T *Acc = A + (size_t)c * lda + c;
-            LSX_TRY(launch_panel<T>(h, n - c, jb, Acc, lda, c, d_ipiv + c, d_info));
-            if (h->moves_valid) {   // left and right of the panel in one launch
-                LSX_TRY(launch_laswp_moves_around<T>(h, n, A, lda, c, c, jb));
+            LSX_TRY(launch_panel<T>(h, n - c, jb, Acc, lda, c, d_ipiv + c, d_info, pa));
+            if (pa.listed) {   // left and right of the panel in one launch
+                LSX_TRY(launch_laswp_moves_around<T>(h, (const int2 *)pa.list, n, A, lda, c, c, jb));
             } else {
-                LSX_TRY(apply_panel_swaps<T>(h, c, A, lda, c, jb, d_ipiv + c));                      // left
-                LSX_TRY(apply_panel_swaps<T>(h, n - c - jb, A + c + jb, lda, c, jb, d_ipiv + c));  // right
+                LSX_TRY(launch_laswp<T>(h, c, A, lda, c, jb, d_ipiv + c));                      // left
+                LSX_TRY(launch_laswp<T>(h, n - c - jb, A + c + jb, lda, c, jb, d_ipiv + c));  // right
             }
             const int inner = w - j - jb;  // columns of the super-block still to be factored
             if (inner > 0) {
@@ -563,7 +521,7 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
                 LSX_TRY(launch_trtri<T>(h, 1, jb, Acc, lda, Tinv));
                 LSX_TRY(launch_trsm_block<T>(h, 1, jb, inner, Acc, lda, Tinv, A12, lda));
                 LSX_TRY(launch_gemm_sub<T>(h, n - c - jb, inner, jb, A + (size_t)(c + jb) * lda + c, lda, A12,
-                                           lda, A + (size_t)(c + jb) * lda + c + jb, lda));
+                                           lda, A + (size_t)(c + jb) * lda + c + jb, lda, mfma));
             }
         }
         const int rest = n - k - w;
@@ -580,7 +538,7 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
                     const int jb = (w - j < nb) ? w - j : nb;
                     if (j > 0)
                         LSX_TRY(launch_gemm_sub<T>(h, jb, rest, j, Akk + (size_t)j * lda, lda, A12, lda,
-                                                   A12 + (size_t)j * lda, lda));
+                                                   A12 + (size_t)j * lda, lda, mfma));
                     LSX_TRY(launch_trsm_block<T>(h, 1, jb, rest, Akk + (size_t)j * lda + j, lda,
                                                  Tinv + (size_t)(j / 64) * 4096, A12 + (size_t)j * lda, lda));
                 }
@@ -588,7 +546,7 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
                 LSX_TRY(launch_trsm_block<T>(h, 1, w, rest, Akk, lda, Tinv, A12, lda));
             }
             LSX_TRY(launch_gemm_sub<T>(h, rest, rest, w, A + (size_t)(k + w) * lda + k, lda, A12, lda,
-                                       A + (size_t)(k + w) * lda + k + w, lda));
+                                       A + (size_t)(k + w) * lda + k + w, lda, mfma));
         }
     }
     if (k_end < n) {
@@ -597,17 +555,17 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
         // device-scope panel (12288^2 fp64: 46.4 -> see DESIGN 6).
         int xrows = 32 * 64 * (sizeof(T) == 8 ? 4 : 8);
         if (h->xrows_limit > 0 && h->xrows_limit < xrows) xrows = h->xrows_limit;   // tests: hand-over at small orders
-        if (h->panel_mode == 4 && !h->panel_debug && nb % 32 == 0 && k_end % 32 == 0 &&
-            panel_x_area_bytes(h, n - k_end, sizeof(T)) > 0) {
+        if (pa.mode == 4 && !h->panel_debug && nb % 32 == 0 && k_end % 32 == 0 &&
+            panel_x_area_bytes(h, pa.mode, n - k_end, sizeof(T)) > 0) {
             int kx = k_end;
             if (n - kx > xrows) kx += (n - kx - xrows + nb - 1) / nb * nb;
             if (h->hybrid_off && kx > k_end) kx = n;
             if (kx < n) {
-                if (kx > k_end) LSX_TRY(getrf_lookahead<T>(h, n, A, lda, d_ipiv, d_info, Tinv, k_end, kx));
-                return getrf_lookahead_x<T>(h, n, A, lda, d_ipiv, d_info, Tinv, kx);
+                if (kx > k_end) LSX_TRY(getrf_lookahead<T>(h, n, A, lda, d_ipiv, d_info, Tinv, pa, k_end, kx));
+                return getrf_lookahead_x<T>(h, n, A, lda, d_ipiv, d_info, Tinv, pa, kx);
             }
         }
-        return getrf_lookahead<T>(h, n, A, lda, d_ipiv, d_info, Tinv, k_end);
+        return getrf_lookahead<T>(h, n, A, lda, d_ipiv, d_info, Tinv, pa, k_end);
     }
     return LSX_OK;
 }
@@ -618,7 +576,7 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
 // the MFMA pipe instead of 0.68, profiles/r03_pmc_gemm_mfma.json, and there are half as many launches), the block row in
 // between gets its own 128-deep update first.  Per element the same fused multiply-adds in the same order as one block at a
 // time: the accumulators start from C and take k in sequence either way; going upwards, where the block that comes second
-// in memory must be applied first, the tile rotates its k index (gemm_kshift).  Same bits (tools/getri_ab.py, tests).
+// in memory must be applied first, the tile rotates its k index (GemmPlan::kshift).  Same bits (tools/getri_ab.py, tests).
 // tri (forward sweep of the inverse): block row kb only has columns [0, kb + jb) to work on, the others are exact zeros.
 template <typename T>
 static int sweep_forward(lsx_handle_t h, int n, int ncols, bool tri, bool pairs, const T *LU, int lda, const T *TinvL, T *X, int ldx) {
@@ -665,10 +623,9 @@ static int sweep_backward(lsx_handle_t h, int n, int ncols, bool pairs, const T 
         LSX_TRY(launch_trsm_block<T>(h, 0, sb, ncols, Up(lo, lo), lda, TinvU + (size_t)(lo / 64) * 4096, Xp(lo), ldx));
         if (lo > 0) {
             // rows above the pair: k runs over block kb first, then block lo -- the order of one block at a time
-            h->gemm_kshift = sb;
-            const int rc = launch_gemm_sub<T>(h, lo, ncols, sb + jb, Up(0, lo), lda, Xp(lo), ldx, X, ldx);
-            h->gemm_kshift = 0;
-            LSX_TRY(rc);
+            GemmPlan rotated;
+            rotated.kshift = sb;
+            LSX_TRY(launch_gemm_sub<T>(h, lo, ncols, sb + jb, Up(0, lo), lda, Xp(lo), ldx, X, ldx, rotated));
         }
         kb = lo - sb;
     }
@@ -678,7 +635,7 @@ static int sweep_backward(lsx_handle_t h, int n, int ncols, bool pairs, const T 
 // two blocks per update pay where the updates are large and regular (8192^2 inverse 17.8 -> 15.7 ms, 4096^2 3.18 -> 3.05;
 // ragged or small orders lose 3-12 % to the extra launches and the edge kernels)
 static bool sweep_pairs(lsx_handle_t h, int n, int ncols) {
-    return h->getri_pairs && !h->gemm_queue && ncols >= 1024 && (n >= 7168 || (n % 128 == 0 && n >= 4096));
+    return h->getri_pairs && ncols >= 1024 && (n >= 7168 || (n % 128 == 0 && n >= 4096));
 }
 
 // X <- U^-1 L^-1 X for X already row-permuted (n x nrhs)
@@ -802,12 +759,7 @@ static int factor_from_host(lsx_handle_t h, int n, const T *A, int lda, T *dA, i
         if (attempt == 0) {
             rc = getrf_dev<T>(h, n, dA, ld, dp, dinfo);
         } else {
-            const int mode = h->panel_mode, look = h->lookahead;
-            h->panel_mode = 0;
-            h->lookahead = 0;
-            rc = getrf_dev<T>(h, n, dA, ld, dp, dinfo);
-            h->panel_mode = mode;
-            h->lookahead = look;
+            rc = getrf_dev<T>(h, n, dA, ld, dp, dinfo, true);
             h->panel_fallbacks += 1;
         }
         LSX_TRY(rc);
@@ -1141,8 +1093,8 @@ int lsx_create(lsx_handle_t *out, int device) {
     if (r == LSX_OK) {
         size_t mv = 0;
         r = grow(&h->moves_buf[0], &mv, 8192);
+        h->moves_api = (char *)h->moves_buf[0] + 2048;
         h->moves_buf[1] = (char *)h->moves_buf[0] + 4096;
-        h->moves = h->moves_buf[0];
     }
     if (r != LSX_OK) { (void)hipStreamDestroy(h->own_stream); delete h; return r; }
     *out = h;
@@ -1475,22 +1427,23 @@ static int rref_first_fast(lsx_handle_t h, int m, int n, int bar, double *R, int
     LSX_TRY(ensure_getrf_workspace(h, m, sizeof(T)));
     T *Tinv = (T *)h->ws2;
     LSX_HIP(hipMemsetAsync(ginfo, 0, sizeof(int), h->stream));
-    struct MfmaOnly { lsx_handle_t h; MfmaOnly(lsx_handle_t h_) : h(h_) { h->gemm_mfma_only = true; } ~MfmaOnly() { h->gemm_mfma_only = false; } } mfma_only(h);
+    GemmPlan mfma;   // as in the LU drivers (the solve and the update of step 3 are no LU updates: plain)
+    mfma.mfma_only = true;
+    PanelArgs pa(h, h->moves_buf[0]);
     for (int k = 0; k < r; k += nb) {
         const int jb = (r - k < nb) ? r - k : nb;
         T *Gkk = Gm + (size_t)k * ldg + k;
-        h->moves_valid = false;
-        const int pr = panel_xcd_first(h, m - k, jb, Gkk, ldg, k, k, ipiv + k, ginfo, ftol);
+        const int pr = panel_xcd_first(h, m - k, jb, Gkk, ldg, k, k, ipiv + k, ginfo, ftol, pa);
         if (dbg && pr != LSX_OK) fprintf(stderr, "rref_first_fast: panel at %d returned %d\n", k, pr);
         if (pr != LSX_OK) return pr;
-        if (!h->moves_valid) { set_error("rref_first: panel without a gather list"); return LSX_ERR_INTERNAL; }
-        LSX_TRY(launch_laswp_moves_around<T>(h, r, Gm, ldg, k, k, jb));         // the other columns of G
+        if (!pa.listed) { set_error("rref_first: panel without a gather list"); return LSX_ERR_INTERNAL; }
+        LSX_TRY(launch_laswp_moves_around<T>(h, (const int2 *)pa.list, r, Gm, ldg, k, k, jb));         // the other columns of G
         const int rest = r - k - jb;
         if (rest > 0) {
             T *G12 = Gkk + jb;
             LSX_TRY(launch_trtri<T>(h, 1, jb, Gkk, ldg, Tinv));
             LSX_TRY(launch_trsm_block<T>(h, 1, jb, rest, Gkk, ldg, Tinv, G12, ldg));
-            LSX_TRY(launch_gemm_sub<T>(h, m - k - jb, rest, jb, Gkk + (size_t)jb * ldg, ldg, G12, ldg, Gkk + (size_t)jb * ldg + jb, ldg));
+            LSX_TRY(launch_gemm_sub<T>(h, m - k - jb, rest, jb, Gkk + (size_t)jb * ldg, ldg, G12, ldg, Gkk + (size_t)jb * ldg + jb, ldg, mfma));
         }
     }
     int hinfo = 0;
@@ -1858,8 +1811,11 @@ int lsx_panel_f64_dev(lsx_handle_t h, int m, int jb, double *dP, int ldp, int ro
                       int *d_info) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && m >= 1 && jb >= 1 && jb <= 256 && dP && d_ipiv && ldp >= jb);
-    LSX_TRY(ensure_scratch(h, std::max(pad256(16 * ((size_t)m / 32 + 2)) + ((size_t)m / 32 + 2) * 5248 + 8192, panel_x_area_bytes(h, m, 8) + 4096)));
-    return launch_panel<double>(h, m, jb, dP, ldp, row0, d_ipiv, d_info);
+    LSX_TRY(ensure_scratch(h, std::max(pad256(16 * ((size_t)m / 32 + 2)) + ((size_t)m / 32 + 2) * 5248 + 8192, panel_x_area_bytes(h, h->panel_mode, m, 8) + 4096)));
+    PanelArgs pa(h, h->moves_api);
+    const int r = launch_panel<double>(h, m, jb, dP, ldp, row0, d_ipiv, d_info, pa);
+    h->moves_api_valid = pa.listed;
+    return r;
 }
 int lsx_laswp_f64_dev(lsx_handle_t h, int ncols, double *dA, int lda, int row0, int jb,
                       const int32_t *d_ipiv) {
@@ -1870,19 +1826,15 @@ int lsx_laswp_f64_dev(lsx_handle_t h, int ncols, double *dA, int lda, int row0, 
 int lsx_panel_moves_dev(lsx_handle_t h, int32_t *d_moves, int *valid) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && d_moves && valid);
-    *valid = h->moves_valid ? 1 : 0;
-    if (h->moves_valid)
-        LSX_HIP(hipMemcpyAsync(d_moves, h->moves, 256 * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    *valid = h->moves_api_valid ? 1 : 0;
+    if (h->moves_api_valid)
+        LSX_HIP(hipMemcpyAsync(d_moves, h->moves_api, 256 * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
     return LSX_OK;
 }
 int lsx_laswp_moves_f64_dev(lsx_handle_t h, int ncols, double *dA, int lda, int row0, const int32_t *d_moves) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && dA && d_moves);
-    void *keep = h->moves;
-    h->moves = (void *)d_moves;
-    const int r = launch_laswp_moves<double>(h, ncols, dA, lda, row0);
-    h->moves = keep;
-    return r;
+    return launch_laswp_moves<double>(h, (const int2 *)d_moves, ncols, dA, lda, row0);
 }
 int lsx_trsm_lu_f64_dev(lsx_handle_t h, int jb, int ncols, const double *dL, int ldl, double *dB,
                         int ldb) {
@@ -1902,12 +1854,12 @@ int lsx_gemm_sub_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dA, 
         int *w = (int *)h->scratch;
         LSX_HIP(hipMemsetAsync(w, 0, 1024, h->stream));
         if (h->gemm_queue_test >= 2) LSX_HIP(hipMemsetD32Async((hipDeviceptr_t)w, 1, 1, h->stream));
-        h->gemm_queue = 1; h->gemm_counters = w + 64; h->gemm_counter_sets = 1; h->gemm_counter_set = 0;
-        h->gemm_avoid_word = h->gemm_queue_test >= 2 ? w : nullptr; h->gemm_pass_word = w + 1;
-        h->gemm_col0 = h->gemm_queue_test == 3 ? w + 32 : nullptr;   // 3: with the column-0-first phase
-        const int r = launch_gemm_sub<double>(h, m, n, k, dA, lda, dB, ldb, dC, ldc);
-        h->gemm_queue = 0; h->gemm_counters = nullptr; h->gemm_avoid_word = nullptr; h->gemm_pass_word = nullptr; h->gemm_col0 = nullptr;
-        return r;
+        GemmPlan plan;
+        plan.counters = w + 64;
+        plan.avoid_word = h->gemm_queue_test >= 2 ? w : nullptr;
+        plan.pass_word = w + 1;
+        plan.col0 = h->gemm_queue_test == 3 ? w + 32 : nullptr;   // 3: with the column-0-first phase
+        return launch_gemm_sub<double>(h, m, n, k, dA, lda, dB, ldb, dC, ldc, plan);
     }
     return launch_gemm_sub<double>(h, m, n, k, dA, lda, dB, ldb, dC, ldc);
 }

@@ -93,35 +93,14 @@ struct lsx_handle_s {
     int trsv_mode = 2;    // few-RHS solve: 2 = 128-row steps + helper workgroups (default), 1 = one cooperative launch per direction with 64-row steps, 0 = one launch per 128-row step
     int gemm_stagger = 0; // trailing update: start delay of every second resident workgroup, units of 8128 clocks
     int gemm_waves = 0;   // waves per workgroup in the trailing-update kernel (0 = auto; 4: 64x64 per wave, 8: 64x32)
-    // trailing update through a work queue (look-ahead driver with the XCD-scope panel): see kernels_gemm.hip
-    int gemm_queue = 0;           // 1: interior tiles are handed out by per-XCD counters
-    const int *gemm_avoid_word = nullptr;  // device word: 1 + XCC id whose workgroups take no tiles (the panel's XCD)
-    int *panel_xcc_word = nullptr;         // where the XCD-scope panel kernel records 1 + its XCC id
-    int *gemm_counters = nullptr; // gemm_counter_sets x 8 ints in scratch, zeroed by the driver
-    int gemm_counter_sets = 0, gemm_counter_set = 0;
-    int *gemm_pass_word = nullptr;   // incremented by every workgroup that leaves because it sits on the avoided XCD
-    int gemm_kshift = 0;             // next gemm launches: the k index starts at this offset and wraps (getri_dev)
     int getri_pairs = 1;             // inverse: two 128-row blocks per trailing update (K = 256), same bits
     int left_per_step = 1;           // XCD look-ahead driver: a panel's interchanges left of it trail its step (0: all at the end)
     int chain_fused = 1;             // 1: chain head and the next panel's block solve in one launch (option chain_fused)
-    int *chain_info = nullptr;       // look-ahead driver: the factorisation's info word, for the chain's in-kernel waits (time-out -> negative)
     int chain_wait_limit = 1 << 21;  // polls of those waits before they give up (option chain_wait_limit: tests inject a time-out with 0)
-    int *gemm_col0_static = nullptr; // shared-CU look-ahead driver: finished-tile count of the static grid's first tile column (zeroed by the driver)
-    int *gemm_col0 = nullptr;        // look-ahead driver: {ticket, done} words of this update's tile column 0 (zeroed by the driver)
-    int gemm_col0_tiles = 0;         // set with it: tiles in that column
     int x_events = 0;                // option x_events (measurements, tests): no column-0 ordering in the XCD-scope schedule
-    bool gemm_col0_complete = false; // set by the last launch_gemm_*: the done word reaching tiles_m means column 0 is final
-    int gemm_queue_used = 0;         // set by the last launch_gemm_*: 1 = its interior went through the queue
     void *moves_all = nullptr;       // look-ahead driver with the XCD-scope panel: one gather list per panel
     size_t moves_all_bytes = 0;
     int panel_debug = 0;  // 1: stamped diagnostic panel kernel (tools/kbench.py)
-    // set by the LU drivers: updates narrower than 16 columns also take the MFMA kernel, so that a column sees the
-    // same summation order whichever driver (sequential / look-ahead) splits the trailing matrix around it
-    bool gemm_mfma_only = false;
-    // look-ahead driver: > 0 = the pipelined panel alternates between two exchange areas this far apart in
-    // `scratch` and the DRIVER clears them (off the panel-to-panel chain); 0 = the launch clears its own
-    size_t panel_area_stride = 0;
-    int panel_area = 0;
     int num_cu = 256;
     // persistent device workspace (grown on demand, never shrunk)
     void *ws = nullptr;      // staging of caller matrices (host-buffer entry points)
@@ -145,10 +124,11 @@ struct lsx_handle_s {
     void *ws7 = nullptr;     // condition estimate: the iteration vector, its sign vector, the record, an identity interchange list
     size_t ws7_bytes = 0;
     int gecon_solves = 0;    // read-only option: single-right-hand-side solves of the last condition estimate
+    // gather lists (int2[256] each) emitted by the cooperative panel kernels: storage only, a launch is told which one
+    void *moves_buf[2] = {nullptr, nullptr};  // the drivers' lists (the shared-CU look-ahead driver alternates)
+    void *moves_api = nullptr;       // list of the last lsx_panel_f64_dev call, handed out by lsx_panel_moves_dev
+    bool moves_api_valid = false;    // that call emitted one (touched by those two entry points only)
     // small fixed device scratch: pivot search partials, flags, info words
-    void *moves = nullptr;      // int2[256]: gather list emitted by the cooperative panel kernel (current buffer)
-    void *moves_buf[2] = {nullptr, nullptr};  // the look-ahead driver alternates between two lists
-    bool moves_valid = false;   // set by the last panel launch when `moves` describes its interchanges
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
     // device status words (never cleared by kernels): [0] panel exchange time-outs when the caller gave no info
@@ -167,10 +147,49 @@ struct lsx_handle_s {
 
 namespace lsx {
 
+// launches inside this scope go to stream s: h->stream is the ambient "stream in use", this guard alone swaps it
+struct OnStream {
+    lsx_handle_t h; hipStream_t keep;
+    OnStream(lsx_handle_t h_, hipStream_t s) : h(h_), keep(h_->stream) { h->stream = s; }
+    ~OnStream() { h->stream = keep; }
+};
+
+// How one trailing-update launch (launch_gemm_*) is scheduled; the default is the plain static grid.
+struct GemmPlan {
+    int kshift = 0;               // the k index starts at this offset and wraps (pair form of the backward sweep)
+    // LU drivers: updates narrower than 16 columns also take the MFMA kernel, so that a column sees the same summation
+    // order whichever driver (sequential / look-ahead / multi-device) splits the trailing matrix around it
+    bool mfma_only = false;
+    int *col0_static = nullptr;   // static grid: finished-tile count of its first tile column (zeroed by the driver)
+    // interior tiles through the work queue (look-ahead driver with the XCD-scope panel, kernels_gemm.hip)
+    int *counters = nullptr;      // non-null = queue: the eight per-XCD strip counters, zeroed by the driver
+    const int *avoid_word = nullptr;   // device word: 1 + XCC id whose workgroups take no tiles (the panel's XCD)
+    int *pass_word = nullptr;     // incremented by every workgroup that leaves because it sits on the avoided XCD
+    int *col0 = nullptr;          // {ticket, done} words of the update's tile column 0 (zeroed by the driver)
+};
+// What launch_gemm_* reports about the launch it made.
+struct GemmDone {
+    bool queued = false;          // the interior went through the queue
+    bool col0_complete = false;   // the column-0 count reaching col0_tiles means that column is final
+    int col0_tiles = 0;
+};
+
+// Where one panel launch writes and which form it takes.  mode / nt / rt start as the handle's options; a driver that
+// needs other values (shared-CU schedule, tall panels, host fall-back) changes its own copy.
+struct PanelArgs {
+    int mode, nt, rt;             // effective panel mode, threads per workgroup, rows per thread
+    void *list;                   // int2[256]: where a cooperative kernel writes this panel's gather list
+    size_t area_off = 0, area_bytes = 0;   // exchange area inside scratch that the DRIVER keeps cleared (off the panel-to-panel chain); 0 bytes = the launch clears its own
+    int *xcc_word = nullptr;      // where the XCD-scope kernel records 1 + its XCC id
+    bool listed = false;          // out: a cooperative kernel ran, `list` describes this panel's interchanges
+    PanelArgs(lsx_handle_t h, void *list_) : mode(h->panel_mode), nt(h->panel_nt), rt(h->panel_rt), list(list_) {}
+};
+
 int ensure_ws(lsx_handle_t h, size_t bytes);
 int ensure_getrf_workspace(lsx_handle_t h, int n, size_t elem);
 // XCD-scope panel under the reference's first-non-zero pivot rule (kernels_panel_x.hip); 1 = shape not served
-int panel_xcd_first(lsx_handle_t h, int m, int jb, double *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, double tol);
+int panel_xcd_first(lsx_handle_t h, int m, int jb, double *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, double tol,
+                    PanelArgs &pa);
 template <typename T>
 int launch_gather_pivot_cols(lsx_handle_t h, int m, int r, int row_lo, const T *src, int lds, const int32_t *d_pivots, T *dst, int ldd);
 template <typename T>
@@ -178,7 +197,7 @@ int launch_rref_finish(lsx_handle_t h, int m, int bar, T *W, int ldw, const int3
 template <typename T>
 int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *d_pivots, int *d_rank, double tol, int pivot_rule);   // scratch + block-inverse workspace of one LU (api.hip)
 
-// RAII-less profiling bracket: call begin() before a launch group, end() after.
+// Profiling bracket of a launch group: the constructor records the start event, the destructor the end event.
 struct ProfScope {
     lsx_handle_t h;
     hipStream_t st;
@@ -221,31 +240,32 @@ int launch_fill(lsx_handle_t h, int kind, uint64_t seed, int m, int n, T *A, int
                 int col_off);
 template <typename T>
 int launch_gemm_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb,
-                    T *C, int ldc);
+                    T *C, int ldc, const GemmPlan &plan = GemmPlan(), GemmDone *done = nullptr);
 // C += A*B (plus = 1) or C -= A*B (plus = 0), same MFMA kernel
 template <typename T>
 int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, int lda, const T *B, int ldb,
-                    T *C, int ldc);
+                    T *C, int ldc, const GemmPlan &plan = GemmPlan(), GemmDone *done = nullptr);
 // traced reference-order row reduction (kernels_trace.hip); d_out = {pivots, steps, overflow}
 int launch_rref_trace(lsx_handle_t h, int m, int n, int bar, double *R, int ldr, unsigned char *Tm,
                       int32_t *d_pivots, int32_t *d_steps, int max_steps, double *d_snaps,
                       unsigned char *d_snap_t, int max_snaps, int *d_out);
 template <typename T>
 int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t *d_ipiv,
-                 int *d_info);
-// bytes of one exchange area of the pipelined panel for panels of up to m rows; 0 = this handle's panel
+                 int *d_info, PanelArgs &pa);
+// bytes of one exchange area of the pipelined panel for panels of up to m rows; 0 = these panel
 // settings are not ones the pipelined kernel serves for every height <= m
-size_t panel_pipe_area_bytes(lsx_handle_t h, int m);
-size_t panel_x_area_bytes(lsx_handle_t h, int m, size_t elem);
+size_t panel_pipe_area_bytes(lsx_handle_t h, int mode, int nt, int rt, int m);
+size_t panel_x_area_bytes(lsx_handle_t h, int mode, int m, size_t elem);
 template <typename T>
 int launch_laswp(lsx_handle_t h, int ncols, T *A, int lda, int row0, int jb, const int32_t *d_ipiv);
-// same interchanges from the gather list h->moves (written by the cooperative panel kernel)
+// same interchanges from a gather list (written by the cooperative panel kernel)
 template <typename T>
-int launch_laswp_moves(lsx_handle_t h, int ncols, T *A, int lda, int row0);
+int launch_laswp_moves(lsx_handle_t h, const int2 *moves, int ncols, T *A, int lda, int row0);
 template <typename T>
 int launch_laswp_left_all(lsx_handle_t h, T *A, int lda, int k0, int nb, int nsteps, const void *lists);
 int launch_gate(lsx_handle_t h, const int *word, int target);
-int launch_wait_count(lsx_handle_t h, const int *word, int target);
+// info: the factorisation's info word (a time-out makes it negative), or null
+int launch_wait_count(lsx_handle_t h, const int *word, int target, int *info);
 int launch_resid_mixed(lsx_handle_t h, int n, int nrhs, const float *A, int lda, const float *B, int ldb, const double *X,
                        int ldx, float *R, int ldr);
 int launch_refine_apply(lsx_handle_t h, int n, int nrhs, int init, const float *D, int ldd, double *X, int ldx, float *Xf,
@@ -254,19 +274,20 @@ template <typename T>
 int diag_chain_head(lsx_handle_t h, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A, int lda, int row0,
                     const void *moves);
 template <typename T>
-int launch_laswp_moves_around(lsx_handle_t h, int n, T *A, int lda, int row0, int hole_at, int hole_w);
+int launch_laswp_moves_around(lsx_handle_t h, const int2 *moves, int n, T *A, int lda, int row0, int hole_at, int hole_w);
 // Tinv (ceil(jb/64) blocks of 64x64) <- inverses of the 64x64 diagonal blocks of the
 // unit-lower (lower=1) or non-unit upper (lower=0) triangle stored at T.
 template <typename T>
 int launch_trtri(lsx_handle_t h, int lower, int jb, const T *Tm, int ldt, T *Tinv);
-// trtri(unit lower) + gather-list interchanges on a column block in one launch; 1 = not applicable
+// trtri(unit lower) + gather-list interchanges on a column block in one launch; 1 = not applicable (no list: moves
+// null, or shapes).  info: the factorisation's info word for the in-kernel wait (time-out -> negative), or null
 template <typename T>
-int launch_chain_head(lsx_handle_t h, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A, int lda, int row0,
-                      const int *wait_word = nullptr, int wait_target = 0);
+int launch_chain_head(lsx_handle_t h, const int2 *moves, int *info, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A,
+                      int lda, int row0, const int *wait_word = nullptr, int wait_target = 0);
 // chain head + block solve of the next panel's 128 columns in one launch (kernels_misc.hip); 1 = shapes not served
 template <typename T>
-int launch_chain_fused(lsx_handle_t h, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A, int lda, int row0,
-                       const int *wait_word, int wait_target, int *ready);
+int launch_chain_fused(lsx_handle_t h, const int2 *moves, int *info, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A,
+                       int lda, int row0, const int *wait_word, int wait_target, int *ready);
 template <typename T>
 int launch_trtri_both(lsx_handle_t h, int n, const T *LU, int lda, T *invL, T *invU);
 // B (jb x ncols) <- inv(Tm) * B in place; Tinv = inverses of Tm's 64x64 diagonal blocks.

@@ -411,16 +411,19 @@ __global__ __launch_bounds__(256) void gemm_sub_skinny_kernel(int M, int N, int 
 
 template <typename T>
 int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, int lda, const T *B, int ldb,
-                    T *C, int ldc) {
+                    T *C, int ldc, const GemmPlan &plan, GemmDone *done) {
+    GemmDone unread;
+    GemmDone &did = done ? *done : unread;
+    did = GemmDone();
     if (m <= 0 || n <= 0 || k <= 0) return LSX_OK;
-    h->gemm_queue_used = 0;
-    h->gemm_col0_complete = false;
-    const bool skinny = n < 16 && !h->gemm_mfma_only && !h->gemm_kshift;
-    if (h->gemm_kshift && (h->gemm_queue || h->gemm_kshift >= k || h->gemm_kshift > 0xfff || h->gemm_kshift % BK || (k - h->gemm_kshift) % BK)) {
-        set_error("gemm: k rotation %d not served here (k = %d)", h->gemm_kshift, k);
+    const bool queue = plan.counters != nullptr;
+    const int kshift = plan.kshift;
+    const bool skinny = n < 16 && !plan.mfma_only && !kshift;
+    if (kshift && (queue || kshift >= k || kshift > 0xfff || kshift % BK || (k - kshift) % BK)) {
+        set_error("gemm: k rotation %d not served here (k = %d)", kshift, k);
         return LSX_ERR_INTERNAL;
     }
-    const bool tiles64 = !h->gemm_queue && n >= 16 && sizeof(T) == 8 && (h->gemm_waves == 0 || h->gemm_waves == 8) && m % 64 == 0 &&
+    const bool tiles64 = !queue && n >= 16 && sizeof(T) == 8 && (h->gemm_waves == 0 || h->gemm_waves == 8) && m % 64 == 0 &&
                          n % BN == 0 && k % BK == 0 && ((m + BM - 1) / BM) * (n / BN) <= h->num_cu / 2 &&
                          ((size_t)A % 16 == 0) && ((size_t)B % 16 == 0) && ((size_t)C % 16 == 0) && lda % 2 == 0 &&
                          ldb % 2 == 0 && ldc % 2 == 0;
@@ -440,18 +443,18 @@ int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, i
         const int fm = aligned ? m / BM : 0, fn = aligned ? n / BN : 0;  // complete tiles
         // static grid with the counted first tile column (shared-CU look-ahead driver): only when the interior launch
         // covers that column completely, i.e. no edge strip below touches it
-        int *col0s = (h->gemm_col0_static && !h->gemm_queue && waves == 8 && fm == tm && fm > 0 && fn > 1) ? h->gemm_col0_static : nullptr;
-        h->gemm_col0_complete = col0s != nullptr;
-        h->gemm_col0_tiles = fm;
+        int *col0s = (plan.col0_static && !queue && waves == 8 && fm == tm && fm > 0 && fn > 1) ? plan.col0_static : nullptr;
+        did.col0_complete = col0s != nullptr;
+        did.col0_tiles = fm;
         auto go = [&](bool full, int gm, int gn, int om, int on) {
             if (gm <= 0 || gn <= 0) return;
             const dim3 grid(gm * gn);
             if (waves == 8) {
-                if (full) hipLaunchKernelGGL((gemm_sub_kernel<T, 4, true>), grid, dim3(512), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, plus | (h->gemm_stagger << 8) | (h->gemm_kshift << 16), col0s);
-                else hipLaunchKernelGGL((gemm_sub_kernel<T, 4, false>), grid, dim3(512), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, plus | (h->gemm_stagger << 8) | (h->gemm_kshift << 16));
+                if (full) hipLaunchKernelGGL((gemm_sub_kernel<T, 4, true>), grid, dim3(512), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, plus | (h->gemm_stagger << 8) | (kshift << 16), col0s);
+                else hipLaunchKernelGGL((gemm_sub_kernel<T, 4, false>), grid, dim3(512), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, plus | (h->gemm_stagger << 8) | (kshift << 16));
             } else {
-                if (full) hipLaunchKernelGGL((gemm_sub_kernel<T, 2, true>), grid, dim3(256), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, plus | (h->gemm_stagger << 8) | (h->gemm_kshift << 16));
-                else hipLaunchKernelGGL((gemm_sub_kernel<T, 2, false>), grid, dim3(256), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, plus | (h->gemm_stagger << 8) | (h->gemm_kshift << 16));
+                if (full) hipLaunchKernelGGL((gemm_sub_kernel<T, 2, true>), grid, dim3(256), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, plus | (h->gemm_stagger << 8) | (kshift << 16));
+                else hipLaunchKernelGGL((gemm_sub_kernel<T, 2, false>), grid, dim3(256), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, plus | (h->gemm_stagger << 8) | (kshift << 16));
             }
         };
         // skinny updates (the next panel's column block in the look-ahead driver, block rows in the sharded
@@ -459,25 +462,23 @@ int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, i
         if (tiles64) {
             if (m % 32 == 0 && (m / 32) * tn <= h->num_cu && !h->gemm_no_tiles32)   // even skinnier: one 32-row tile per CU
                 hipLaunchKernelGGL((gemm_sub_kernel<T, 4, true, 32>), dim3((m / 32) * tn), dim3(256), 0, h->stream, m, n, k,
-                                   A, lda, B, ldb, C, ldc, m / 32, tn, 0, 0, plus | (h->gemm_kshift << 16));
+                                   A, lda, B, ldb, C, ldc, m / 32, tn, 0, 0, plus | (kshift << 16));
             else
                 hipLaunchKernelGGL((gemm_sub_kernel<T, 4, true, 64>), dim3((m / 64) * tn), dim3(256), 0, h->stream, m, n, k,
-                                   A, lda, B, ldb, C, ldc, m / 64, tn, 0, 0, plus | (h->gemm_kshift << 16));
+                                   A, lda, B, ldb, C, ldc, m / 64, tn, 0, 0, plus | (kshift << 16));
             LSX_HIP(hipGetLastError());
             return LSX_OK;
         }
-        if (h->gemm_queue && fm > 0 && fn > 0 && h->gemm_counters) {
-            h->gemm_queue_used = 1;
+        if (queue && fm > 0 && fn > 0) {
+            did.queued = true;
             // the column-0 count covers that column only if no edge launch below touches it
-            h->gemm_col0_complete = (h->gemm_col0 != nullptr) && fm == tm;
-            h->gemm_col0_tiles = fm;
+            did.col0_complete = (plan.col0 != nullptr) && fm == tm;
             // interior tiles through the work queue (look-ahead driver; counters zeroed by the driver)
             const dim3 grid(2 * h->num_cu);
-            int *ctr = h->gemm_counters + 8 * (h->gemm_counter_set++ % h->gemm_counter_sets);
             if (waves == 8)
-                hipLaunchKernelGGL((gemm_sub_queue_kernel<T, 4>), grid, dim3(512), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, fm, fn, plus, ctr, h->gemm_avoid_word, h->gemm_pass_word, h->gemm_col0);
+                hipLaunchKernelGGL((gemm_sub_queue_kernel<T, 4>), grid, dim3(512), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, fm, fn, plus, plan.counters, plan.avoid_word, plan.pass_word, plan.col0);
             else
-                hipLaunchKernelGGL((gemm_sub_queue_kernel<T, 2>), grid, dim3(256), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, fm, fn, plus, ctr, h->gemm_avoid_word, h->gemm_pass_word, h->gemm_col0);
+                hipLaunchKernelGGL((gemm_sub_queue_kernel<T, 2>), grid, dim3(256), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, fm, fn, plus, plan.counters, plan.avoid_word, plan.pass_word, plan.col0);
         } else {
             go(true, fm, fn, 0, 0);                 // interior
         }
@@ -490,18 +491,18 @@ int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, i
 
 template <typename T>
 int launch_gemm_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C,
-                    int ldc) {
-    return launch_gemm_acc<T>(h, 0, m, n, k, A, lda, B, ldb, C, ldc);
+                    int ldc, const GemmPlan &plan, GemmDone *done) {
+    return launch_gemm_acc<T>(h, 0, m, n, k, A, lda, B, ldb, C, ldc, plan, done);
 }
 
 template int launch_gemm_acc<double>(lsx_handle_t, int, int, int, int, const double *, int, const double *,
-                                     int, double *, int);
+                                     int, double *, int, const GemmPlan &, GemmDone *);
 template int launch_gemm_acc<float>(lsx_handle_t, int, int, int, int, const float *, int, const float *, int,
-                                    float *, int);
+                                    float *, int, const GemmPlan &, GemmDone *);
 template int launch_gemm_sub<double>(lsx_handle_t, int, int, int, const double *, int,
-                                     const double *, int, double *, int);
+                                     const double *, int, double *, int, const GemmPlan &, GemmDone *);
 template int launch_gemm_sub<float>(lsx_handle_t, int, int, int, const float *, int, const float *,
-                                    int, float *, int);
+                                    int, float *, int, const GemmPlan &, GemmDone *);
 
 }  // namespace lsx
 

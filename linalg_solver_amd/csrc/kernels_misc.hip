@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void laswp_moves_kernel(int ncols, T *__restri
 
 // all columns of an n-column matrix except the hole_w columns starting at hole_at, one launch
 template <typename T>
-int launch_laswp_moves_around(lsx_handle_t h, int n, T *A, int lda, int row0, int hole_at, int hole_w) {
+int launch_laswp_moves_around(lsx_handle_t h, const int2 *moves, int n, T *A, int lda, int row0, int hole_at, int hole_w) {
     const int ncols = n - hole_w;
     if (ncols <= 0) return LSX_OK;
     ProfScope ps(h, LSX_PROF_LASWP, 0, 4.0 * sizeof(T) * 128 * (double)ncols);
@@ -198,13 +198,13 @@ int launch_laswp_moves_around(lsx_handle_t h, int n, T *A, int lda, int row0, in
     if (((size_t)A % 16 == 0) && lda % VW == 0 && n % VW == 0 && hole_at % VW == 0 && hole_w % VW == 0) {
         constexpr int CW = 32 / VW;   // the same 32 columns per workgroup, so the grid still covers the chip
         hipLaunchKernelGGL((laswp_moves_kernel<T, CW, VW>), dim3((ncols / VW + CW - 1) / CW), dim3(256), 0, h->stream,
-                           ncols / VW, A, lda / VW, row0, (const int2 *)h->moves, hole_at / VW, hole_w / VW);
+                           ncols / VW, A, lda / VW, row0, moves, hole_at / VW, hole_w / VW);
         LSX_HIP(hipGetLastError());
         return LSX_OK;
     }
     constexpr int CW = 32;
     hipLaunchKernelGGL((laswp_moves_kernel<T, CW, 1>), dim3((ncols + CW - 1) / CW), dim3(256), 0, h->stream,
-                       ncols, A, lda, row0, (const int2 *)h->moves, hole_at, hole_w);
+                       ncols, A, lda, row0, moves, hole_at, hole_w);
     LSX_HIP(hipGetLastError());
     return LSX_OK;
 }
@@ -283,17 +283,17 @@ __global__ __launch_bounds__(64) void wait_count_kernel(const int *word, int tar
         if (info) atomicMin(info, -0x40000000);
     }
 }
-int launch_wait_count(lsx_handle_t h, const int *word, int target) {
+int launch_wait_count(lsx_handle_t h, const int *word, int target, int *info) {
     hipLaunchKernelGGL(wait_count_kernel, dim3(1), dim3(64), 0, h->stream, word, target, h->chain_wait_limit, h->dev_status,
-                       h->chain_info);
+                       info);
     LSX_HIP(hipGetLastError());
     return LSX_OK;
 }
 
 // the same for a plain column range
 template <typename T>
-int launch_laswp_moves(lsx_handle_t h, int ncols, T *A, int lda, int row0) {
-    return launch_laswp_moves_around<T>(h, ncols, A, lda, row0, 0, 0);
+int launch_laswp_moves(lsx_handle_t h, const int2 *moves, int ncols, T *A, int lda, int row0) {
+    return launch_laswp_moves_around<T>(h, moves, ncols, A, lda, row0, 0, 0);
 }
 
 // ------------------------------------------------------------------ triangular 64-block inverse
@@ -495,16 +495,16 @@ __global__ __launch_bounds__(256) void chain_head_kernel(int ntri, int jb, const
 // trtri(lower) of the jb x jb triangle at Tm  +  the gather-list interchanges on `ncols` columns at A.
 // Returns 1 when the shapes do not allow the 16-byte path (the caller then issues the two launches).
 template <typename T>
-int launch_chain_head(lsx_handle_t h, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A, int lda, int row0,
-                      const int *wait_word, int wait_target) {
+int launch_chain_head(lsx_handle_t h, const int2 *moves, int *info, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A,
+                      int lda, int row0, const int *wait_word, int wait_target) {
     constexpr int VW = 16 / (int)sizeof(T);
     constexpr int CW = 32 / VW;
-    if (!h->moves_valid || jb <= 0 || ncols <= 0 || ((size_t)A % 16) || lda % VW || ncols % VW) return 1;
+    if (!moves || jb <= 0 || ncols <= 0 || ((size_t)A % 16) || lda % VW || ncols % VW) return 1;
     const int ntri = (jb + TB - 1) / TB;
     ProfScope ps(h, LSX_PROF_TRSM);
     hipLaunchKernelGGL((chain_head_kernel<T, CW, VW>), dim3(ntri + (ncols / VW + CW - 1) / CW), dim3(256), 0, h->stream,
-                       ntri, jb, Tm, ldt, Tinv, ncols / VW, A, lda / VW, row0, (const int2 *)h->moves, wait_word, wait_target,
-                       h->chain_wait_limit, h->dev_status, h->chain_info);
+                       ntri, jb, Tm, ldt, Tinv, ncols / VW, A, lda / VW, row0, moves, wait_word, wait_target,
+                       h->chain_wait_limit, h->dev_status, info);
     LSX_HIP(hipGetLastError());
     return LSX_OK;
 }
@@ -830,18 +830,18 @@ __global__ __launch_bounds__(256) void chain_fused_kernel(int jb, const T *__res
 
 // Returns 1 when the shapes do not allow it (the caller issues chain head and block solve separately).
 template <typename T>
-int launch_chain_fused(lsx_handle_t h, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A, int lda, int row0,
-                       const int *wait_word, int wait_target, int *ready) {
+int launch_chain_fused(lsx_handle_t h, const int2 *moves, int *info, int jb, const T *Tm, int ldt, T *Tinv, int ncols, T *A,
+                       int lda, int row0, const int *wait_word, int wait_target, int *ready) {
     constexpr int VW = 16 / (int)sizeof(T);
     constexpr int CW = 32 / VW;
-    if (!h->chain_fused || !h->moves_valid || jb != 128 || ncols != 128 || ((size_t)A % 16) || lda % VW ||
+    if (!h->chain_fused || !moves || jb != 128 || ncols != 128 || ((size_t)A % 16) || lda % VW ||
         ((size_t)Tm % 16) || ((size_t)Tinv % 16) || ldt % 2 || !ready)
         return 1;
     const size_t shm = ((size_t)128 * (CWT + 2) + 3 * TB * TLD) * sizeof(T);
     ProfScope ps(h, LSX_PROF_TRSM, (double)jb * jb * ncols);
     LSX_HIP(hipFuncSetAttribute((const void *)chain_fused_kernel<T, CW, VW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     hipLaunchKernelGGL((chain_fused_kernel<T, CW, VW>), dim3(2 + 128 / 32), dim3(256), shm, h->stream, jb, Tm, ldt, Tinv, A, lda,
-                       row0, (const int2 *)h->moves, wait_word, wait_target, h->chain_wait_limit, h->dev_status, h->chain_info,
+                       row0, moves, wait_word, wait_target, h->chain_wait_limit, h->dev_status, info,
                        ready);
     LSX_HIP(hipGetLastError());
     return LSX_OK;
@@ -1257,11 +1257,11 @@ int launch_refine_apply(lsx_handle_t h, int n, int nrhs, int init, const float *
 #define INST(T)                                                                                   \
     template int launch_fill<T>(lsx_handle_t, int, uint64_t, int, int, T *, int, int, int);       \
     template int launch_laswp<T>(lsx_handle_t, int, T *, int, int, int, const int32_t *);         \
-    template int launch_laswp_moves<T>(lsx_handle_t, int, T *, int, int);                         \
+    template int launch_laswp_moves<T>(lsx_handle_t, const int2 *, int, T *, int, int);           \
     template int launch_laswp_left_all<T>(lsx_handle_t, T *, int, int, int, int, const void *);   \
-    template int launch_laswp_moves_around<T>(lsx_handle_t, int, T *, int, int, int, int);        \
-    template int launch_chain_head<T>(lsx_handle_t, int, const T *, int, T *, int, T *, int, int, const int *, int);  \
-    template int launch_chain_fused<T>(lsx_handle_t, int, const T *, int, T *, int, T *, int, int, const int *, int, int *); \
+    template int launch_laswp_moves_around<T>(lsx_handle_t, const int2 *, int, T *, int, int, int, int); \
+    template int launch_chain_head<T>(lsx_handle_t, const int2 *, int *, int, const T *, int, T *, int, T *, int, int, const int *, int);  \
+    template int launch_chain_fused<T>(lsx_handle_t, const int2 *, int *, int, const T *, int, T *, int, T *, int, int, const int *, int, int *); \
     template int launch_trtri<T>(lsx_handle_t, int, int, const T *, int, T *);                    \
     template int launch_trtri_both<T>(lsx_handle_t, int, const T *, int, T *, T *);               \
     template int launch_trsm_block<T>(lsx_handle_t, int, int, int, const T *, int, const T *, T *, \

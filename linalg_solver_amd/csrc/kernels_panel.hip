@@ -154,30 +154,30 @@ int panel_percolumn(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
 
 template <typename T>
 int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv,
-                    int *d_info);
+                    int *d_info, PanelArgs &pa);
 
 template <typename T>
-int panel_xcd(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info);
+int panel_xcd(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, PanelArgs &pa);
 
 template <typename T>
 int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t *d_ipiv,
-                 int *d_info) {
+                 int *d_info, PanelArgs &pa) {
+    pa.listed = false;
     if (m <= 0 || jb <= 0) return LSX_OK;
-    h->moves_valid = false;
     ProfScope ps(h, LSX_PROF_PANEL, 0, 2.0 * sizeof(T) * m * (double)jb);
     // the panel's first column is global column row0 (square LU: panel starts on the diagonal)
-    if (h->panel_mode == 4) {   // one XCD; taller panels than it holds take the device-scope kernel
-        const int r = panel_xcd<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);   // rows distributed, pivot exchange in the L2
+    if (pa.mode == 4) {   // one XCD; taller panels than it holds take the device-scope kernel
+        const int r = panel_xcd<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info, pa);   // rows distributed, pivot exchange in the L2
         if (r != 1) return r;
     }
-    if (h->panel_mode >= 3) {
-        const int r = panel_pipelined<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);
+    if (pa.mode >= 3) {
+        const int r = panel_pipelined<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info, pa);
         if (r != 1) return r;  // 1 = shape not supported: per-column launches
     }
     return panel_percolumn<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);
 }
 
-template int launch_panel<double>(lsx_handle_t, int, int, double *, int, int, int32_t *, int *);
-template int launch_panel<float>(lsx_handle_t, int, int, float *, int, int, int32_t *, int *);
+template int launch_panel<double>(lsx_handle_t, int, int, double *, int, int, int32_t *, int *, PanelArgs &);
+template int launch_panel<float>(lsx_handle_t, int, int, float *, int, int, int32_t *, int *, PanelArgs &);
 
 }  // namespace lsx

@@ -513,15 +513,15 @@ __global__ __launch_bounds__(NT, NT / 256) void panel_pipe_kernel(int m, int jb,
 
 template <typename T, int RT, int NT, int KS>
 static int panel_pipe_launch(lsx_handle_t h, int G, int m, int jb, T *P, int ldp, int row0, int col0,
-                             int32_t *d_ipiv, int *d_info) {
+                             int32_t *d_ipiv, int *d_info, PanelArgs &pa) {
     // exchange area in scratch: status | headers[2][G] (HDR_STRIDE apart) | granule rows[2][G][128]
     const size_t hdr_bytes = (size_t)2 * G * HDR_STRIDE;
     const size_t need = 256 + hdr_bytes + (size_t)2 * G * PC_COLS * sizeof(XGran);
     const size_t dbg_off = (need + 255) & ~(size_t)255;
     const size_t total = dbg_off + (h->panel_debug ? (size_t)G * 64 : 0);
-    const bool driver_clears = h->panel_area_stride > 0 && !h->panel_debug;
-    const size_t base_off = driver_clears ? (size_t)h->panel_area * h->panel_area_stride : 0;
-    if (base_off + total > h->scratch_bytes || (driver_clears && need > h->panel_area_stride)) {
+    const bool driver_clears = pa.area_bytes > 0 && !h->panel_debug;
+    const size_t base_off = driver_clears ? pa.area_off : 0;
+    if (base_off + total > h->scratch_bytes || (driver_clears && need > pa.area_bytes)) {
         set_error("panel_pipe: scratch too small (%zu + %zu > %zu)", base_off, total, h->scratch_bytes);
         return LSX_ERR_INTERNAL;
     }
@@ -535,28 +535,28 @@ static int panel_pipe_launch(lsx_handle_t h, int G, int m, int jb, T *P, int ldp
     unsigned long long *dbg = h->panel_debug ? (unsigned long long *)(base + dbg_off) : nullptr;
     if (h->panel_debug) {
         hipLaunchKernelGGL((panel_pipe_kernel<T, RT, NT, KS, true>), dim3(G), dim3(NT), 0, h->stream, m, jb, P, ldp,
-                           row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)h->moves);
+                           row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)pa.list);
     } else {
         hipLaunchKernelGGL((panel_pipe_kernel<T, RT, NT, KS, false>), dim3(G), dim3(NT), 0, h->stream, m, jb, P, ldp,
-                           row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)h->moves);
+                           row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)pa.list);
     }
     LSX_HIP(hipGetLastError());
-    h->moves_valid = true;
+    pa.listed = true;
     return LSX_OK;
 }
 
 // Returns 1 when the shape is outside what the kernel supports (caller falls back).
 template <typename T>
 int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv,
-                    int *d_info) {
+                    int *d_info, PanelArgs &pa) {
     if (jb > PC_COLS) return 1;
     // workgroup shape: NT threads (16 thread columns x NT/16 thread rows), RT rows per thread.  One
     // wave per SIMD (NT = 256) keeps the critical wave's issue slots to itself; taller panels take
     // 512 threads so that every workgroup is still resident at once.
-    int nt = h->panel_nt, rt = h->panel_rt;
+    int nt = pa.nt, rt = pa.rt;
     auto rows = [](int nt_, int rt_) { return nt_ / 16 * rt_; };
     auto wgs = [&](int nt_, int rt_) { return (m + rows(nt_, rt_) - 1) / rows(nt_, rt_); };
-    if (h->panel_nt == 0) {  // measured: one header per polling lane (<= 64 workgroups) wins
+    if (pa.nt == 0) {  // measured: one header per polling lane (<= 64 workgroups) wins
         nt = 256, rt = 4;
         if (wgs(nt, rt) > 64) nt = 512;
     }
@@ -567,7 +567,7 @@ int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
     const int ks = G <= 64 ? 1 : (G <= 128 ? 2 : 4);
 #define LSX_PP(RT_, NT_, KS_)                     \
     if (rt == RT_ && nt == NT_ && ks == KS_)      \
-        return panel_pipe_launch<T, RT_, NT_, KS_>(h, G, m, jb, P, ldp, row0, col0, d_ipiv, d_info);
+        return panel_pipe_launch<T, RT_, NT_, KS_>(h, G, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
     LSX_PP(4, 256, 1) LSX_PP(4, 256, 2) LSX_PP(4, 256, 4)
     LSX_PP(4, 512, 1) LSX_PP(4, 512, 2) LSX_PP(4, 512, 4)
     LSX_PP(8, 512, 1) LSX_PP(8, 512, 2) LSX_PP(8, 512, 4)
@@ -575,19 +575,19 @@ int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
     return 1;
 }
 
-size_t panel_pipe_area_bytes(lsx_handle_t h, int m) {
-    if (h->panel_mode < 3 || h->panel_debug || h->nb > PC_COLS) return 0;
-    if (h->panel_nt != 0 && h->panel_nt != 256 && h->panel_nt != 512) return 0;
-    if (!(h->panel_rt == 4 || (h->panel_rt == 8 && h->panel_nt == 512))) return 0;
+size_t panel_pipe_area_bytes(lsx_handle_t h, int mode, int nt, int rt, int m) {
+    if (mode < 3 || h->panel_debug || h->nb > PC_COLS) return 0;
+    if (nt != 0 && nt != 256 && nt != 512) return 0;
+    if (!(rt == 4 || (rt == 8 && nt == 512))) return 0;
     if (m > 256 * (h->num_cu < 256 ? h->num_cu : 256)) return 0;
     int G = (m + 127) / 128;        // 128-row slices above 4096 rows, never more than 64 slices below
     if (G < 64) G = 64;
-    if (h->panel_nt == 256 && h->panel_rt == 4) G = (m + 63) / 64;
+    if (nt == 256 && rt == 4) G = (m + 63) / 64;
     if (G > 256) G = 256;
     return ((size_t)256 + (size_t)G * (2 * HDR_STRIDE + 2 * PC_COLS * sizeof(XGran)) + 255) & ~(size_t)255;
 }
 
-template int panel_pipelined<double>(lsx_handle_t, int, int, double *, int, int, int, int32_t *, int *);
-template int panel_pipelined<float>(lsx_handle_t, int, int, float *, int, int, int, int32_t *, int *);
+template int panel_pipelined<double>(lsx_handle_t, int, int, double *, int, int, int, int32_t *, int *, PanelArgs &);
+template int panel_pipelined<float>(lsx_handle_t, int, int, float *, int, int, int, int32_t *, int *, PanelArgs &);
 
 }  // namespace lsx

@@ -689,9 +689,9 @@ __global__ __launch_bounds__(PX_NT, PX_NT / 256) void panel_x_kernel(int m, int 
 }
 
 // bytes of one exchange area for panels of up to m rows (0: not served)
-size_t panel_x_area_bytes(lsx_handle_t h, int m, size_t elem) {
+size_t panel_x_area_bytes(lsx_handle_t h, int mode, int m, size_t elem) {
     const int rt = elem == 8 ? 4 : 8;
-    if (h->panel_mode != 4 || h->panel_debug || h->nb > PC_COLS) return 0;
+    if (mode != 4 || h->panel_debug || h->nb > PC_COLS) return 0;
     if (m > 32 * 64 * rt) m = 32 * 64 * rt;   // taller panels take the device-scope kernel (its own area size)
     return ((size_t)256 + (size_t)32 * (2 * PX_REC + 4 * PC_COLS * sizeof(XGran)) + 255) & ~(size_t)255;
 }
@@ -699,7 +699,7 @@ size_t panel_x_area_bytes(lsx_handle_t h, int m, size_t elem) {
 // Returns 1 when the shape is outside what the kernel serves (caller falls back to the device-scope kernel).
 template <typename T, int RT>
 static int panel_xcd_rt(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info,
-                        const double first_tol = -1.0) {
+                        PanelArgs &pa, const double first_tol = -1.0) {
     if (jb > PC_COLS) return 1;
     const int G = (m + 64 * RT - 1) / (64 * RT);
     if (G > 32 || 8 * G > 8 * h->num_cu) return 1;
@@ -708,9 +708,9 @@ static int panel_xcd_rt(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, 
     const size_t need = 256 + rec_bytes + (size_t)4 * G * PC_COLS * sizeof(XGran);
     const size_t dbg_off = (need + 255) & ~(size_t)255;
     const size_t total = dbg_off + (h->panel_debug ? (size_t)G * 128 : 0);
-    const bool driver_clears = h->panel_area_stride > 0 && !h->panel_debug;
-    const size_t base_off = driver_clears ? (size_t)h->panel_area * h->panel_area_stride : 0;
-    if (base_off + total > h->scratch_bytes || (driver_clears && need > h->panel_area_stride)) {
+    const bool driver_clears = pa.area_bytes > 0 && !h->panel_debug;
+    const size_t base_off = driver_clears ? pa.area_off : 0;
+    if (base_off + total > h->scratch_bytes || (driver_clears && need > pa.area_bytes)) {
         set_error("panel_xcd: scratch too small (%zu + %zu > %zu)", base_off, total, h->scratch_bytes);
         return LSX_ERR_INTERNAL;
     }
@@ -724,17 +724,17 @@ static int panel_xcd_rt(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, 
     if (first_tol >= 0.0) {   // the reference's first-non-zero rule (fp64, up to 8192 rows: callers check)
         if constexpr (sizeof(T) == 8 && RT <= 4)
             hipLaunchKernelGGL((panel_x_kernel<T, RT, false, true>), dim3(8 * G), dim3(PX_NT), 0, h->stream, m, jb, P, ldp, row0,
-                               col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)h->moves, xcc, h->panel_xcc_word, h->panel_spin_limit, first_tol);
+                               col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)pa.list, xcc, pa.xcc_word, h->panel_spin_limit, first_tol);
         else
             return 1;
     } else if (h->panel_debug)
         hipLaunchKernelGGL((panel_x_kernel<T, RT, true>), dim3(8 * G), dim3(PX_NT), 0, h->stream, m, jb, P, ldp, row0,
-                           col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)h->moves, xcc, h->panel_xcc_word, h->panel_spin_limit, -1.0);
+                           col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)pa.list, xcc, pa.xcc_word, h->panel_spin_limit, -1.0);
     else
         hipLaunchKernelGGL((panel_x_kernel<T, RT, false>), dim3(8 * G), dim3(PX_NT), 0, h->stream, m, jb, P, ldp, row0,
-                           col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)h->moves, xcc, h->panel_xcc_word, h->panel_spin_limit, -1.0);
+                           col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)pa.list, xcc, pa.xcc_word, h->panel_spin_limit, -1.0);
     LSX_HIP(hipGetLastError());
-    h->moves_valid = true;
+    pa.listed = true;
     return LSX_OK;
 }
 
@@ -744,25 +744,26 @@ static int panel_xcd_rt(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, 
 // all-gather of more workgroups: 4 -> 2 -> 1 took 8192^2 fp64 from 17.1 to 16.6 to 16.3 ms and 4096^2 from 6.95 to
 // 6.36 to 6.23 ms, 8 -> 4 took 8192^2 fp32 from 16.9 to 14.5 ms.  Same arithmetic per element, same pivots.
 template <typename T>
-int panel_xcd(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info) {
-    if (m <= 32 * 64 * 1) return panel_xcd_rt<T, 1>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info);
-    if (m <= 32 * 64 * 2) return panel_xcd_rt<T, 2>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info);
-    if (sizeof(T) == 4 && m > 32 * 64 * 4) return panel_xcd_rt<T, sizeof(T) == 4 ? 8 : 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info);
-    return panel_xcd_rt<T, 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info);
+int panel_xcd(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, PanelArgs &pa) {
+    if (m <= 32 * 64 * 1) return panel_xcd_rt<T, 1>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
+    if (m <= 32 * 64 * 2) return panel_xcd_rt<T, 2>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
+    if (sizeof(T) == 4 && m > 32 * 64 * 4) return panel_xcd_rt<T, sizeof(T) == 4 ? 8 : 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
+    return panel_xcd_rt<T, 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
 }
 
 // The same panel under the reference's pivot rule (first row in the current order with |a| > tol); fp64, at most 8192
 // rows.  Returns 1 for anything else.
 int panel_xcd_first(lsx_handle_t h, int m, int jb, double *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info,
-                    double tol) {
+                    double tol, PanelArgs &pa) {
+    pa.listed = false;
     if (tol < 0.0 || m > 32 * 64 * 4) return 1;
-    if (m <= 32 * 64 * 1) return panel_xcd_rt<double, 1>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, tol);
-    if (m <= 32 * 64 * 2) return panel_xcd_rt<double, 2>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, tol);
-    return panel_xcd_rt<double, 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, tol);
+    if (m <= 32 * 64 * 1) return panel_xcd_rt<double, 1>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa, tol);
+    if (m <= 32 * 64 * 2) return panel_xcd_rt<double, 2>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa, tol);
+    return panel_xcd_rt<double, 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa, tol);
 }
 
-template int panel_xcd<double>(lsx_handle_t, int, int, double *, int, int, int, int32_t *, int *);
-template int panel_xcd<float>(lsx_handle_t, int, int, float *, int, int, int, int32_t *, int *);
+template int panel_xcd<double>(lsx_handle_t, int, int, double *, int, int, int, int32_t *, int *, PanelArgs &);
+template int panel_xcd<float>(lsx_handle_t, int, int, float *, int, int, int, int32_t *, int *, PanelArgs &);
 
 }  // namespace lsx
 

@@ -302,8 +302,8 @@ int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *
     }
     T *L = (T *)h->ws3;
     T *Tinv = (T *)((char *)h->ws3 + lbytes);
-    struct MfmaOnly { lsx_handle_t h; bool keep; ~MfmaOnly() { h->gemm_mfma_only = keep; } } mo{h, h->gemm_mfma_only};
-    h->gemm_mfma_only = true;
+    GemmPlan mfma;   // as in the LU drivers: narrow updates on the MFMA kernel too
+    mfma.mfma_only = true;
     hipStream_t s = h->stream;
     LSX_HIP(hipMemsetAsync(h->scratch, 0, 2048, s));
     if (tol < 0) hipLaunchKernelGGL(rrb_amax_kernel<T>, dim3(256), dim3(256), 0, s, m, bar, W, ldw, amax);
@@ -340,7 +340,7 @@ int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *
                 LSX_TRY(launch_trsm_block<T>(h, 1, q, right, L, RB_W, Tinv, A12, ldw));
                 if (rows_left > q)
                     LSX_TRY(launch_gemm_sub<T>(h, rows_left - q, right, q, L + (size_t)q * RB_W, RB_W, A12, ldw,
-                                               W + (size_t)(r + q) * ldw + c0 + w, ldw));
+                                               W + (size_t)(r + q) * ldw + c0 + w, ldw, mfma));
             }
         }
         hipLaunchKernelGGL(rrb_block_end_kernel, dim3(1), dim3(128), 0, s, st, d_pivots, d_rank);
@@ -364,7 +364,7 @@ int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *
         T *X = W + (size_t)kb * ldw + col0;
         LSX_TRY(launch_trtri<T>(h, 0, jb, Ublk, RB_W, Tinv));
         LSX_TRY(launch_trsm_block<T>(h, 0, jb, ncols, Ublk, RB_W, Tinv, X, ldw));
-        if (kb > 0) LSX_TRY(launch_gemm_sub<T>(h, kb, ncols, jb, L, RB_W, X, ldw, W + col0, ldw));
+        if (kb > 0) LSX_TRY(launch_gemm_sub<T>(h, kb, ncols, jb, L, RB_W, X, ldw, W + col0, ldw, mfma));
     }
     hipLaunchKernelGGL(rrb_finish_kernel<T>, dim3((std::max(bar, rank) + 255) / 256, std::min(m, 65535)), dim3(256), 0, s, m, bar, W, ldw, d_pivots, rank);
     LSX_HIP(hipGetLastError());

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void trsv_step_kernel(int lower, int n, const 
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same solve in ONE launch per direction (option "trsv" = 1, default).  Workgroup w owns rows
+// The same solve in ONE launch per direction (option "trsv" = 1; the default is the third form below).  Workgroup w owns rows
 // [64 w, 64 w + 64) for the whole sweep and keeps their right-hand sides on chip; all workgroups are
 // co-resident (n <= 64 * #CUs).  Per 64-row step k the only cross-CU traffic is x_k: its owner forms
 // it from its finished rows with the 64 x 64 diagonal-block inverse and publishes it as

@@ -48,10 +48,6 @@ struct Guard {
 
 }  // namespace
 
-// per-device building blocks (api.hip / kernels)
-template <typename T>
-int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t *d_ipiv, int *d_info);
-
 static int mg_free(std::vector<Dev> &D, int rc) {
     for (auto &d : D) {
         (void)hipSetDevice(d.dev);
@@ -128,12 +124,8 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
         LSX_HIP(hipEventRecord(x.freed[0], x.comp));
         LSX_HIP(hipEventRecord(x.freed[1], x.comp));
     }
-    struct Modes {   // the look-ahead below shares a device's CUs between a panel and an update: device-scope panel
-        std::vector<Dev> &D; std::vector<int> keep;
-        explicit Modes(std::vector<Dev> &D_) : D(D_) { for (auto &d : D) { keep.push_back(d.h->panel_mode); if (d.h->panel_mode == 4) d.h->panel_mode = 3; } }
-        ~Modes() { for (size_t i = 0; i < D.size(); ++i) D[i].h->panel_mode = keep[i]; }
-    } modes(D);
-
+    GemmPlan mfma;   // same summation order whatever the column split (as in getrf_dev)
+    mfma.mfma_only = true;
     bool cur_list = false;   // the panel being applied came with a gather list (set per step)
     auto shape = [&](int b, int &k, int &jb, int &m) { k = b * nb; jb = std::min(nb, n - k); m = n - k; };
     // row range [r0, r1) of chunk c of a panel of m rows: multiples of 64 rows, chunk 0 holds at least the top jb rows
@@ -145,8 +137,8 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
     };
     auto local_index = [&](const Dev &x, int b) { return (int)(std::lower_bound(x.blocks.begin(), x.blocks.end(), b) - x.blocks.begin()); };
 
-    // owner: factor panel b in place, pack it, start the copies to every peer
-    auto pack_and_send = [&](int b) -> int {
+    // owner: factor panel b in place, pack it, start the copies to every peer; listed = it came with a gather list
+    auto pack_and_send = [&](int b, bool &listed) -> int {
         int k, jb, m;
         shape(b, k, jb, m);
         const int o = b % P, p = b & 1;
@@ -158,9 +150,12 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
         for (int e = 0; e < P; ++e)
             if (e != o && D[e].landed[((size_t)o * 2 + p) * MG_CHUNKS + MG_CHUNKS - 1] && b >= 2 && (b - 2) % P == o)
                 LSX_HIP(hipStreamWaitEvent(x.comp, D[e].landed[((size_t)o * 2 + p) * MG_CHUNKS + MG_CHUNKS - 1], 0));
-        LSX_TRY(launch_panel<double>(x.h, m, jb, Pn, lda[o], k, d_ipiv[o] + k, d_info[o]));
+        PanelArgs pa(x.h, x.h->moves_buf[0]);
+        if (pa.mode == 4) pa.mode = 3;   // the look-ahead below shares a device's CUs between a panel and an update: device-scope panel
+        LSX_TRY(launch_panel<double>(x.h, m, jb, Pn, lda[o], k, d_ipiv[o] + k, d_info[o], pa));
+        listed = pa.listed;
         char *buf = x.buf[p];
-        if (x.h->moves_valid) LSX_HIP(hipMemcpyAsync(buf, x.h->moves, 2048, hipMemcpyDeviceToDevice, x.comp));
+        if (listed) LSX_HIP(hipMemcpyAsync(buf, pa.list, 2048, hipMemcpyDeviceToDevice, x.comp));
         else LSX_HIP(hipMemsetAsync(buf, 0xff, 2048, x.comp));   // all (-1, -1): no gather list, peers use the pivots
         LSX_HIP(hipMemcpyAsync(buf + 2048, d_info[o], sizeof(int), hipMemcpyDeviceToDevice, x.comp));
         LSX_HIP(hipMemcpyAsync(buf + 2304, d_ipiv[o] + k, sizeof(int32_t) * jb, hipMemcpyDeviceToDevice, x.comp));
@@ -201,19 +196,8 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
         auto landed = [&](int c) { return D[d].landed[((size_t)o * 2 + p) * MG_CHUNKS + c]; };
         if (d != o) LSX_HIP(hipStreamWaitEvent(x.comp, landed(0), 0));
         // interchanges: the owner's gather list when there is one
-        void *keep_moves = x.h->moves;
-        const bool keep_valid = x.h->moves_valid;
-        int rc = LSX_OK;
-        if (cur_list) {
-            x.h->moves = (void *)buf;
-            x.h->moves_valid = true;
-            rc = launch_laswp_moves<double>(x.h, c1 - c0, Ac, lda[d], k);
-        } else {
-            rc = launch_laswp<double>(x.h, c1 - c0, Ac, lda[d], k, jb, (const int32_t *)(buf + 2304));
-        }
-        x.h->moves = keep_moves;
-        x.h->moves_valid = keep_valid;
-        LSX_TRY(rc);
+        if (cur_list) LSX_TRY(launch_laswp_moves<double>(x.h, (const int2 *)buf, c1 - c0, Ac, lda[d], k));
+        else LSX_TRY(launch_laswp<double>(x.h, c1 - c0, Ac, lda[d], k, jb, (const int32_t *)(buf + 2304)));
         double *U12 = dA[d] + (size_t)k * lda[d] + c0;
         const size_t tinv = (size_t)((jb + 63) / 64) * 4096 * sizeof(double);
         if (x.h->ws2_bytes < tinv) { set_error("getrf_mg: block-inverse workspace"); return LSX_ERR_INTERNAL; }
@@ -223,7 +207,7 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
             if (d == o || !chunked) {
                 if (d != o) LSX_HIP(hipStreamWaitEvent(x.comp, landed(MG_CHUNKS - 1), 0));
                 LSX_TRY(launch_gemm_sub<double>(x.h, m - jb, c1 - c0, jb, panel + (size_t)jb * jb, jb, U12, lda[d],
-                                                dA[d] + (size_t)(k + jb) * lda[d] + c0, lda[d]));
+                                                dA[d] + (size_t)(k + jb) * lda[d] + c0, lda[d], mfma));
             } else {
                 for (int c = 0; c < MG_CHUNKS; ++c) {   // each row range as its chunk lands
                     int r0, r1;
@@ -232,7 +216,7 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
                     if (r1 <= r0) continue;
                     LSX_HIP(hipStreamWaitEvent(x.comp, landed(c), 0));
                     LSX_TRY(launch_gemm_sub<double>(x.h, r1 - r0, c1 - c0, jb, panel + (size_t)r0 * jb, jb, U12, lda[d],
-                                                    dA[d] + (size_t)(k + r0) * lda[d] + c0, lda[d]));
+                                                    dA[d] + (size_t)(k + r0) * lda[d] + c0, lda[d], mfma));
                 }
             }
         }
@@ -246,19 +230,8 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
         Dev &x = D[d];
         LSX_HIP(hipSetDevice(x.dev));
         const char *buf = x.buf[p];
-        void *keep_moves = x.h->moves;
-        const bool keep_valid = x.h->moves_valid;
-        int rc;
-        if (cur_list) {
-            x.h->moves = (void *)buf;
-            x.h->moves_valid = true;
-            rc = launch_laswp_moves<double>(x.h, ncols, dA[d], lda[d], k);
-        } else {
-            rc = launch_laswp<double>(x.h, ncols, dA[d], lda[d], k, jb, (const int32_t *)(buf + 2304));
-        }
-        x.h->moves = keep_moves;
-        x.h->moves_valid = keep_valid;
-        return rc;
+        if (cur_list) return launch_laswp_moves<double>(x.h, (const int2 *)buf, ncols, dA[d], lda[d], k);
+        return launch_laswp<double>(x.h, ncols, dA[d], lda[d], k, jb, (const int32_t *)(buf + 2304));
     };
     // non-owner: pivots and info of panel b out of its buffer
     auto unpack = [&](int d, int b) -> int {
@@ -276,13 +249,10 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
     for (int d = 0; d < P; ++d) {
         LSX_HIP(hipSetDevice(D[d].dev));
         if (ensure_getrf_workspace(hs[d], n, sizeof(double)) != LSX_OK) { set_error("getrf_mg: workspace allocation failed"); return LSX_ERR_ALLOC; }
-        hs[d]->gemm_mfma_only = true;   // same summation order whatever the column split (as in getrf_dev)
     }
-    struct MfmaOnly { std::vector<Dev> &D; ~MfmaOnly() { for (auto &d : D) d.h->gemm_mfma_only = false; } } mfma_only{D};
 
     bool has_list[2] = {false, false};   // whether the panel in buffer p came with a gather list
-    int rc = pack_and_send(0);
-    has_list[0] = D[0].h->moves_valid;
+    int rc = pack_and_send(0, has_list[0]);
     for (int d = 1; d < P && rc == LSX_OK; ++d) {
         LSX_HIP(hipSetDevice(D[d].dev));
         LSX_HIP(hipStreamWaitEvent(D[d].comp, D[d].landed[((size_t)0 * 2 + 0) * MG_CHUNKS + 0], 0));
@@ -303,8 +273,7 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
             const int li = right_of(x, b);
             const int w = std::min(nb, n - (b + 1) * nb);
             rc = apply_panel(own_next, b, x.offset[li], x.offset[li] + w, false);
-            if (rc == LSX_OK) rc = pack_and_send(b + 1);
-            has_list[(b + 1) & 1] = x.h->moves_valid;
+            if (rc == LSX_OK) rc = pack_and_send(b + 1, has_list[(b + 1) & 1]);
             done_cols = x.offset[li] + w;
         }
         for (int d = 0; d < P && rc == LSX_OK; ++d) {

@@ -1384,3 +1384,63 @@ def test_blocked_rref_8192_rank_4096(dev):
     # the reduced right block is the planted combination: R[:rk, rk:] = C / 64
     assert float((R[:rk, rk:] - C / 64.0).abs().max()) < 1e-7
     assert float((B @ R[:rk, :] - A).abs().max() / A.abs().max()) < 1e-9
+
+
+def test_a_calls_bits_do_not_depend_on_what_the_handle_ran_before(dev):
+    """A call's bits do not depend on what the handle ran before.  One handle runs, in order, every driver that gives
+    its launches scheduling of its own -- the inverse of a 4096^2 factorisation (the smallest order whose backward
+    sweep takes the pair form with the rotated k index), a 641^2 factorisation through shared-CU phase, hand-over and
+    XCD driver with a ragged last panel (narrow updates on the MFMA kernel, work queue, counted columns), the blocked
+    row reduction of a 600 x 700 matrix -- and then a panel with its gather list, a 9-column update (the shape whose
+    kernel, and with it the summation order, such scheduling would change) and a 256-column one.  The last three give
+    the bits they give on handles that have run nothing else."""
+    import torch
+
+    from linalg_solver_amd import _native as N
+    from linalg_solver_amd import gen
+    from linalg_solver_amd.device import DeviceSolver
+
+    def filled(m, n, seed):
+        return dev.fill_(torch.empty(m, n, dtype=torch.float64, device="cuda"), gen.U11, seed)
+
+    def panel(d, P0):
+        P = P0.clone()
+        ipiv = torch.zeros(P.shape[1], dtype=torch.int32, device="cuda")
+        info = torch.zeros(1, dtype=torch.int32, device="cuda")
+        d.panel_(P, 0, ipiv, info)
+        mv = torch.zeros(512, dtype=torch.int32, device="cuda")
+        listed = d.panel_moves_(mv)
+        return P, ipiv, info, mv, listed
+
+    def update(d, C0, A, B):
+        return d.gemm_sub_(C0.clone(), A, B)
+
+    P0 = filled(384, 128, 5)
+    narrow = (filled(200, 9, 6), filled(200, 128, 7), filled(128, 9, 8))
+    wide = (filled(256, 256, 9), filled(256, 128, 10), filled(128, 256, 11))
+    h = dev.h
+    try:
+        A = filled(4096, 4096, 1)
+        ipiv, info = dev.getrf_(A)
+        dev.getri(A, ipiv)
+        h.set_option("lookahead_min", 128)
+        h.set_option("panel", 4)
+        h.set_option("xrows_limit", 256)
+        ipiv2, info2 = dev.getrf_(filled(641, 641, 2))
+        dev.rref_(filled(600, 700, 3), pivot_rule=N.PIVOT_MAX)
+        used = (panel(dev, P0), update(dev, *narrow), update(dev, *wide))
+        torch.cuda.synchronize()
+    finally:
+        h.set_option("lookahead_min", 0)
+        h.set_option("panel", DEFAULT_PANEL)
+        h.set_option("xrows_limit", 0)
+    assert int(info.item()) == 0 and int(info2.item()) == 0
+    fresh_narrow = update(DeviceSolver(), *narrow)
+    fresh_wide = update(DeviceSolver(), *wide)
+    fresh_panel = panel(DeviceSolver(), P0)
+    torch.cuda.synchronize()
+    assert torch.equal(used[1], fresh_narrow)
+    assert torch.equal(used[2], fresh_wide)
+    assert used[0][4] and fresh_panel[4]
+    for a, b in zip(used[0][:4], fresh_panel[:4]):
+        assert torch.equal(a, b)

@@ -11,7 +11,7 @@ import torch
 from linalg_solver_amd import gen
 from linalg_solver_amd.device import DeviceSolver
 
-NAMES = {1: "panel_x", 2: "chain_head", 3: "trsm_block2", 4: "gemm_sub", 6: "gemm_queue", 7: "gate", 8: "laswp_moves", 9: "laswp_left_all"}
+NAMES = {1: "panel_x", 2: "chain_head", 3: "trsm_block2", 4: "gemm_sub", 6: "gemm_sub_queue", 7: "gate", 8: "laswp_moves", 9: "laswp_left_all"}
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 s0 = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 ns = int(sys.argv[3]) if len(sys.argv) > 3 else 2
