@@ -234,6 +234,54 @@ int lsx_gecon_f32_dev(lsx_handle_t h, int norm, int n, const float *dLU, int lda
 int lsx_rcond_f64(lsx_handle_t h, int norm, int n, const double *A, int lda, double *rcond, int *info);
 int lsx_rcond_f32(lsx_handle_t h, int norm, int n, const float *A, int lda, double *rcond, int *info);
 
+/* ---- refined solves with forward and backward error bounds (LAPACK's gerfs) ---- */
+/* trans: 0 = A X = B, 1 = A^T X = B.  A is the UNFACTORED matrix, LU / ipiv its factors from lsx_getrf_*.
+ * X holds a solution on entry (from lsx_getrs_* / lsx_getrs_t_*) and the refined one on return; ferr[nrhs] and
+ * berr[nrhs] are host doubles in all forms (the host drives the iteration and reads one small record per step: all
+ * forms synchronise the handle's stream).  No equilibration, no scaling: dgerfs.f step for step.
+ *   berr[j] = max_i |r_i| / w_i with r = b - op(A) x and w = |b| + |op(A)| |x| (guarded as in dgerfs where w_i is
+ *     below safe2 = (n + 1) safmin / u): the componentwise backward error of the returned column.  r and w come
+ *     from ONE pass over A for up to 8 right-hand sides, accumulated in fp64 (fp32 data: converted on load, rounded
+ *     once on store).
+ *   A column is corrected (x += inv(op A) r, from the factors with ipiv) while berr > u, it at least halves and
+ *     fewer than 5 steps were taken; a column that has stopped keeps its x.  The option "gerfs_steps" reads back the
+ *     most steps any column of the last call took.
+ *   ferr[j] bounds max_i |x_ij - xtrue_ij| / max_i |x_ij|: lacn2's estimate (the iteration of lsx_gecon_*) of
+ *     || |inv(op A)| (|r| + (n + 1) u w) ||_inf, divided by max_i |x_ij| (undivided when that is 0).  It costs 4 to 11
+ *     single-right-hand-side solves PER COLUMN, one column after the other (no estimator batched across columns);
+ *     the option "gerfs_solves" reads back their number for the last call.
+ * u is LAPACK's lamch('E'): 2^-53 (fp64), 2^-24 (fp32), so the results compare directly with dgesvx / sgesvx.
+ * Deterministic: every sum has a fixed order, two calls give identical bits, and a column gets the same bits
+ * whichever other columns are passed with it.
+ * Numerical outcomes are values, not statuses: n == 0 or nrhs == 0 give ferr = berr = 0; an exactly zero or NaN U_ii
+ * leaves X untouched with ferr = berr = +inf; a NaN in A, B or X gives berr = ferr = NaN for the columns it reaches
+ * and no refinement step for them.  Arguments are validated as in lsx_getrs_* (lda, ldlu >= n; ldb, ldx >= nrhs;
+ * trans 0 or 1; non-NULL pointers when n * nrhs > 0).  A time-out of the cooperative solve inside is
+ * LSX_ERR_INTERNAL, never a bound. */
+int lsx_gerfs_f64(lsx_handle_t h, int trans, int n, int nrhs, const double *A, int lda, const double *LU, int ldlu,
+                  const int32_t *ipiv, const double *B, int ldb, double *X, int ldx, double *ferr, double *berr);
+int lsx_gerfs_f32(lsx_handle_t h, int trans, int n, int nrhs, const float *A, int lda, const float *LU, int ldlu,
+                  const int32_t *ipiv, const float *B, int ldb, float *X, int ldx, double *ferr, double *berr);
+/* The same on device pointers for A, LU, ipiv, B and X; ferr / berr stay host arrays. */
+int lsx_gerfs_f64_dev(lsx_handle_t h, int trans, int n, int nrhs, const double *dA, int lda, const double *dLU, int ldlu,
+                      const int32_t *d_ipiv, const double *dB, int ldb, double *dX, int ldx, double *ferr, double *berr);
+int lsx_gerfs_f32_dev(lsx_handle_t h, int trans, int n, int nrhs, const float *dA, int lda, const float *dLU, int ldlu,
+                      const int32_t *d_ipiv, const float *dB, int ldb, float *dX, int ldx, double *ferr, double *berr);
+/* One call for a host system: factor, solve, refine, bound.  A and B are not modified, X receives the solution;
+ * *info as lsx_getrf_* (> 0: X is not written, ferr = berr = +inf). */
+int lsx_gesvr_f64(lsx_handle_t h, int trans, int n, int nrhs, const double *A, int lda, const double *B, int ldb,
+                  double *X, int ldx, double *ferr, double *berr, int *info);
+int lsx_gesvr_f32(lsx_handle_t h, int trans, int n, int nrhs, const float *A, int lda, const float *B, int ldb,
+                  float *X, int ldx, double *ferr, double *berr, int *info);
+/* Measurement hooks (tools/kbench.py): one residual-and-bound pass for nrhs <= 8 columns, dR / dW (n x nrhs, ldr),
+ * and the fp32-in / fp64-sum residual of lsx_gesv_f32_refined on its own. */
+int lsx_diag_resid_bound_f64_dev(lsx_handle_t h, int trans, int n, int nrhs, const double *dA, int lda, const double *dB,
+                                 int ldb, const double *dX, int ldx, double *dR, double *dW, int ldr);
+int lsx_diag_resid_bound_f32_dev(lsx_handle_t h, int trans, int n, int nrhs, const float *dA, int lda, const float *dB,
+                                 int ldb, const float *dX, int ldx, float *dR, float *dW, int ldr);
+int lsx_diag_resid_mixed_dev(lsx_handle_t h, int n, int nrhs, const float *dA, int lda, const float *dB, int ldb,
+                             const double *dX, int ldx, float *dR, int ldr);
+
 /* ---- device-pointer entry points (asynchronous on the handle's stream) ---- */
 /* d_info: device int (may be NULL).  d_ipiv: device int32[n].
  * *d_info < 0 after the call means the in-kernel pivot exchange timed out (LSX_ERR_INTERNAL

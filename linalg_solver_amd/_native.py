@@ -75,6 +75,15 @@ _SIGS = {
     "lsx_gecon_f32": [_vp, _i, _i, _fp, _i, _ip, C.c_double, _dp],
     "lsx_gecon_f64_dev": [_vp, _i, _i, _vp, _i, _vp, C.c_double, _dp],
     "lsx_gecon_f32_dev": [_vp, _i, _i, _vp, _i, _vp, C.c_double, _dp],
+    "lsx_gerfs_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _ip, _dp, _i, _dp, _i, _dp, _dp],
+    "lsx_gerfs_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _i, _ip, _fp, _i, _fp, _i, _dp, _dp],
+    "lsx_gerfs_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _dp, _dp],
+    "lsx_gerfs_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _dp, _dp],
+    "lsx_gesvr_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, C.POINTER(_i)],
+    "lsx_gesvr_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, _dp, _dp, C.POINTER(_i)],
+    "lsx_diag_resid_bound_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_diag_resid_bound_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_diag_resid_mixed_dev": [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i],
     "lsx_rcond_f64": [_vp, _i, _i, _dp, _i, _dp, C.POINTER(_i)],
     "lsx_rcond_f32": [_vp, _i, _i, _fp, _i, _dp, C.POINTER(_i)],
     "lsx_panel_f64_dev": [_vp, _i, _i, _vp, _i, _i, _vp, _vp],

@@ -906,9 +906,54 @@ static int lange_dev(lsx_handle_t h, int norm, int m, int n, const T *dA, int ld
     return launch_lange<T>(h, norm, m, n, dA, lda, (double *)h->scratch, d_out);
 }
 
-// LAPACK's gecon: lacn2's iteration (dlacn2.f, the states JUMP = 1..5) around single-right-hand-side solves with
-// L U and its transpose.  The vector steps run on the device (kernels_trsvt.hip); the host reads one record after
-// each and decides.  Synchronises the handle's stream.
+// lacn2's iteration (dlacn2.f, the states JUMP = 1..5) for the 1-norm of an operator M that is only available as
+// apply(1): x <- M x and apply(2): x <- M^T x.  x holds the start vector 1/n on entry and isgn is cleared; the vector
+// steps run on the device (kernels_trsvt.hip), the host reads the record (8 doubles at rec) after each and decides.
+// Shared by the condition estimate (M = inv(A)) and the forward error bound of gerfs (M = diag(W) inv(op A)^T).
+template <typename T, typename Apply>
+static int lacn2_dev(lsx_handle_t h, int n, T *x, signed char *isgn, double *rec, Apply apply, double *est_out) {
+    double r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto read = [&]() -> int {
+        LSX_HIP(hipMemcpyAsync(r, rec, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        return LSX_OK;
+    };
+    double est = 0;
+    LSX_TRY(apply(1));
+    LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec));         // JUMP 1
+    LSX_TRY(read());
+    est = r[0];
+    if (n > 1) {
+        LSX_TRY(apply(2));
+        LSX_TRY(launch_est_amax_unit<T>(h, n, x, -1, rec));       // JUMP 2: j, x <- e_j
+        LSX_TRY(read());
+        int j = (int)r[1];
+        for (int iter = 2;; ++iter) {
+            LSX_TRY(apply(1));
+            LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec)); // JUMP 3
+            LSX_TRY(read());
+            const double estold = est;
+            est = r[0];
+            if (r[4] != 0.0 || est <= estold) break;              // repeated sign vector, or no increase
+            LSX_TRY(apply(2));
+            LSX_TRY(launch_est_amax_unit<T>(h, n, x, j, rec));    // JUMP 4
+            LSX_TRY(read());
+            j = (int)r[1];
+            if (!(r[3] != r[2] && iter < 5)) break;
+        }
+        LSX_TRY(launch_est_fill<T>(h, n, 1, x, (int32_t *)nullptr));   // the alternating vector
+        LSX_TRY(apply(1));
+        LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec));     // JUMP 5
+        LSX_TRY(read());
+        const double temp = 2.0 * (r[0] / (3.0 * n));
+        if (temp > est) est = temp;
+    }
+    *est_out = est;
+    return LSX_OK;
+}
+
+// LAPACK's gecon: lacn2's iteration around single-right-hand-side solves with L U and its transpose.  Synchronises
+// the handle's stream.
 template <typename T>
 static int gecon_dev(lsx_handle_t h, int norm, int n, const T *LU, int lda, const int32_t *d_ipiv, double anorm,
                      double *rcond) {
@@ -930,11 +975,6 @@ static int gecon_dev(lsx_handle_t h, int norm, int n, const T *LU, int lda, cons
     signed char *isgn = (signed char *)((char *)h->ws7 + xb + ib);
     double *rec = (double *)((char *)h->ws7 + xb + ib + sb);     // 8 doubles; rec[5] = min |U_ii|
     double r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto read = [&]() -> int {
-        LSX_HIP(hipMemcpyAsync(r, rec, sizeof(r), hipMemcpyDeviceToHost, h->stream));
-        LSX_HIP(hipStreamSynchronize(h->stream));
-        return LSX_OK;
-    };
     // kase 1: x <- inv(A) x, kase 2: x <- inv(A^T) x; the infinity-norm of A is the 1-norm of A^T
     auto solve = [&](const int kase) -> int {
         h->gecon_solves += 1;
@@ -944,40 +984,186 @@ static int gecon_dev(lsx_handle_t h, int norm, int n, const T *LU, int lda, cons
     LSX_HIP(hipMemsetAsync(isgn, 0, (size_t)n, h->stream));
     LSX_TRY(launch_diag_minabs<T>(h, n, LU, lda, rec + 4));      // writes its second slot: rec[5]
     LSX_TRY(launch_est_fill<T>(h, n, 0, x, ident));
-    LSX_TRY(read());
+    LSX_HIP(hipMemcpyAsync(r, rec, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
     if (!(r[5] > 0)) return LSX_OK;                               // an exactly zero (or NaN) pivot: singular, rcond = 0
     double est = 0;
-    LSX_TRY(solve(1));
-    LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec));         // JUMP 1
-    LSX_TRY(read());
-    est = r[0];
-    if (n > 1) {
-        LSX_TRY(solve(2));
-        LSX_TRY(launch_est_amax_unit<T>(h, n, x, -1, rec));       // JUMP 2: j, x <- e_j
-        LSX_TRY(read());
-        int j = (int)r[1];
-        for (int iter = 2;; ++iter) {
-            LSX_TRY(solve(1));
-            LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec)); // JUMP 3
-            LSX_TRY(read());
-            const double estold = est;
-            est = r[0];
-            if (r[4] != 0.0 || est <= estold) break;              // repeated sign vector, or no increase
-            LSX_TRY(solve(2));
-            LSX_TRY(launch_est_amax_unit<T>(h, n, x, j, rec));    // JUMP 4
-            LSX_TRY(read());
-            j = (int)r[1];
-            if (!(r[3] != r[2] && iter < 5)) break;
-        }
-        LSX_TRY(launch_est_fill<T>(h, n, 1, x, (int32_t *)nullptr));   // the alternating vector
-        LSX_TRY(solve(1));
-        LSX_TRY(launch_est_asum_sign<T>(h, n, x, isgn, rec));     // JUMP 5
-        LSX_TRY(read());
-        const double temp = 2.0 * (r[0] / (3.0 * n));
-        if (temp > est) est = temp;
-    }
+    LSX_TRY((lacn2_dev<T>(h, n, x, isgn, rec, solve, &est)));
     LSX_TRY(check_dev_status(h));                                 // a timed-out solve is a failure, not an estimate
     if (est > 0 && est - est == 0) *rcond = (1.0 / est) / anorm;  // non-finite estimate: 0
+    return LSX_OK;
+}
+
+template <typename T> struct Lamch;
+template <> struct Lamch<double> { static constexpr double u = 0x1p-53, safmin = 0x1p-1022; };
+template <> struct Lamch<float> { static constexpr double u = 0x1p-24, safmin = 0x1p-126; };
+
+// LAPACK's gerfs (dgerfs.f step for step) on device data: refine X with the caller's factors until the componentwise
+// backward error stops improving, then bound the forward error of every column with lacn2 on inv(op A) diag(W).
+// Residual and bound of up to 8 columns come from one pass over A (kernels_refine.hip); a correction is a single
+// right-hand-side solve of the column that asked for it, so a column gets the same bits whatever rides along.
+// The host reads one record per step.  Synchronises the handle's stream.
+template <typename T>
+static int gerfs_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int lda, const T *LU, int ldlu,
+                     const int32_t *d_ipiv, const T *B, int ldb, T *X, int ldx, double *ferr, double *berr,
+                     bool *singular = nullptr) {
+    LSX_ARG((trans == 0 || trans == 1) && n >= 0 && nrhs >= 0 && lda >= n && ldlu >= n && ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(nrhs == 0 || (ferr && berr));
+    if (singular) *singular = false;
+    h->gerfs_steps = 0;
+    h->gerfs_solves = 0;
+    for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = 0.0;
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(A && LU && d_ipiv && B && X);
+    constexpr int G = 8, ITMAX = 5;
+    const double u = Lamch<T>::u, safe1 = (n + 1.0) * Lamch<T>::safmin, safe2 = safe1 / u, nu = (n + 1.0) * u;
+    const size_t gb = pad256(sizeof(T) * (size_t)n * G), vb = pad256(sizeof(T) * (size_t)n), sb = pad256((size_t)n);
+    LSX_TRY(grow(&h->ws8, &h->ws8_bytes, 2 * gb + 2 * vb + sb + 512 + resid_bound_work_bytes(trans, n)));
+    char *w8 = (char *)h->ws8;
+    T *Rg = (T *)w8;                                    // residuals of the group, n x 8
+    T *Wg = (T *)(w8 + gb);                             // bounds of the group
+    T *v = (T *)(w8 + 2 * gb);                          // correction of one column / the estimator's vector
+    T *wt = (T *)(w8 + 2 * gb + vb);                    // the weights W of one column
+    signed char *isgn = (signed char *)(w8 + 2 * gb + 2 * vb);
+    double *rec = (double *)(w8 + 2 * gb + 2 * vb + sb);   // 16 doubles: berr[8], max|x|[8]
+    double *erec = rec + 16;                               // the estimator's record (8 doubles)
+    double *part = rec + 64;                               // partial sums of the transposed residual
+    double r[16];
+    LSX_TRY(launch_diag_minabs<T>(h, n, LU, ldlu, rec));   // writes its second slot: rec[1]
+    LSX_HIP(hipMemcpyAsync(r, rec, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (!(r[1] > 0)) {                                      // an exactly zero (or NaN) pivot: no solution to refine
+        for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = INFINITY;
+        if (singular) *singular = true;
+        return LSX_OK;
+    }
+    // x <- inv(op A) x (transposed: inv(op A)^T x) for one vector, with the caller's interchanges
+    auto solve = [&](const bool transposed) -> int {
+        return (trans != 0) != transposed ? getrs_t_dev<T>(h, n, 1, LU, ldlu, d_ipiv, v, 1)
+                                          : getrs_dev<T>(h, n, 1, LU, ldlu, d_ipiv, v, 1);
+    };
+    for (int c0 = 0; c0 < nrhs; c0 += G) {
+        const int g = std::min(G, nrhs - c0);
+        int steps[G] = {0, 0, 0, 0, 0, 0, 0, 0};
+        double lstres[G];
+        bool active[G];
+        for (int j = 0; j < G; ++j) { lstres[j] = 3.0; active[j] = j < g; }
+        for (;;) {
+            LSX_TRY(launch_resid_bound<T>(h, trans, n, g, A, lda, B + c0, ldb, X + c0, ldx, Rg, Wg, G, part));
+            LSX_TRY(launch_berr<T>(h, n, g, Rg, Wg, G, X + c0, ldx, safe1, safe2, rec));
+            LSX_HIP(hipMemcpyAsync(r, rec, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+            LSX_HIP(hipStreamSynchronize(h->stream));
+            bool any = false;
+            for (int j = 0; j < g; ++j) {
+                if (!active[j]) continue;                   // a column that has stopped keeps its x (and its berr)
+                const double be = r[j];
+                berr[c0 + j] = be;
+                if (be > u && 2.0 * be <= lstres[j] && steps[j] < ITMAX) {
+                    LSX_TRY(launch_refine_take<T>(h, n, Rg + j, G, v));
+                    LSX_TRY(solve(false));
+                    LSX_TRY(launch_refine_add<T>(h, n, v, X + c0 + j, ldx));
+                    lstres[j] = be;
+                    steps[j] += 1;
+                    h->gerfs_steps = std::max(h->gerfs_steps, steps[j]);
+                    any = true;
+                } else {
+                    active[j] = false;                      // a NaN compares false: no step
+                }
+            }
+            if (!any) break;                                // Rg, Wg and max|x| now belong to the final X
+        }
+        for (int j = 0; j < g; ++j) {
+            if (berr[c0 + j] != berr[c0 + j]) { ferr[c0 + j] = berr[c0 + j]; continue; }   // NaN in A, B or X
+            const double xmax = r[8 + j];
+            LSX_TRY(launch_ferr_weight<T>(h, n, Rg + j, Wg + j, G, nu, safe1, safe2, wt));
+            LSX_HIP(hipMemsetAsync(isgn, 0, (size_t)n, h->stream));
+            LSX_TRY(launch_est_fill<T>(h, n, 0, v, (int32_t *)nullptr));
+            // lacn2 on M = diag(W) inv(op A)^T: its 1-norm is the infinity-norm of inv(op A) diag(W)
+            auto apply = [&](const int kase) -> int {
+                h->gerfs_solves += 1;
+                if (kase == 1) {
+                    LSX_TRY(solve(true));
+                    return launch_vec_mul<T>(h, n, wt, v);
+                }
+                LSX_TRY(launch_vec_mul<T>(h, n, wt, v));
+                return solve(false);
+            };
+            double est = 0;
+            LSX_TRY((lacn2_dev<T>(h, n, v, isgn, erec, apply, &est)));
+            ferr[c0 + j] = xmax != 0 ? est / xmax : est;
+        }
+    }
+    return check_dev_status(h);                             // a timed-out solve is a failure, not a bound
+}
+
+// host buffers: stage A, the factors, B and X, refine on the device, bring X back
+template <typename T>
+static int gerfs_host(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int lda, const T *LU, int ldlu,
+                      const int32_t *ipiv, const T *B, int ldb, T *X, int ldx, double *ferr, double *berr) {
+    LSX_ARG(h && (trans == 0 || trans == 1) && n >= 0 && nrhs >= 0 && lda >= n && ldlu >= n && ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(nrhs == 0 || (ferr && berr));
+    if (n == 0 || nrhs == 0) return gerfs_dev<T>(h, trans, n, nrhs, A, lda, LU, ldlu, ipiv, B, ldb, X, ldx, ferr, berr);
+    LSX_ARG(A && LU && ipiv && B && X);
+    const int ld = ld_for(n), ldr = ld_for(nrhs);
+    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) +
+                             pad256(sizeof(int32_t) * n) + 512));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    T *dLU = c.take<T>((size_t)n * ld);
+    T *dB = c.take<T>((size_t)n * ldr);
+    T *dX = c.take<T>((size_t)n * ldr);
+    int32_t *dp = c.take<int32_t>(n);
+    LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
+    LSX_TRY(h2d<T>(h, n, n, LU, ldlu, dLU, ld));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
+    LSX_TRY(h2d<T>(h, n, nrhs, X, ldx, dX, ldr));
+    LSX_HIP(hipMemcpyAsync(dp, ipiv, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+    bool singular = false;
+    LSX_TRY(gerfs_dev<T>(h, trans, n, nrhs, dA, ld, dLU, ld, dp, dB, ldr, dX, ldr, ferr, berr, &singular));
+    if (singular) return LSX_OK;                                    // X is left untouched
+    LSX_TRY(d2h<T>(h, n, nrhs, dX, ldr, X, ldx));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+// factor, solve, refine, bound for a host system; A and B are kept
+template <typename T>
+static int gesvr_host(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int lda, const T *B, int ldb, T *X, int ldx,
+                      double *ferr, double *berr, int *info) {
+    LSX_ARG(h && (trans == 0 || trans == 1) && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(nrhs == 0 || (ferr && berr));
+    if (info) *info = 0;
+    h->gerfs_steps = 0;
+    h->gerfs_solves = 0;
+    for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = 0.0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A && (nrhs == 0 || (B && X)));
+    const int ld = ld_for(n), ldr = ld_for(nrhs > 0 ? nrhs : 1);
+    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) +
+                             pad256(sizeof(int32_t) * n) + 1024));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    T *dLU = c.take<T>((size_t)n * ld);
+    T *dB = c.take<T>((size_t)n * ldr);
+    T *dX = c.take<T>((size_t)n * ldr);
+    int32_t *dp = c.take<int32_t>(n);
+    int *dinfo = c.take<int>(1);
+    int hinfo = 0;
+    LSX_TRY(factor_from_host<T>(h, n, A, lda, dLU, ld, dp, dinfo, &hinfo));
+    if (info) *info = hinfo;
+    if (hinfo != 0) {                                               // singular: X is not written
+        for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = INFINITY;
+        return LSX_OK;
+    }
+    if (nrhs == 0) return LSX_OK;
+    LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dX, ldr));
+    if (trans) LSX_TRY(getrs_t_dev<T>(h, n, nrhs, dLU, ld, dp, dX, ldr));
+    else LSX_TRY(getrs_dev<T>(h, n, nrhs, dLU, ld, dp, dX, ldr));
+    LSX_TRY(gerfs_dev<T>(h, trans, n, nrhs, dA, ld, dLU, ld, dp, dB, ldr, dX, ldr, ferr, berr));
+    LSX_TRY(d2h<T>(h, n, nrhs, dX, ldr, X, ldx));
+    LSX_HIP(hipStreamSynchronize(h->stream));
     return LSX_OK;
 }
 
@@ -1113,6 +1299,7 @@ int lsx_destroy(lsx_handle_t h) {
     if (h->ws4) (void)hipFree(h->ws4);
     if (h->ws6) (void)hipFree(h->ws6);
     if (h->ws7) (void)hipFree(h->ws7);
+    if (h->ws8) (void)hipFree(h->ws8);
     if (h->xchg) (void)hipFree(h->xchg);
     if (h->ws5) (void)hipFree(h->ws5);
     if (h->scratch) (void)hipFree(h->scratch);
@@ -1271,6 +1458,8 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value) {
     else if (!strcmp(key, "panel_fallbacks")) *value = h->panel_fallbacks;
     else if (!strcmp(key, "num_cu")) *value = h->num_cu;
     else if (!strcmp(key, "gecon_solves")) *value = h->gecon_solves;
+    else if (!strcmp(key, "gerfs_steps")) *value = h->gerfs_steps;
+    else if (!strcmp(key, "gerfs_solves")) *value = h->gerfs_solves;
     else { set_error("unknown option '%s'", key); return LSX_ERR_ARG; }
     return LSX_OK;
 }
@@ -1697,6 +1886,46 @@ int lsx_gecon_f32_dev(lsx_handle_t h, int norm, int n, const float *dLU, int lda
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h);
     return gecon_dev<float>(h, norm, n, dLU, lda, d_ipiv, anorm, rcond);
+}
+
+#define LSX_GERFS_ABI(sfx, T)                                                                                              \
+    int lsx_gerfs_##sfx(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int lda, const T *LU, int ldlu,           \
+                        const int32_t *ipiv, const T *B, int ldb, T *X, int ldx, double *ferr, double *berr) {             \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        return gerfs_host<T>(h, trans, n, nrhs, A, lda, LU, ldlu, ipiv, B, ldb, X, ldx, ferr, berr);                       \
+    }                                                                                                                      \
+    int lsx_gerfs_##sfx##_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *dA, int lda, const T *dLU, int ldlu,   \
+                              const int32_t *d_ipiv, const T *dB, int ldb, T *dX, int ldx, double *ferr, double *berr) {   \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        LSX_ARG(h);                                                                                                        \
+        return gerfs_dev<T>(h, trans, n, nrhs, dA, lda, dLU, ldlu, d_ipiv, dB, ldb, dX, ldx, ferr, berr);                  \
+    }                                                                                                                      \
+    int lsx_gesvr_##sfx(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int lda, const T *B, int ldb, T *X,       \
+                        int ldx, double *ferr, double *berr, int *info) {                                                  \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        return gesvr_host<T>(h, trans, n, nrhs, A, lda, B, ldb, X, ldx, ferr, berr, info);                                 \
+    }                                                                                                                      \
+    int lsx_diag_resid_bound_##sfx##_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *dA, int lda, const T *dB,   \
+                                         int ldb, const T *dX, int ldx, T *dR, T *dW, int ldr) {                           \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        LSX_ARG(h && (trans == 0 || trans == 1) && n >= 0 && nrhs >= 0 && nrhs <= 8 && lda >= n && ldb >= nrhs &&          \
+                ldx >= nrhs && ldr >= nrhs);                                                                               \
+        if (n == 0 || nrhs == 0) return LSX_OK;                                                                            \
+        LSX_ARG(dA && dB && dX && dR && dW);                                                                               \
+        LSX_TRY(ensure_scratch(h, resid_bound_work_bytes(trans, n) + 256));                                                \
+        return launch_resid_bound<T>(h, trans, n, nrhs, dA, lda, dB, ldb, dX, ldx, dR, dW, ldr, (double *)h->scratch);     \
+    }
+LSX_GERFS_ABI(f64, double)
+LSX_GERFS_ABI(f32, float)
+#undef LSX_GERFS_ABI
+
+int lsx_diag_resid_mixed_dev(lsx_handle_t h, int n, int nrhs, const float *dA, int lda, const float *dB, int ldb,
+                             const double *dX, int ldx, float *dR, int ldr) {
+    LSX_DEVICE_GUARD(h);
+    LSX_ARG(h && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs && ldx >= nrhs && ldr >= nrhs);
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(dA && dB && dX && dR);
+    return launch_resid_mixed(h, n, nrhs, dA, lda, dB, ldb, dX, ldx, dR, ldr);
 }
 int lsx_rcond_f64(lsx_handle_t h, int norm, int n, const double *A, int lda, double *rcond, int *info) {
     LSX_DEVICE_GUARD(h);

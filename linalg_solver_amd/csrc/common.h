@@ -124,6 +124,10 @@ struct lsx_handle_s {
     void *ws7 = nullptr;     // condition estimate: the iteration vector, its sign vector, the record, an identity interchange list
     size_t ws7_bytes = 0;
     int gecon_solves = 0;    // read-only option: single-right-hand-side solves of the last condition estimate
+    void *ws8 = nullptr;     // refined solve (gerfs): residual and bound of a group, correction / estimator vectors, records, partial sums
+    size_t ws8_bytes = 0;
+    int gerfs_steps = 0;     // read-only option: most refinement steps any column of the last gerfs took
+    int gerfs_solves = 0;    // read-only option: single-right-hand-side estimator solves of the last gerfs
     // gather lists (int2[256] each) emitted by the cooperative panel kernels: storage only, a launch is told which one
     void *moves_buf[2] = {nullptr, nullptr};  // the drivers' lists (the shared-CU look-ahead driver alternates)
     void *moves_api = nullptr;       // list of the last lsx_panel_f64_dev call, handed out by lsx_panel_moves_dev
@@ -335,6 +339,24 @@ template <typename T>
 int launch_est_asum_sign(lsx_handle_t h, int n, T *x, signed char *isgn, double *rec);
 template <typename T>
 int launch_est_amax_unit(lsx_handle_t h, int n, T *x, int jlast, double *rec);
+// refined solves (kernels_refine.hip): residual + componentwise bound of up to 8 right-hand sides in one pass over A
+// (trans: of A^T, two passes over partial sums in d_work), backward error / max |x| per column, and the vector steps
+size_t resid_bound_work_bytes(int trans, int n);
+template <typename T>
+int launch_resid_bound(lsx_handle_t h, int trans, int n, int ncols, const T *A, int lda, const T *B, int ldb, const T *X,
+                       int ldx, T *R, T *W, int ldr, double *d_work);
+template <typename T>
+int launch_berr(lsx_handle_t h, int n, int ncols, const T *R, const T *W, int ldr, const T *X, int ldx, double safe1,
+                double safe2, double *rec);
+template <typename T>
+int launch_refine_take(lsx_handle_t h, int n, const T *Rj, int ldr, T *d);
+template <typename T>
+int launch_refine_add(lsx_handle_t h, int n, const T *d, T *Xj, int ldx);
+template <typename T>
+int launch_ferr_weight(lsx_handle_t h, int n, const T *Rj, const T *Wj, int ldr, double nu, double safe1, double safe2,
+                       T *out);
+template <typename T>
+int launch_vec_mul(lsx_handle_t h, int n, const T *wt, T *v);
 int diag_mfma_peak(lsx_handle_t h, int is_f32, int iters, int blocks_per_cu, double *tflops, double *clock_mhz);
 int diag_cu_mask_probe(lsx_handle_t h, const uint32_t *mask_words, int nwords, int nblocks, unsigned *out_host);
 int getrf_mg_f64(lsx_handle_t *hs, int P, int n, double *const *dA, const int *lda, int32_t *const *d_ipiv,

@@ -201,6 +201,76 @@ def lu_rcond(LU: np.ndarray, ipiv: np.ndarray, anorm: float, norm=1, handle: Opt
     return rc.value
 
 
+def lu_refine(a, LU, ipiv, b, x, trans: bool = False, handle: Optional[N.Handle] = None):
+    """LAPACK's gerfs from existing factors (lsx_gerfs_*): refine the solution x of A X = B (trans=True: A^T X = B)
+    until its componentwise backward error stops improving, and bound its error.  a is the UNFACTORED matrix, LU /
+    ipiv its factors (lu_factor), x a solution (lu_solve).  Returns (x, ferr, berr): the refined solution (a new
+    array), and per right-hand side a bound of max|x - x_true| / max|x| and the componentwise backward error.  Both
+    are +inf when a pivot is exactly zero (x is returned as given) and NaN for a column with a NaN in its data."""
+    LU = np.asarray(LU)
+    if LU.ndim != 2 or LU.shape[0] != LU.shape[1]:
+        raise ValueError("lu_refine needs the square factor matrix")
+    ct, sfx = _ct(LU.dtype)
+    dt = LU.dtype
+    n = LU.shape[0]
+    A = np.ascontiguousarray(a, dtype=dt)
+    if A.shape != (n, n):
+        raise ValueError("lu_refine needs the unfactored matrix and its factors: same shape")
+    if len(ipiv) < n:
+        raise ValueError("ipiv is shorter than the matrix order")
+    if np.shape(b)[:1] != (n,) or np.shape(x) != np.shape(b):
+        raise ValueError("right-hand side and solution need as many rows as the matrix, and the same shape")
+    h = _h(handle)
+    LU = np.ascontiguousarray(LU)
+    ipiv = np.ascontiguousarray(ipiv, dtype=np.int32)
+    B = np.ascontiguousarray(b, dtype=dt)
+    X = np.array(x, dtype=dt, order="C", copy=True)
+    vec = X.ndim == 1
+    if vec:
+        B, X = B.reshape(n, 1), X.reshape(n, 1)
+    nrhs = X.shape[1]
+    ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+    ld, ldr = max(n, 1), max(nrhs, 1)
+    name = f"lsx_gerfs_{sfx}"
+    N.check(getattr(h.lib, name)(h.ptr, int(bool(trans)), n, nrhs, _ptr(A, ct), ld, _ptr(LU, ct), ld,
+                                 _ptr(ipiv, C.c_int32), _ptr(B, ct), ldr, _ptr(X, ct), ldr, _ptr(ferr, C.c_double),
+                                 _ptr(berr, C.c_double)), name)
+    ferr, berr = ferr[:nrhs], berr[:nrhs]
+    if vec:
+        return X[:, 0].copy(), float(ferr[0]), float(berr[0])
+    return X, ferr, berr
+
+
+def solve_bounded(a, b, trans: bool = False, dtype=np.float64, handle: Optional[N.Handle] = None):
+    """Factor, solve, refine and bound in one call (lsx_gesvr_*): returns (x, ferr, berr, info) with ferr / berr as in
+    lu_refine (floats for a vector b, arrays for a matrix).  info > 0 is an exactly zero pivot: x is None and the
+    bounds are +inf."""
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    n = A.shape[0]
+    if A.ndim != 2 or A.shape[1] != n:
+        raise ValueError("solve_bounded needs a square matrix")
+    if np.shape(b)[:1] != (n,):
+        raise ValueError("right-hand side has the wrong number of rows")
+    h = _h(handle)
+    B = np.ascontiguousarray(b, dtype=dtype)
+    vec = B.ndim == 1
+    if vec:
+        B = B.reshape(n, 1)
+    nrhs = B.shape[1]
+    X = np.zeros((n, nrhs), dtype=dtype)
+    ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+    info = C.c_int(0)
+    ld, ldr = max(n, 1), max(nrhs, 1)
+    name = f"lsx_gesvr_{sfx}"
+    N.check(getattr(h.lib, name)(h.ptr, int(bool(trans)), n, nrhs, _ptr(A, ct), ld, _ptr(B, ct), ldr, _ptr(X, ct), ldr,
+                                 _ptr(ferr, C.c_double), _ptr(berr, C.c_double), C.byref(info)), name)
+    ferr, berr = ferr[:nrhs], berr[:nrhs]
+    if vec:
+        return (None if info.value else X[:, 0].copy()), float(ferr[0]), float(berr[0]), info.value
+    return (None if info.value else X), ferr, berr, info.value
+
+
 def solve_refined(a, b, sweeps: int = 3, handle: Optional[N.Handle] = None):
     """Mixed-precision solve of A X = B (lsx_gesv_f32_refined): fp32 factors on the fp32 MFMA tile, residuals in
     fp64, `sweeps` corrections.  a and b are taken in fp32 (BASELINE config 5 computes in fp32); returns

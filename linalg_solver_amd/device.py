@@ -112,6 +112,33 @@ class DeviceSolver:
                                         anorm, C.byref(rc)), name)
         return rc.value
 
+    def gerfs_(self, A: torch.Tensor, LU: torch.Tensor, ipiv: torch.Tensor, B: torch.Tensor, X: torch.Tensor,
+               trans: bool = False):
+        """Refine X (a solution of A X = B, or A^T X = B with trans=True) in place from the factors LU / ipiv of A and
+        bound its error: LAPACK's gerfs on tensors in HBM (lsx_gerfs_*_dev).  Returns (ferr, berr) as numpy arrays,
+        one entry per right-hand side.  Synchronises the stream: the host drives the iteration."""
+        import ctypes as C
+
+        import numpy as np
+
+        for t, w in ((A, "A"), (LU, "LU"), (B, "B"), (X, "X")):
+            _rowmajor(t, "gerfs_ " + w)
+        n = A.shape[0]
+        if A.shape[1] != n or LU.shape != A.shape or B.shape[0] != n or X.shape != B.shape:
+            raise ValueError("gerfs_: need a square matrix, its factors, and B / X with as many rows")
+        if not (A.dtype == LU.dtype == B.dtype == X.dtype):
+            raise TypeError("gerfs_: all operands must have the same dtype")
+        if ipiv.dtype != torch.int32 or not ipiv.is_cuda or ipiv.dim() != 1 or not ipiv.is_contiguous() or ipiv.numel() < n:
+            raise ValueError("gerfs_: ipiv must be a contiguous int32 tensor on the GPU with at least n entries")
+        nrhs = B.shape[1]
+        ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+        dp = C.POINTER(C.c_double)
+        name = f"lsx_gerfs_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, int(bool(trans)), n, nrhs, A.data_ptr(), A.stride(0), LU.data_ptr(),
+                                        LU.stride(0), ipiv.data_ptr(), B.data_ptr(), B.stride(0), X.data_ptr(),
+                                        X.stride(0), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp)), name)
+        return ferr[:nrhs], berr[:nrhs]
+
     def getri(self, LU: torch.Tensor, ipiv: torch.Tensor, out: Optional[torch.Tensor] = None):
         _rowmajor(LU, "getri")
         n = LU.shape[0]

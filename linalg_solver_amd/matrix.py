@@ -274,11 +274,65 @@ class Matrix:
             raise IndexError("list index out of range")
         return R, pivots
 
-    def solve_array(self, rhs, trans: bool = False) -> "np.ndarray | Matrix.NoSolution":
+    def _solve_bounded(self, rhs, trans: bool):
+        """solve_array(bounds=True): factor once, solve, refine and bound (lsx_gerfs_*); NoSolution by the rule of
+        solve_array (exactly zero pivot, or smallest |pivot| / largest |entry| <= n eps)."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            import torch
+
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            n = A.shape[0]
+            if A.shape[1] != n:
+                raise ValueError("solve_array needs a square matrix")
+            dev = DeviceSolver(self._dev.device.index)
+            LU = A.clone()
+            ipiv, info = dev.getrf_(LU)
+            B = rhs if hasattr(rhs, "is_cuda") else torch.as_tensor(np.asarray(rhs, dtype=np.float64))
+            B = B.to(device=A.device, dtype=torch.float64)
+            vec = B.dim() == 1
+            if B.shape[0] != n:
+                raise ValueError("Matrix dimensions must match")
+            B = B.reshape(n, -1).contiguous()
+            code = int(info.item())
+            if code < 0:
+                dev.h.check_status()
+                raise RuntimeError(f"device factorisation failed (info = {code})")
+            ratio = float(LU.diagonal().abs().min() / A.abs().max().clamp_min(1e-300)) if n else 1.0
+            if code != 0 or not (ratio > dense.EPS64 * n):
+                return Matrix.NoSolution()
+            X = B.clone()
+            dev.getrs_(LU, ipiv, X, trans=trans)
+            ferr, berr = dev.gerfs_(A, LU, ipiv, B, X, trans=trans)
+            return (X[:, 0], float(ferr[0]), float(berr[0])) if vec else (X, ferr, berr)
+        A = self._array()
+        n = A.shape[0]
+        if A.shape[1] != n:
+            raise ValueError("solve_array needs a square matrix")
+        B = np.asarray(rhs, dtype=np.float64)
+        vec = B.ndim == 1
+        if B.shape[0] != n:
+            raise ValueError("Matrix dimensions must match")
+        B = B.reshape(n, -1)
+        LU, ipiv, info = dense.lu_factor(A)
+        amax = float(np.max(np.abs(A))) if n else 0.0
+        ratio = float(np.min(np.abs(np.diagonal(LU)))) / amax if amax > 0 else 0.0
+        if info != 0 or not (ratio > dense.EPS64 * n):
+            return Matrix.NoSolution()
+        X = dense.lu_solve(LU, ipiv, B, trans=trans)
+        X, ferr, berr = dense.lu_refine(A, LU, ipiv, B, X, trans=trans)
+        return (X[:, 0], float(ferr[0]), float(berr[0])) if vec else (X, ferr, berr)
+
+    def solve_array(self, rhs, trans: bool = False, bounds: bool = False):
         """Unique solution(s) of self * X = rhs for a square matrix (rhs: vector or matrix) as an ndarray;
         NoSolution() when the matrix is singular to working precision (use find_preimage_of for the
         general affine answer).  trans=True solves self^T * X = rhs (x * self = rhs^T for rows) from the factors of
-        self: no transposed copy, no second factorisation."""
+        self: no transposed copy, no second factorisation.  bounds=True refines the solution (LAPACK's gerfs) and
+        returns (x, ferr, berr): per right-hand side a bound of max|x - x_true| / max|x| and the componentwise
+        backward error (floats for a vector rhs, arrays for a matrix)."""
+        if bounds:
+            return self._solve_bounded(rhs, trans)
         if getattr(self, "_dev", None) is not None and self._items is None:
             return self._solve_device(rhs, trans)   # operands in HBM: the result is a device tensor too
         A = self._array()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | gecon [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | gecon | gerfs [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -11,6 +11,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from linalg_solver_amd import _native as N  # noqa: E402
 from linalg_solver_amd import gen  # noqa: E402
 from linalg_solver_amd.device import DeviceSolver  # noqa: E402
 
@@ -406,6 +407,87 @@ def main():
             t_con = sorted(ts)[len(ts) // 2]
             print(f"gecon f64 n={n}: getrf {t_lu:.3f} ms  lange {t_nrm:.3f} ms  gecon {t_con:.3f} ms "
                   f"({dev.h.get_option('gecon_solves')} solves, {t_con / t_lu * 100:.1f} % of getrf)  rcond {rc:.3e}", flush=True)
+    if "gerfs" in args.what:
+        # the residual-and-bound pass of the refined solve (kernels_refine.hip) alone, plain and transposed, beside the
+        # fp32-in / fp64-sum residual of the mixed-precision solve on the same fp32 data; then a whole gerfs call beside
+        # the factorisation and the condition estimate.  Median of 21 timed calls after 3 warm-up calls, two
+        # alternating rounds (the smaller median is reported, both are printed).
+        HBM = 8.0e12
+        lib, hp = dev.lib, dev.h.ptr
+
+        def med(fn):
+            return timeit(fn, reps=21, warm=3)[1]
+        for n in (1024, 4096, 8192):
+            for dt in (torch.float64, torch.float32):
+                sfx = "f64" if dt == torch.float64 else "f32"
+                A = torch.empty(n, n, dtype=dt, device="cuda")
+                dev.fill_(A, gen.U11, 1)
+                for nrhs in (1, 8):
+                    B = torch.empty(n, nrhs, dtype=dt, device="cuda")
+                    X = torch.empty(n, nrhs, dtype=dt, device="cuda")
+                    dev.fill_(B, gen.U11, 2)
+                    dev.fill_(X, gen.U11, 3)
+                    R, W = torch.empty_like(B), torch.empty_like(B)
+                    fn = getattr(lib, f"lsx_diag_resid_bound_{sfx}_dev")
+                    runs = {"plain": lambda: fn(hp, 0, n, nrhs, A.data_ptr(), n, B.data_ptr(), nrhs, X.data_ptr(), nrhs,
+                                                R.data_ptr(), W.data_ptr(), nrhs),
+                            "transposed": lambda: fn(hp, 1, n, nrhs, A.data_ptr(), n, B.data_ptr(), nrhs, X.data_ptr(), nrhs,
+                                                     R.data_ptr(), W.data_ptr(), nrhs)}
+                    if dt == torch.float32:
+                        X64 = X.double()
+                        runs["resid_mixed"] = lambda: lib.lsx_diag_resid_mixed_dev(hp, n, nrhs, A.data_ptr(), n, B.data_ptr(),
+                                                                                   nrhs, X64.data_ptr(), nrhs, R.data_ptr(), nrhs)
+                    for k, f in runs.items():       # a refused call must not be timed as a very fast pass
+                        N.check(f(), k)
+                    res = {k: [] for k in runs}
+                    for _ in range(2):
+                        for k, f in runs.items():
+                            res[k].append(med(f))
+                    by = float(n) * n * A.element_size()
+                    print(f"resid_bound {sfx} n={n} nrhs={nrhs}: " + "  ".join(
+                        f"{k} {min(v) * 1e3:.1f} us (rounds {v[0] * 1e3:.1f} / {v[1] * 1e3:.1f}; "
+                        f"{by / (min(v) * 1e-3) / HBM * 100:.1f} % of 8 TB/s)" for k, v in res.items()), flush=True)
+        for n in (1024, 4096, 8192):
+            A0 = torch.empty(n, n, dtype=torch.float64, device="cuda")
+            dev.fill_(A0, gen.U11, 1)
+            LU = A0.clone()
+            ipiv = torch.zeros(n, dtype=torch.int32, device="cuda")
+            info = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+            def factor():
+                LU.copy_(A0)
+                dev.getrf_(LU, ipiv, info)
+            t_lu = timeit(factor, reps=7, warm=2)[1] - timeit(lambda: LU.copy_(A0), reps=7, warm=2)[1]
+            factor()
+            anorm = float(dev.norm(A0, 1).item())
+
+            def host_med(fn, reps=21, warm=3):      # synchronous calls: host clock around them
+                for _ in range(warm):
+                    fn()
+                ts = []
+                for _ in range(reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                return sorted(ts)[len(ts) // 2]
+            t_con = host_med(lambda: dev.rcond(LU, ipiv, anorm))
+            for nrhs in (1, 8):
+                B = torch.empty(n, nrhs, dtype=torch.float64, device="cuda")
+                dev.fill_(B, gen.U11, 2)
+                X0 = B.clone()
+                dev.getrs_(LU, ipiv, X0)
+                X = X0.clone()
+
+                def refine():
+                    X.copy_(X0)
+                    return dev.gerfs_(A0, LU, ipiv, B, X)
+                rounds = [host_med(refine) for _ in range(2)]
+                ferr, berr = refine()
+                print(f"gerfs f64 n={n} nrhs={nrhs}: getrf {t_lu:.3f} ms  gecon {t_con:.3f} ms  gerfs {min(rounds):.3f} ms "
+                      f"(rounds {rounds[0]:.3f} / {rounds[1]:.3f}; {dev.h.get_option('gerfs_steps')} steps, "
+                      f"{dev.h.get_option('gerfs_solves')} estimator solves, {min(rounds) / t_lu * 100:.1f} % of getrf)  "
+                      f"berr {berr.max():.2e} ferr {ferr.max():.2e}", flush=True)
     if "lu" in args.what:
         n = args.n
         A0 = torch.empty(n, n, dtype=torch.float32 if args.f32 else torch.float64, device="cuda")
