@@ -95,6 +95,9 @@ const char *lsx_last_error(void);
  *                   in one launch at the end
  *   "getri_pairs"   inverse / many-right-hand-side solve at large regular orders: 1 = two 128-row blocks per trailing
  *                   update (depth 256, same bits, 8192^2 inverse 17.6 -> 15.8 ms) [1], 0 = one
+ *   "getrs_t_blocked_min"  transposed solve with n > 128: the smallest nrhs that takes the blocked sweeps on the MFMA
+ *                   tile instead of groups of 8 columns; any value >= 1, 0 = never [64; measured break-even 32: DESIGN 3.4]
+ *   "getrs_t_path"  (read only) 1 if the last lsx_getrs_t_* call on this handle took the blocked sweeps, else 0
  *   "gemm_waves", "gemm_stagger", "panel_rt", "panel_nt", "hybrid", "xrows_limit", "rref_blocked",
  *   "getri_structured"                      tuning / cross-check switches, see DESIGN.md
  *   "panel_spin_limit", "trsv_spin_limit", "chain_wait_limit"   bounded-spin limits (tests inject time-outs)
@@ -189,10 +192,18 @@ int lsx_gesv_f32(lsx_handle_t h, int n, int nrhs, const float *A, int lda, float
 /* matrix norms of lsx_lange_* / lsx_gecon_* / lsx_rcond_*: max absolute column sum, max absolute row sum */
 enum { LSX_NORM_ONE = 0, LSX_NORM_INF = 1 };
 /* Solve A^T X = B (equivalently x A = b for rows) from the factors of A: U^T Y = B, L^T Z = Y, X[perm] = Z -- no
- * second factorisation.  B (n x nrhs, row-major) is overwritten by X.  Arguments are validated as in lsx_getrs_*;
- * right-hand sides are processed in groups of up to 8 columns (one launch per 128-row block step and group: the
- * few-right-hand-side path, correct but not a throughput path for many columns).  Deterministic: two calls give
- * identical bits. */
+ * second factorisation, no transposed copy of the factors.  B (n x nrhs, row-major) is overwritten by X.  Arguments
+ * are validated as in lsx_getrs_*.  Two paths (n <= 128 is one workgroup either way):
+ *   grouped   nrhs < "getrs_t_blocked_min" (or that option 0): right-hand sides in groups of up to 8 columns, one launch
+ *             per 128-row block step and group, the block rows of the factors streamed through registers -- the path
+ *             of few right-hand sides and of the single-column solves inside lsx_gecon_* and lsx_gerfs_*;
+ *   blocked   nrhs >= "getrs_t_blocked_min" and n > 128: all columns at once, 128-row block sweeps whose products
+ *             C -= A^T B run on the MFMA tile of the trailing update in its TN form (lsx_gemm_tn_sub_*_dev), two
+ *             launches per block step whatever nrhs is; extra work space 2 n x nrhs elements.
+ * The option "getrs_t_path" reads back which one the last call took.  Deterministic: two calls give identical bits on
+ * either path, and on the blocked path a column gets the same bits whichever other columns are passed with it and
+ * whatever lda, ldb and the alignment of the operands are.  The two paths sum in different orders: their results
+ * agree to rounding, not bit for bit. */
 int lsx_getrs_t_f64(lsx_handle_t h, int n, int nrhs, const double *LU, int lda, const int32_t *ipiv,
                     double *B, int ldb);
 int lsx_getrs_t_f32(lsx_handle_t h, int n, int nrhs, const float *LU, int lda, const int32_t *ipiv,
@@ -342,6 +353,19 @@ int lsx_gemm_add_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dA, 
                          const double *dB, int ldb, double *dC, int ldc);
 int lsx_gemm_sub_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dA, int lda,
                          const float *dB, int ldb, float *dC, int ldc);
+/* "TN" forms of the same tile: dC (m x n) -= dA^T * dB with dA stored k x m, row-major, lda >= m (a block row of U or L
+ * as it lies in the factors: the transposed sweeps).  Any m, n, k >= 0, any alignment and leading dimensions; a zero
+ * extent leaves dC untouched (pointers may then be NULL).  Every n takes the MFMA tile and k is taken in ascending
+ * order, so a column of dC gets the same bits whatever the other columns of the call are and whichever of the interior
+ * and bounds-checked forms its tile takes.  LSX_ERR_ARG for negative sizes, lda < m, ldb < n, ldc < n or a NULL pointer
+ * with non-zero sizes. */
+int lsx_gemm_tn_sub_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dA, int lda,
+                            const double *dB, int ldb, double *dC, int ldc);
+/* dC += dA^T * dB. */
+int lsx_gemm_tn_add_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dA, int lda,
+                            const double *dB, int ldb, double *dC, int ldc);
+int lsx_gemm_tn_sub_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dA, int lda,
+                            const float *dB, int ldb, float *dC, int ldc);
 
 /* Deterministic synthetic inputs written straight into HBM:
  * element (i,j) = f(splitmix64(seed*GOLDEN + (i+row_off)<<32 + (j+col_off))). */

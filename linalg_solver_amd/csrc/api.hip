@@ -855,10 +855,54 @@ static int gesv_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, T *B,
 
 
 // ---------------------------------------------------------------- transposed solve, norms, condition estimate
-// A^T X = B from the factors (kernels_trsvt.hip).  Work space as in getrs_dev, so the two share what they grow.
+// Blocked A^T X = B for many right-hand sides (n > 128): the sweeps of lu_solve_permuted for the transposed factors, every
+// product on the TN form of the MFMA tile (kernels_gemm.hip), which reads the block rows of U and L as they lie in memory.
+//   forward,  U^T Y = B, k ascending:   Y_k = inv(U_kk)^T W_k ;  W[k+jb:] -= U[k:k+jb, k+jb:]^T Y_k
+//   backward, L^T Z = Y, k descending:  Z_k = inv(L_kk)^T Y_k ;  Y[:k]    -= L[k:k+jb, :k]^T Z_k
+//   X[perm[i], :] = Z[i, :]
+// inv(T_kk) are the natural-orientation 128 x 128 block inverses of the grouped path (identity outside the matrix), so
+// inv^T W_k is a TN product of depth jb too; it cannot run in place, so the two n x nrhs work arrays take turns: the
+// forward sweep reads W and leaves Y in the second array, the backward sweep leaves Z in the first.  W (ld = ldw, a
+// multiple of 16) is an aligned copy of B: whatever ldb is, the interior tiles take the FULL form when LU allows it.
+// A column's bits do not depend on the other columns of the call: every product is an MFMA tile that takes k in order.
 template <typename T>
-static int getrs_t_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, const int32_t *d_ipiv, T *B, int ldb) {
+static int lu_solve_transposed_blocked(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, const int32_t *perm, T *B,
+                                       int ldb, const T *inv128L, const T *inv128U, T *W, T *Y, int ldw) {
+    const int sb = 128;
+    auto Fp = [&](int r, int c) { return LU + (size_t)r * lda + c; };
+    auto Wp = [&](int r) { return W + (size_t)r * ldw; };
+    auto Yp = [&](int r) { return Y + (size_t)r * ldw; };
+    LSX_TRY(launch_copy2d<T>(h, n, nrhs, B, ldb, W, ldw));
+    for (int kb = 0; kb < n; kb += sb) {
+        const int jb = (n - kb < sb) ? n - kb : sb;
+        LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nrhs, jb, inv128U + (size_t)(kb / sb) * sb * sb, sb, Wp(kb), ldw, Yp(kb), ldw));
+        LSX_TRY(launch_gemm_tn_sub<T>(h, n - kb - jb, nrhs, jb, Fp(kb, kb + jb), lda, Yp(kb), ldw, Wp(kb + jb), ldw));
+    }
+    for (int kb = ((n - 1) / sb) * sb; kb >= 0; kb -= sb) {
+        const int jb = (n - kb < sb) ? n - kb : sb;
+        LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nrhs, jb, inv128L + (size_t)(kb / sb) * sb * sb, sb, Yp(kb), ldw, Wp(kb), ldw));
+        LSX_TRY(launch_gemm_tn_sub<T>(h, kb, nrhs, jb, Fp(kb, 0), lda, Wp(kb), ldw, Y, ldw));
+    }
+    return launch_scatter_rows<T>(h, n, nrhs, perm, W, ldw, B, ldb);
+}
+
+// lsx_gemm_tn_*_dev: A is k x m (lda >= m).  A zero extent is legal and leaves C untouched, with or without pointers.
+template <typename T>
+static int gemm_tn_dev(lsx_handle_t h, int plus, int m, int n, int k, const T *dA, int lda, const T *dB, int ldb, T *dC,
+                       int ldc) {
+    LSX_ARG(h && m >= 0 && n >= 0 && k >= 0 && lda >= m && ldb >= n && ldc >= n);
+    if (m == 0 || n == 0 || k == 0) return LSX_OK;
+    LSX_ARG(dA && dB && dC);
+    return launch_gemm_tn_acc<T>(h, plus, m, n, k, dA, lda, dB, ldb, dC, ldc);
+}
+
+// A^T X = B from the factors (kernels_trsvt.hip).  Work space as in getrs_dev, so the two share what they grow.
+// may_block = false: the single-column solves inside the estimators, which keep the grouped path whatever the option says.
+template <typename T>
+static int getrs_t_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, const int32_t *d_ipiv, T *B, int ldb,
+                       bool may_block = false) {
     LSX_ARG(n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs && LU && d_ipiv && B);
+    if (may_block) h->getrs_t_path = 0;
     if (n == 0 || nrhs == 0) return LSX_OK;
     if (n <= 128)   // one workgroup, interchanges included: no work space
         return lu_solve_transposed<T>(h, n, nrhs, LU, lda, d_ipiv, nullptr, B, ldb, (T *)nullptr, (T *)nullptr,
@@ -866,12 +910,23 @@ static int getrs_t_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, co
     const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
     const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
     const size_t vec = pad256(sizeof(T) * (size_t)n * 8);
-    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(int32_t) * n) + 3 * vec));
+    // blocked path: two n x nrhs work arrays (ld = ldw) in place of the n x 8 work vector
+    const bool blocked = may_block && h->getrs_t_blocked_min > 0 && nrhs >= h->getrs_t_blocked_min;
+    const int ldw = ld_for(nrhs);
+    const size_t arr = pad256(sizeof(T) * (size_t)n * ldw);
+    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(int32_t) * n) + (blocked ? 2 * arr : 3 * vec)));
     LSX_TRY(grow(&h->ws2, &h->ws2_bytes, 2 * b64 + 2 * b128));
     LSX_TRY(ensure_scratch(h, 8 * (size_t)n + 256));   // index arrays of the permutation conversion
     int32_t *perm = (int32_t *)h->ws3;
     T *W = (T *)((char *)h->ws3 + pad256(sizeof(int32_t) * n));
     char *w2 = (char *)h->ws2;
+    if (blocked) {
+        LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
+        LSX_TRY(launch_inv128_natural<T>(h, n, LU, lda, (T *)w2, (T *)(w2 + b64), (T *)(w2 + 2 * b64), (T *)(w2 + 2 * b64 + b128)));
+        h->getrs_t_path = 1;
+        return lu_solve_transposed_blocked<T>(h, n, nrhs, LU, lda, perm, B, ldb, (const T *)(w2 + 2 * b64),
+                                              (const T *)(w2 + 2 * b64 + b128), W, (T *)((char *)W + arr), ldw);
+    }
     LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
     return lu_solve_transposed<T>(h, n, nrhs, LU, lda, d_ipiv, perm, B, ldb, (T *)w2, (T *)(w2 + b64), (T *)(w2 + 2 * b64),
                                   (T *)(w2 + 2 * b64 + b128), W);
@@ -892,7 +947,7 @@ static int getrs_t_host(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, c
     LSX_TRY(h2d<T>(h, n, n, LU, lda, dA, ld));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
     LSX_HIP(hipMemcpyAsync(dp, ipiv, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-    LSX_TRY(getrs_t_dev<T>(h, n, nrhs, dA, ld, dp, dB, ldx));
+    LSX_TRY(getrs_t_dev<T>(h, n, nrhs, dA, ld, dp, dB, ldx, true));
     LSX_TRY(d2h<T>(h, n, nrhs, dB, ldx, B, ldb));
     LSX_HIP(hipStreamSynchronize(h->stream));
     return LSX_OK;
@@ -1159,7 +1214,7 @@ static int gesvr_host(lsx_handle_t h, int trans, int n, int nrhs, const T *A, in
     LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dX, ldr));
-    if (trans) LSX_TRY(getrs_t_dev<T>(h, n, nrhs, dLU, ld, dp, dX, ldr));
+    if (trans) LSX_TRY(getrs_t_dev<T>(h, n, nrhs, dLU, ld, dp, dX, ldr, true));
     else LSX_TRY(getrs_dev<T>(h, n, nrhs, dLU, ld, dp, dX, ldr));
     LSX_TRY(gerfs_dev<T>(h, trans, n, nrhs, dA, ld, dLU, ld, dp, dB, ldr, dX, ldr, ferr, berr));
     LSX_TRY(d2h<T>(h, n, nrhs, dX, ldr, X, ldx));
@@ -1429,6 +1484,9 @@ int lsx_set_option(lsx_handle_t h, const char *key, int value) {
     } else if (!strcmp(key, "lookahead_min")) {
         LSX_ARG(value >= 0);
         h->lookahead_min = value;
+    } else if (!strcmp(key, "getrs_t_blocked_min")) {   // transposed solve: smallest nrhs on the blocked sweeps (n > 128); 0 = never
+        LSX_ARG(value >= 0);
+        h->getrs_t_blocked_min = value;
     } else {
         set_error("unknown option '%s'", key);
         return LSX_ERR_ARG;
@@ -1460,6 +1518,8 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value) {
     else if (!strcmp(key, "gecon_solves")) *value = h->gecon_solves;
     else if (!strcmp(key, "gerfs_steps")) *value = h->gerfs_steps;
     else if (!strcmp(key, "gerfs_solves")) *value = h->gerfs_solves;
+    else if (!strcmp(key, "getrs_t_blocked_min")) *value = h->getrs_t_blocked_min;
+    else if (!strcmp(key, "getrs_t_path")) *value = h->getrs_t_path;
     else { set_error("unknown option '%s'", key); return LSX_ERR_ARG; }
     return LSX_OK;
 }
@@ -1847,13 +1907,13 @@ int lsx_getrs_t_f64_dev(lsx_handle_t h, int n, int nrhs, const double *dLU, int 
                         int ldb) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h);
-    return getrs_t_dev<double>(h, n, nrhs, dLU, lda, d_ipiv, dB, ldb);
+    return getrs_t_dev<double>(h, n, nrhs, dLU, lda, d_ipiv, dB, ldb, true);
 }
 int lsx_getrs_t_f32_dev(lsx_handle_t h, int n, int nrhs, const float *dLU, int lda, const int32_t *d_ipiv, float *dB,
                         int ldb) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h);
-    return getrs_t_dev<float>(h, n, nrhs, dLU, lda, d_ipiv, dB, ldb);
+    return getrs_t_dev<float>(h, n, nrhs, dLU, lda, d_ipiv, dB, ldb, true);
 }
 int lsx_lange_f64_dev(lsx_handle_t h, int norm, int m, int n, const double *dA, int lda, double *d_out) {
     LSX_DEVICE_GUARD(h);
@@ -2103,6 +2163,21 @@ int lsx_gemm_sub_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dA, i
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && dA && dB && dC && lda >= k && ldb >= n && ldc >= n);
     return launch_gemm_sub<float>(h, m, n, k, dA, lda, dB, ldb, dC, ldc);
+}
+int lsx_gemm_tn_sub_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dA, int lda, const double *dB, int ldb,
+                            double *dC, int ldc) {
+    LSX_DEVICE_GUARD(h);
+    return gemm_tn_dev<double>(h, 0, m, n, k, dA, lda, dB, ldb, dC, ldc);
+}
+int lsx_gemm_tn_add_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dA, int lda, const double *dB, int ldb,
+                            double *dC, int ldc) {
+    LSX_DEVICE_GUARD(h);
+    return gemm_tn_dev<double>(h, 1, m, n, k, dA, lda, dB, ldb, dC, ldc);
+}
+int lsx_gemm_tn_sub_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dA, int lda, const float *dB, int ldb,
+                            float *dC, int ldc) {
+    LSX_DEVICE_GUARD(h);
+    return gemm_tn_dev<float>(h, 0, m, n, k, dA, lda, dB, ldb, dC, ldc);
 }
 
 int lsx_fill_f64_dev(lsx_handle_t h, int kind, uint64_t seed, int m, int n, double *dA, int lda,

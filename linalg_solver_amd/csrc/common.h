@@ -128,6 +128,8 @@ struct lsx_handle_s {
     size_t ws8_bytes = 0;
     int gerfs_steps = 0;     // read-only option: most refinement steps any column of the last gerfs took
     int gerfs_solves = 0;    // read-only option: single-right-hand-side estimator solves of the last gerfs
+    int getrs_t_blocked_min = 64;   // transposed solve: smallest nrhs that takes the blocked (MFMA) sweeps when n > 128; 0 = never
+    int getrs_t_path = 0;    // read-only option: 1 if the last lsx_getrs_t_* call took the blocked sweeps
     // gather lists (int2[256] each) emitted by the cooperative panel kernels: storage only, a launch is told which one
     void *moves_buf[2] = {nullptr, nullptr};  // the drivers' lists (the shared-CU look-ahead driver alternates)
     void *moves_api = nullptr;       // list of the last lsx_panel_f64_dev call, handed out by lsx_panel_moves_dev
@@ -249,6 +251,12 @@ int launch_gemm_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, co
 template <typename T>
 int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, int lda, const T *B, int ldb,
                     T *C, int ldc, const GemmPlan &plan = GemmPlan(), GemmDone *done = nullptr);
+// TN form on the same tile, A stored k x m: C -= A^T*B (mode 0), C += A^T*B (1), C = A^T*B (3)
+template <typename T>
+int launch_gemm_tn_acc(lsx_handle_t h, int mode, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C,
+                       int ldc);
+template <typename T>
+int launch_gemm_tn_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C, int ldc);
 // traced reference-order row reduction (kernels_trace.hip); d_out = {pivots, steps, overflow}
 int launch_rref_trace(lsx_handle_t h, int m, int n, int bar, double *R, int ldr, unsigned char *Tm,
                       int32_t *d_pivots, int32_t *d_steps, int max_steps, double *d_snaps,
@@ -330,6 +338,9 @@ int launch_inv128_natural(lsx_handle_t h, int n, const T *LU, int lda, T *inv64L
 template <typename T>
 int lu_solve_transposed(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, const int32_t *d_ipiv, const int32_t *perm,
                         T *B, int ldb, T *inv64L, T *inv64U, T *inv128L, T *inv128U, T *W);
+// X[perm[i], 0..ncols) = W[i, 0..ncols): the row scatter that ends a transposed solve, whole rows at once
+template <typename T>
+int launch_scatter_rows(lsx_handle_t h, int n, int ncols, const int32_t *d_perm, const T *W, int ldw, T *X, int ldx);
 size_t lange_work_bytes(int norm, int m, int n);
 template <typename T>
 int launch_lange(lsx_handle_t h, int norm, int m, int n, const T *A, int lda, double *d_work, double *d_out);

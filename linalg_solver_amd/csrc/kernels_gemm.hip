@@ -73,7 +73,12 @@ struct ASlab {
 // ticket_ctr != nullptr (work-queue kernel): thread 0 draws the workgroup's NEXT ticket from that counter while the
 // last slab is being multiplied and leaves it in *s_next before the C stores -- a device-scope atomic takes 2-3 us
 // to return, which drawn between two tiles would be ~10 % of a tile with nothing to cover it.
-template <typename T, bool FULL, int NWN, int BM_>
+// TA ("TN" form, C -+= A^T * B): A is stored K x M row-major, so a k-slab of A^T is 16 rows of 128 contiguous elements --
+// the shape of the B slab -- and is loaded with B's thread map (one k-row per wave, 16 bytes per lane in fp64) and stored
+// into the same AS_AT layout: a wave writes one k-row of 128 consecutive elements, which no pair stride can make
+// conflict.  The MFMA loop and the C traffic are those of the plain form.  plus bit 1 (TA only): the accumulators
+// start from zero instead of from C, so plus = 3 is C = A^T * B.
+template <typename T, bool FULL, int NWN, int BM_, bool TA = false>
 __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__restrict__ A, int lda,
                                               const T *__restrict__ B, int ldb, T *__restrict__ C, int ldc,
                                               int m0, int n0, T (*As)[BK / 2][ASlab<T, BM_>::PAIR], T (*Bs)[BK][BN + LPAD],
@@ -104,18 +109,22 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
     // B slab 16 x 128: thread -> k (tid>>6) + (NT/64)*i, column pair (tid&63)*2
     const int a_row = tid >> 3, a_k = (tid & 7) * 2;
     const int b_k = tid >> 6, b_n = (tid & 63) * 2;
+    // TN form: A^T slab 16 x 128 with the B map: thread -> k (tid>>6) + (NT/64)*i, row pair (tid&63)*2 of the tile
+    static_assert(!TA || NLA == NL, "the TN form stages A with the B map: 128-row tiles only");
     T ra0[NLA][2], rb0[NL][2];   // one staging set: slab kt+1 is in flight under the MFMAs of slab kt
-    const T sgn = plus ? T(1) : T(-1);
+    const T sgn = (TA ? (plus & 1) : plus) ? T(1) : T(-1);
+    const bool from_zero = TA && (plus & 2);
     unsigned a_off[NLA], b_off[NL];
 #pragma unroll
-    for (int i = 0; i < NLA; ++i) a_off[i] = (unsigned)(a_row + (NT / 8) * i) * (unsigned)lda + a_k;
+    for (int i = 0; i < NLA; ++i)
+        a_off[i] = TA ? (unsigned)(b_k + (NT / 64) * i) * (unsigned)lda + b_n : (unsigned)(a_row + (NT / 8) * i) * (unsigned)lda + a_k;
 #pragma unroll
     for (int i = 0; i < NL; ++i) b_off[i] = (unsigned)(b_k + (NT / 64) * i) * (unsigned)ldb + b_n;
 
     auto load_slab = [&](int k0, T (&ra)[NLA][2], T (&rb)[NL][2]) __attribute__((always_inline)) {
         if (FULL) {
             // uniform 64-bit base + 32-bit lane offset: the addresses cost NL VGPRs per operand, not 2*NL per set
-            const T *Au = A + (size_t)m0 * lda + kmap(k0);
+            const T *Au = TA ? A + (size_t)kmap(k0) * lda + m0 : A + (size_t)m0 * lda + kmap(k0);
             const T *Bu = B + (size_t)kmap(k0) * ldb + n0;
 #pragma unroll
             for (int i = 0; i < NLA; ++i) {
@@ -130,11 +139,19 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
         } else {
 #pragma unroll
             for (int i = 0; i < NLA; ++i) {
-                const int row = m0 + a_row + (NT / 8) * i;
-                const int kk = k0 + a_k;
-                const T *p = A + (size_t)row * lda;
-                ra[i][0] = (row < M && kk < K) ? p[kmap(kk)] : T(0);
-                ra[i][1] = (row < M && kk + 1 < K) ? p[kmap(kk + 1)] : T(0);
+                if (TA) {
+                    const int kk = k0 + b_k + (NT / 64) * i;
+                    const int row = m0 + b_n;
+                    const T *p = A + (size_t)(kk < K ? kmap(kk) : 0) * lda + row;
+                    ra[i][0] = (kk < K && row < M) ? p[0] : T(0);
+                    ra[i][1] = (kk < K && row + 1 < M) ? p[1] : T(0);
+                } else {
+                    const int row = m0 + a_row + (NT / 8) * i;
+                    const int kk = k0 + a_k;
+                    const T *p = A + (size_t)row * lda;
+                    ra[i][0] = (row < M && kk < K) ? p[kmap(kk)] : T(0);
+                    ra[i][1] = (row < M && kk + 1 < K) ? p[kmap(kk + 1)] : T(0);
+                }
             }
 #pragma unroll
             for (int i = 0; i < NL; ++i) {
@@ -152,8 +169,13 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
     auto store_slab = [&](int buf, T (&ra)[NLA][2], T (&rb)[NL][2]) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < NLA; ++i) {  // sign folded into A: the k-loop then accumulates C -+ A*B
-            AS_AT(buf, a_k, a_row + (NT / 8) * i) = sgn * ra[i][0];
-            AS_AT(buf, a_k + 1, a_row + (NT / 8) * i) = sgn * ra[i][1];
+            if (TA) {
+                AS_AT(buf, b_k + (NT / 64) * i, b_n) = sgn * ra[i][0];
+                AS_AT(buf, b_k + (NT / 64) * i, b_n + 1) = sgn * ra[i][1];
+            } else {
+                AS_AT(buf, a_k, a_row + (NT / 8) * i) = sgn * ra[i][0];
+                AS_AT(buf, a_k + 1, a_row + (NT / 8) * i) = sgn * ra[i][1];
+            }
         }
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
@@ -178,7 +200,8 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
             T v[TN];
 #pragma unroll
             for (int t = 0; t < TN; ++t) v[t] = T(0);
-            if (FULL) {
+            if (from_zero) {
+            } else if (FULL) {
 #pragma unroll
                 for (int t = 0; t < TN; t += 2) {
                     const v2 x = *(const v2 *)(p + t);
@@ -247,6 +270,22 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
         }
 }
 
+// XCD-aware grouped tile order: workgroup bid of nwg = tiles_m * tiles_n -> its tile.  Workgroups that share an XCD
+// (bid % 8) take consecutive places in a sequence that walks bands of 8 tile rows column by column.
+__device__ __forceinline__ void grouped_tile(int bid, int nwg, int tiles_m, int tiles_n, int &tile_m, int &tile_n) {
+    {
+        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+    }
+    constexpr int GROUP = 8;
+    const int per_group = GROUP * tiles_n;
+    const int group_id = bid / per_group;
+    const int first_m = group_id * GROUP;
+    const int gsize = min(tiles_m - first_m, GROUP);
+    tile_m = first_m + (bid % per_group) % gsize;
+    tile_n = (bid % per_group) / gsize;
+}
+
 // FULL = true: interior tiles only (grid covers tiles_m x tiles_n complete tiles, operands aligned);
 // FULL = false: any tile, every access bounds-checked.  Two kernels rather than one branch so the
 // interior kernel's register allocation is not set by the edge path (it spilled inside 128 VGPRs).
@@ -292,20 +331,25 @@ __global__ __launch_bounds__((BM_ < 64 ? 1 : BM_ / 64) * NWN * 64, (BM_ <= 64) ?
     const int first_col = col0_done ? 1 : 0;            // columns left to the grouped order
     if (col0_done) tiles_n -= 1;
     const int nwg = tiles_m * tiles_n;
-    int bid = (int)blockIdx.x - (col0_done ? tiles_m : 0);
-    {
-        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
-    constexpr int GROUP = 8;
-    const int per_group = GROUP * tiles_n;
-    const int group_id = bid / per_group;
-    const int first_m = group_id * GROUP;
-    const int gsize = min(tiles_m - first_m, GROUP);
-    const int tile_m = first_m + (bid % per_group) % gsize;
-    const int tile_n = (bid % per_group) / gsize;
+    int tile_m, tile_n;
+    grouped_tile((int)blockIdx.x - (col0_done ? tiles_m : 0), nwg, tiles_m, tiles_n, tile_m, tile_n);
     const int m0 = (tile_m + tm_off) * BM_, n0 = (tile_n + first_col + tn_off) * BN;
     gemm_sub_tile<T, FULL, NWN, BM_>(M, N, K, A, lda, B, ldb, C, ldc, m0, n0, As, Bs, plus);
+}
+
+// TN form, C (M x N) -+= A^T * B with A stored K x M (gemm_sub_tile, TA): the block rows of U and L as they lie in the
+// row-major factors, for the transposed sweeps (api.hip, lu_solve_transposed_blocked).  Plain static grid in the grouped
+// tile order, interior and edge strips as above; no queue, no k rotation, no counters.
+template <typename T, int NWN, bool FULL>
+__global__ __launch_bounds__(BM * NWN, (sizeof(T) == 4 && NWN == 4) ? 6 : NWN) void gemm_tn_kernel(
+    int M, int N, int K, const T *__restrict__ A, int lda, const T *__restrict__ B, int ldb, T *__restrict__ C, int ldc,
+    int tiles_m, int tiles_n, int tm_off, int tn_off, int plus) {
+    __shared__ T As[2][BK / 2][ASlab<T, BM>::PAIR];  // AS_AT(buf, k, m) = -+A[k][m]
+    __shared__ T Bs[2][BK][BN + LPAD];
+    int tile_m, tile_n;
+    grouped_tile((int)blockIdx.x, tiles_m * tiles_n, tiles_m, tiles_n, tile_m, tile_n);
+    gemm_sub_tile<T, FULL, NWN, BM, true>(M, N, K, A, lda, B, ldb, C, ldc, (tile_m + tm_off) * BM, (tile_n + tn_off) * BN, As,
+                                          Bs, plus & 3);
 }
 
 // The same interior tiles handed out by a work queue instead of one workgroup per tile: the look-ahead driver
@@ -489,6 +533,37 @@ int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, i
     return LSX_OK;
 }
 
+// mode: 0  C -= A^T B,  1  C += A^T B,  3  C = A^T B  (C is not read).  A: k x m.  Every n takes the MFMA tile, so a
+// column of C has the same bits whatever the other columns of the call are.
+template <typename T>
+int launch_gemm_tn_acc(lsx_handle_t h, int mode, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C,
+                       int ldc) {
+    if (m <= 0 || n <= 0 || (k <= 0 && mode != 3)) return LSX_OK;
+    if (k < 0) k = 0;
+    ProfScope ps(h, LSX_PROF_GEMM, 2.0 * m * n * (double)k, (mode == 3 ? 1.0 : 2.0) * sizeof(T) * m * (double)n);
+    const int tm = (m + BM - 1) / BM, tn = (n + BN - 1) / BN;
+    const int elems16 = 16 / (int)sizeof(T);
+    const bool aligned = ((size_t)A % 16 == 0) && ((size_t)B % 16 == 0) && ((size_t)C % 16 == 0) && (lda % elems16 == 0) &&
+                         (ldb % elems16 == 0) && (ldc % elems16 == 0) && (k % BK == 0) && k > 0;
+    const int fm = aligned ? m / BM : 0, fn = aligned ? n / BN : 0;  // complete tiles
+    constexpr int NWN = sizeof(T) == 8 ? 4 : 2;   // the trailing update's default forms: 8 waves in fp64, 4 in fp32
+    auto go = [&](bool full, int gm, int gn, int om, int on) {
+        if (gm <= 0 || gn <= 0) return;
+        if (full) hipLaunchKernelGGL((gemm_tn_kernel<T, NWN, true>), dim3(gm * gn), dim3(BM * NWN), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, mode);
+        else hipLaunchKernelGGL((gemm_tn_kernel<T, NWN, false>), dim3(gm * gn), dim3(BM * NWN), 0, h->stream, m, n, k, A, lda, B, ldb, C, ldc, gm, gn, om, on, mode);
+    };
+    go(true, fm, fn, 0, 0);              // interior
+    go(false, tm - fm, tn, fm, 0);       // bottom strip (all columns)
+    go(false, fm, tn - fn, 0, fn);       // right strip (complete tile rows only)
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
+}
+
+template <typename T>
+int launch_gemm_tn_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C, int ldc) {
+    return launch_gemm_tn_acc<T>(h, 0, m, n, k, A, lda, B, ldb, C, ldc);
+}
+
 template <typename T>
 int launch_gemm_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C,
                     int ldc, const GemmPlan &plan, GemmDone *done) {
@@ -499,6 +574,10 @@ template int launch_gemm_acc<double>(lsx_handle_t, int, int, int, int, const dou
                                      int, double *, int, const GemmPlan &, GemmDone *);
 template int launch_gemm_acc<float>(lsx_handle_t, int, int, int, int, const float *, int, const float *, int,
                                     float *, int, const GemmPlan &, GemmDone *);
+template int launch_gemm_tn_acc<double>(lsx_handle_t, int, int, int, int, const double *, int, const double *, int, double *, int);
+template int launch_gemm_tn_acc<float>(lsx_handle_t, int, int, int, int, const float *, int, const float *, int, float *, int);
+template int launch_gemm_tn_sub<double>(lsx_handle_t, int, int, int, const double *, int, const double *, int, double *, int);
+template int launch_gemm_tn_sub<float>(lsx_handle_t, int, int, int, const float *, int, const float *, int, float *, int);
 template int launch_gemm_sub<double>(lsx_handle_t, int, int, int, const double *, int,
                                      const double *, int, double *, int, const GemmPlan &, GemmDone *);
 template int launch_gemm_sub<float>(lsx_handle_t, int, int, int, const float *, int, const float *,

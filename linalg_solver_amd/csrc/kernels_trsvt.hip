@@ -12,6 +12,9 @@
 //                the partial sums of the row groups go through LDS.  The workgroup that owns the NEXT block then
 //                applies inv(T_next)^T with the same routine: the 128 x 128 inverses are stored in their natural
 //                orientation for this solve (merge128_kernel, natural = 1), so inv^T b is again "row by row".
+//                These kernels serve up to getrs_t_blocked_min - 1 right-hand sides in groups of 8 columns; from there on
+//                api.hip runs the same sweeps blocked on the TN form of the MFMA tile (lu_solve_transposed_blocked) and only
+//                the final row scatter (scatter_rows_kernel) lives here.
 //   trsvt_small  n <= 128: one workgroup, the factors in LDS, plain substitution, interchanges included.
 //   Summation order is fixed everywhere (rows ascending inside a thread, then the row groups ascending): two calls
 //   give identical bits.
@@ -154,6 +157,26 @@ __global__ __launch_bounds__(256) void trsvt_scatter_kernel(int n, int NR, int w
     const int p = perm[i];
     if (q < w && p >= 0 && p < n) X[(size_t)p * ldx + c0 + q] = W[e];
 }
+
+// The same scatter for a whole right-hand-side block (blocked path): one workgroup per row, lanes along the row
+template <typename T>
+__global__ __launch_bounds__(256) void scatter_rows_kernel(int n, int ncols, const int32_t *__restrict__ perm,
+                                                           const T *__restrict__ W, int ldw, T *__restrict__ X, int ldx) {
+    const int i = blockIdx.x;
+    const int p = perm[i];
+    if (p < 0 || p >= n) return;
+    for (int q = threadIdx.x; q < ncols; q += 256) X[(size_t)p * ldx + q] = W[(size_t)i * ldw + q];
+}
+
+template <typename T>
+int launch_scatter_rows(lsx_handle_t h, int n, int ncols, const int32_t *d_perm, const T *W, int ldw, T *X, int ldx) {
+    if (n <= 0 || ncols <= 0) return LSX_OK;
+    hipLaunchKernelGGL(scatter_rows_kernel<T>, dim3(n), dim3(256), 0, h->stream, n, ncols, d_perm, W, ldw, X, ldx);
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
+}
+template int launch_scatter_rows<double>(lsx_handle_t, int, int, const int32_t *, const double *, int, double *, int);
+template int launch_scatter_rows<float>(lsx_handle_t, int, int, const int32_t *, const float *, int, float *, int);
 
 // n <= 128, columns [c0, c0 + w) of B with w <= NR: the factors in LDS (dynamic, n x 128 elements), thread (c, hf)
 // keeps entry c of every second column in registers.  Step i hands y_i to the others through a two-slot LDS buffer:

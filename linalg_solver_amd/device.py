@@ -199,6 +199,30 @@ class DeviceSolver:
                                               B.stride(0), C.data_ptr(), C.stride(0)), "gemm_add_dev")
         return C
 
+    def _gemm_tn(self, name: str, C: torch.Tensor, A: torch.Tensor, B: torch.Tensor):
+        for t, w in ((C, "C"), (A, "A"), (B, "B")):
+            _rowmajor(t, name + "_ " + w)
+        k, m = A.shape
+        n = B.shape[1]
+        if B.shape[0] != k or tuple(C.shape) != (m, n):
+            raise ValueError(f"{name}_: need A (k x m), B (k x n) and C (m x n)")
+        if not (A.dtype == B.dtype == C.dtype):
+            raise TypeError(f"{name}_: all operands must have the same dtype")
+        fn = getattr(self.lib, f"lsx_{name}_{self._suffix(C)}_dev")
+        N.check(fn(self.h.ptr, m, n, k, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(),
+                   C.stride(0)), name + "_dev")
+        return C
+
+    def gemm_tn_sub_(self, C: torch.Tensor, A: torch.Tensor, B: torch.Tensor):
+        """C -= A.T @ B with A stored k x m (a block row of the factors), on the MFMA kernel; fp64 or fp32."""
+        return self._gemm_tn("gemm_tn_sub", C, A, B)
+
+    def gemm_tn_add_(self, C: torch.Tensor, A: torch.Tensor, B: torch.Tensor):
+        """C += A.T @ B (fp64) on the same kernel."""
+        if C.dtype != torch.float64:
+            raise TypeError("gemm_tn_add_ takes fp64 operands")
+        return self._gemm_tn("gemm_tn_add", C, A, B)
+
     def panel_(self, P: torch.Tensor, row0: int, ipiv: torch.Tensor, info: torch.Tensor):
         _rowmajor(P, "panel_")
         N.check(self.lib.lsx_panel_f64_dev(self.h.ptr, P.shape[0], P.shape[1], P.data_ptr(), P.stride(0), row0,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | gecon | gerfs [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | gecon | gerfs [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -380,6 +380,42 @@ def main():
                     print(f"solve {str(dt)[6:]} n={n} nrhs={nrhs}: " + "  ".join(
                         f"{k} {min(v) * 1e3:.1f} us (rounds {v[0] * 1e3:.1f} / {v[1] * 1e3:.1f}; {by / min(v) / 1e-3 / HBM * 100:.1f} % of HBM)"
                         for k, v in res.items()), flush=True)
+    if "getrs_t" in args.what:
+        # many right-hand sides: the transposed solve in groups of 8 columns (getrs_t_blocked_min = 0), its blocked
+        # sweeps on the TN form of the MFMA tile (= 1), and the plain solve of the same shape -- the same flops on
+        # the same tile with the NN kernel: the yardstick.  Medians of two alternating rounds, the copy that restores
+        # the right-hand sides subtracted.
+        dt = torch.float64
+        for n in (1024, 4096, 8192):
+            A = torch.empty(n, n, dtype=dt, device="cuda")
+            dev.fill_(A, gen.U11, 1)
+            ipiv, info = dev.getrf_(A)
+            for nrhs in (8, 16, 32, 64, 128, 256, 1024):
+                B0 = torch.empty(n, nrhs, dtype=dt, device="cuda")
+                dev.fill_(B0, gen.U11, 2)
+                B = B0.clone()
+                reps = 5 if n * nrhs >= 4096 * 256 else 11
+                res, paths = {}, {}
+                for rnd in range(2):
+                    t_copy = timeit(lambda: B.copy_(B0), reps=reps, warm=1)[1]
+                    for name, trans, opt in (("grouped", True, 0), ("blocked", True, 1), ("plain", False, None)):
+                        if opt is not None:
+                            dev.h.set_option("getrs_t_blocked_min", opt)
+
+                        def run():
+                            B.copy_(B0)
+                            dev.getrs_(A, ipiv, B, trans=trans)
+                        res.setdefault(name, []).append(timeit(run, reps=reps, warm=1)[1] - t_copy)
+                        if trans:
+                            paths[name] = dev.h.get_option("getrs_t_path")
+                assert paths == {"grouped": 0, "blocked": 1}, paths
+                g, b, pl = (min(res[k]) for k in ("grouped", "blocked", "plain"))
+                fl = 2.0 * n * n * nrhs
+                print(f"getrs_t f64 n={n} nrhs={nrhs}: grouped {g:.3f} ms  blocked {b:.3f} ms ({fl / b / 1e9:.1f} TFLOP/s)  "
+                      f"plain {pl:.3f} ms  | grouped/blocked {g / b:.2f}  blocked/plain {b / pl:.2f}  "
+                      f"(rounds: grouped {res['grouped'][0]:.3f}/{res['grouped'][1]:.3f} blocked {res['blocked'][0]:.3f}/"
+                      f"{res['blocked'][1]:.3f} plain {res['plain'][0]:.3f}/{res['plain'][1]:.3f})", flush=True)
+        dev.h.set_option("getrs_t_blocked_min", 64)
     if "gecon" in args.what:
         # the condition estimate beside the factorisation it follows (fp64, 1-norm; medians)
         for n in (1024, 4096, 8192):
