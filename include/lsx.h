@@ -249,7 +249,7 @@ int lsx_rcond_f32(lsx_handle_t h, int norm, int n, const float *A, int lda, doub
 /* trans: 0 = A X = B, 1 = A^T X = B.  A is the UNFACTORED matrix, LU / ipiv its factors from lsx_getrf_*.
  * X holds a solution on entry (from lsx_getrs_* / lsx_getrs_t_*) and the refined one on return; ferr[nrhs] and
  * berr[nrhs] are host doubles in all forms (the host drives the iteration and reads one small record per step: all
- * forms synchronise the handle's stream).  No equilibration, no scaling: dgerfs.f step for step.
+ * forms synchronise the handle's stream).  No equilibration, no scaling: dgerfs.f step for step (lsx_gesvx_* equilibrates).
  *   berr[j] = max_i |r_i| / w_i with r = b - op(A) x and w = |b| + |op(A)| |x| (guarded as in dgerfs where w_i is
  *     below safe2 = (n + 1) safmin / u): the componentwise backward error of the returned column.  r and w come
  *     from ONE pass over A for up to 8 right-hand sides, accumulated in fp64 (fp32 data: converted on load, rounded
@@ -292,6 +292,81 @@ int lsx_diag_resid_bound_f32_dev(lsx_handle_t h, int trans, int n, int nrhs, con
                                  int ldb, const float *dX, int ldx, float *dR, float *dW, int ldr);
 int lsx_diag_resid_mixed_dev(lsx_handle_t h, int n, int nrhs, const float *dA, int lda, const float *dB, int ldb,
                              const double *dX, int ldx, float *dR, int ldr);
+
+/* ---- equilibration and the expert driver (LAPACK's geequ, laqge, gesvx) ---- */
+/* Which sides of the matrix lsx_laqge_* / lsx_gesvx_* scaled: A_eq = diag(r) A diag(c) with r or c taken as 1 on a side
+ * that was left alone (LAPACK's equed 'N', 'R', 'C', 'B'). */
+enum { LSX_EQUED_NONE = 0, LSX_EQUED_ROW = 1, LSX_EQUED_COL = 2, LSX_EQUED_BOTH = 3 };
+/* Row and column scale factors of the m x n matrix at dA (device pointer), dgeequ.f / sgeequ.f step for step in the
+ * working precision: r_i = 1 / min(max(max_j |a_ij|, smlnum), bignum), c_j = 1 / min(max(max_i |a_ij| r_i, smlnum),
+ * bignum) with smlnum = lamch('S'), bignum = 1 / smlnum; d_r (m entries) and d_c (n entries) are device arrays of the
+ * matrix's type.  d_stats (device, 4 doubles) = {rowcnd, colcnd, amax, info}: the ratios smallest / largest r_i and
+ * c_j, the largest |a_ij|, and LAPACK's info -- i (1-based) for the first exactly zero row, m + j for the first zero
+ * column of the row-scaled matrix; with info != 0 the contents of d_r / d_c are unspecified and the ratios that were
+ * not reached are 0.  r, c, rowcnd, colcnd and amax equal LAPACK's bit for bit (maxima, products and one IEEE division
+ * per factor; nothing depends on an order of summation, on lda or on alignment).  A NaN entry gives amax = NaN.
+ * m == 0 or n == 0 gives rowcnd = colcnd = 1, amax = 0, info = 0.  The matrix is streamed twice (rows, then columns),
+ * each pass followed by one small launch; no atomics.  Arguments are validated like lsx_lange_*_dev.  Asynchronous. */
+int lsx_geequ_f64_dev(lsx_handle_t h, int m, int n, const double *dA, int lda, double *d_r, double *d_c, double *d_stats);
+int lsx_geequ_f32_dev(lsx_handle_t h, int m, int n, const float *dA, int lda, float *d_r, float *d_c, double *d_stats);
+/* Measurement hook (tools/kbench.py): passes = 1 runs the row pass of lsx_geequ_* and its final step alone, 2 the column
+ * pass and its (d_r and d_stats from a row pass), 3 both. */
+int lsx_diag_geequ_pass_f64_dev(lsx_handle_t h, int passes, int m, int n, const double *dA, int lda, double *d_r,
+                                double *d_c, double *d_stats);
+int lsx_diag_geequ_pass_f32_dev(lsx_handle_t h, int passes, int m, int n, const float *dA, int lda, float *d_r,
+                                float *d_c, double *d_stats);
+/* dlaqge.f / slaqge.f: scale the matrix at dA in place if the factors say it is worth it.  rowcnd, colcnd, amax are HOST
+ * scalars (read back from d_stats) and the decision is made on the host: with thresh = 0.1, small = lamch('S') /
+ * lamch('P') and large = 1 / small, rows are scaled unless rowcnd >= thresh and small <= amax <= large, columns unless
+ * colcnd >= thresh.  *equed (host int) receives LSX_EQUED_*; then ONE launch -- a_ij <- r_i a_ij, c_j a_ij or
+ * (c_j r_i) a_ij, dlaqge's association, so the scaled matrix has LAPACK's bits -- or none.  Asynchronous. */
+int lsx_laqge_f64_dev(lsx_handle_t h, int m, int n, double *dA, int lda, const double *d_r, const double *d_c,
+                      double rowcnd, double colcnd, double amax, int *equed);
+int lsx_laqge_f32_dev(lsx_handle_t h, int m, int n, float *dA, int lda, const float *d_r, const float *d_c,
+                      double rowcnd, double colcnd, double amax, int *equed);
+/* The expert driver, dgesvx.f step for step: equil = 0 is LAPACK's fact = 'N', 1 is fact = 'E'; trans as in
+ * lsx_gerfs_*.  A and B are not modified (the contract of lsx_gesvr_*).
+ *   1. equil: geequ; if its info is 0 and amax is no NaN, laqge decides and scales; otherwise *equed = LSX_EQUED_NONE.
+ *   2. B is scaled by r (trans = 0, rows equilibrated) or by c (trans = 1, columns equilibrated).
+ *   3. A copy of the equilibrated matrix is factored.  *info in 1..n (an exactly zero pivot): *rpvgrw is taken over
+ *      the leading *info columns, *rcond = 0, ferr = berr = +inf, X is not written.
+ *   4. anorm = the 1-norm (trans = 0) or the infinity-norm (trans = 1) of the equilibrated matrix (computed and read
+ *      back before step 3, so that a NaN in A is seen before anything is factored).
+ *   5. *rpvgrw = max |A_eq| / max |U|, the reciprocal pivot growth (1 when max |U| is 0), in the working precision.
+ *   6. *rcond from lsx_gecon_*: the condition of the EQUILIBRATED matrix in that norm.
+ *   7. Solve, refine and bound as lsx_gerfs_*, then X is scaled by c (trans = 0, columns equilibrated) or by r (trans = 1,
+ *      rows equilibrated): X solves the system that was passed in.
+ *   8. ferr is divided by colcnd (trans = 0, columns equilibrated) or by rowcnd (trans = 1, rows equilibrated).  This is
+ *      LAPACK's contract and it can make the bound vacuous: on matrices whose columns span 2^-30 .. 2^30 colcnd is about
+ *      1e-17 and ferr comes out as 9e3 .. 1.4e8 although the solution is accurate; berr is not affected.
+ *   9. *info = n + 1 if *rcond < u (2^-53 / 2^-24): singular to working precision; X and the bounds are still returned.
+ * r and c (n entries each, of the matrix's type) are written when equil = 1 and geequ's info is 0, else left untouched
+ * (they are written, and nothing is scaled, when amax is NaN).
+ * nrhs == 0 is valid and returns *equed, r, c, *rcond and *rpvgrw: the condition number of a badly scaled matrix.
+ * n == 0: *rcond = 1, *rpvgrw = 1, *equed = LSX_EQUED_NONE.  A NaN in A (it shows in anorm; with equil = 1 also in amax):
+ * nothing is factored, *equed = LSX_EQUED_NONE, *rcond = *rpvgrw = NaN, ferr = berr = NaN, every entry of X is set to NaN
+ * (no output is left unwritten behind *info = 0; a caller tests *rcond for NaN), *info = 0.  This is the one input on
+ * which equil = 0 does not follow lsx_gesvr_* (+inf bounds from the NaN pivot) and lsx_rcond_*.
+ * A NaN in a column of B: ferr = berr = NaN for that column, as in lsx_gerfs_*.  With equil = 0 the results have the bits
+ * of lsx_gesvr_* (X, ferr, berr) and of lsx_rcond_* (*rcond); so they have with equil = 1 when nothing is scaled.
+ * Numerical outcomes are values, not statuses; a time-out of a cooperative solve inside is LSX_ERR_INTERNAL. */
+int lsx_gesvx_f64(lsx_handle_t h, int equil, int trans, int n, int nrhs, const double *A, int lda, const double *B,
+                  int ldb, double *X, int ldx, int *equed, double *r, double *c, double *rcond, double *ferr,
+                  double *berr, double *rpvgrw, int *info);
+int lsx_gesvx_f32(lsx_handle_t h, int equil, int trans, int n, int nrhs, const float *A, int lda, const float *B,
+                  int ldb, float *X, int ldx, int *equed, float *r, float *c, double *rcond, double *ferr, double *berr,
+                  double *rpvgrw, int *info);
+/* The same on device pointers with LAPACK's in / out contract: dA returns the equilibrated matrix, dB the scaled
+ * right-hand sides, dLU (n x n, ldlu) / d_ipiv the factors of the equilibrated matrix, dX the solution of the system as
+ * passed in, d_r / d_c (required when equil = 1) geequ's factors -- so a caller can go on with lsx_getrs_*_dev /
+ * lsx_gerfs_*_dev on the equilibrated system.  *equed, *rowcnd, *colcnd (may be NULL), *rcond, ferr, berr, *rpvgrw and
+ * *info are host variables.  Synchronises the handle's stream, as lsx_gecon_* and lsx_gerfs_* do. */
+int lsx_gesvx_f64_dev(lsx_handle_t h, int equil, int trans, int n, int nrhs, double *dA, int lda, double *dLU, int ldlu,
+                      int32_t *d_ipiv, double *dB, int ldb, double *dX, int ldx, int *equed, double *d_r, double *d_c,
+                      double *rowcnd, double *colcnd, double *rcond, double *ferr, double *berr, double *rpvgrw, int *info);
+int lsx_gesvx_f32_dev(lsx_handle_t h, int equil, int trans, int n, int nrhs, float *dA, int lda, float *dLU, int ldlu,
+                      int32_t *d_ipiv, float *dB, int ldb, float *dX, int ldx, int *equed, float *d_r, float *d_c,
+                      double *rowcnd, double *colcnd, double *rcond, double *ferr, double *berr, double *rpvgrw, int *info);
 
 /* ---- device-pointer entry points (asynchronous on the handle's stream) ---- */
 /* d_info: device int (may be NULL).  d_ipiv: device int32[n].

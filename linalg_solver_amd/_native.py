@@ -17,6 +17,7 @@ PROF_BUCKETS = {"panel": 0, "laswp": 1, "trsm": 2, "gemm": 3, "other": 4, "gemm_
 FILL_INT5, FILL_U11 = 0, 1
 PIVOT_FIRST, PIVOT_MAX = 0, 1
 NORM_ONE, NORM_INF = 0, 1
+EQUED_NONE, EQUED_ROW, EQUED_COL, EQUED_BOTH = 0, 1, 2, 3
 
 
 class LsxError(RuntimeError):
@@ -81,6 +82,20 @@ _SIGS = {
     "lsx_gerfs_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _dp, _dp],
     "lsx_gesvr_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, C.POINTER(_i)],
     "lsx_gesvr_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, _dp, _dp, C.POINTER(_i)],
+    "lsx_geequ_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "lsx_geequ_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "lsx_diag_geequ_pass_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "lsx_diag_geequ_pass_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "lsx_laqge_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, C.c_double, C.c_double, C.POINTER(_i)],
+    "lsx_laqge_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, C.c_double, C.c_double, C.POINTER(_i)],
+    "lsx_gesvx_f64": [_vp, _i, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, C.POINTER(_i), _dp, _dp, _dp, _dp, _dp, _dp,
+                      C.POINTER(_i)],
+    "lsx_gesvx_f32": [_vp, _i, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, C.POINTER(_i), _fp, _fp, _dp, _dp, _dp, _dp,
+                      C.POINTER(_i)],
+    "lsx_gesvx_f64_dev": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, C.POINTER(_i), _vp, _vp, _dp, _dp,
+                          _dp, _dp, _dp, _dp, C.POINTER(_i)],
+    "lsx_gesvx_f32_dev": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, C.POINTER(_i), _vp, _vp, _dp, _dp,
+                          _dp, _dp, _dp, _dp, C.POINTER(_i)],
     "lsx_diag_resid_bound_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i],
     "lsx_diag_resid_bound_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i],
     "lsx_diag_resid_mixed_dev": [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i],

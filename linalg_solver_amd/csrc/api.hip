@@ -1263,6 +1263,215 @@ static int rcond_host(lsx_handle_t h, int norm, int n, const T *A, int lda, doub
     return gecon_dev<T>(h, norm, n, dA, ld, dp, anorm, rcond);
 }
 
+// ---------------------------------------------------------------- equilibration and the expert driver (gesvx)
+template <typename T> struct LaqgeLim;   // dlaqge's small = safmin / prec with prec = eps * base; large = 1 / small
+template <> struct LaqgeLim<double> { static constexpr double small_ = 0x1p-970, large_ = 0x1p+970; };
+template <> struct LaqgeLim<float> { static constexpr double small_ = 0x1p-103, large_ = 0x1p+103; };
+
+template <typename T>
+static int d2d(lsx_handle_t h, int m, int n, const T *src, int lds, T *dst, int ldd) {
+    if (m <= 0 || n <= 0) return LSX_OK;
+    LSX_HIP(hipMemcpy2DAsync(dst, (size_t)ldd * sizeof(T), src, (size_t)lds * sizeof(T), (size_t)n * sizeof(T), m,
+                             hipMemcpyDeviceToDevice, h->stream));
+    return LSX_OK;
+}
+
+// ws9: 256 bytes of records in front (the drivers'), then the work area of one reduction
+static int ensure_equil_ws(lsx_handle_t h, size_t work) {
+    if (256 + work > h->ws9_bytes) LSX_HIP(hipStreamSynchronize(h->stream));   // growing frees the old block
+    return grow(&h->ws9, &h->ws9_bytes, 256 + work);
+}
+
+// LAPACK's geequ on device data; asynchronous
+template <typename T>
+static int geequ_dev(lsx_handle_t h, int m, int n, const T *dA, int lda, T *d_r, T *d_c, double *d_stats, int passes = 3) {
+    LSX_ARG(m >= 0 && n >= 0 && lda >= n && d_stats && passes >= 1 && passes <= 3);
+    LSX_ARG(m == 0 || n == 0 || (dA && d_r && d_c));
+    LSX_TRY(ensure_equil_ws(h, geequ_work_bytes(m, n, sizeof(T))));
+    return launch_geequ<T>(h, m, n, dA, lda, d_r, d_c, d_stats, (char *)h->ws9 + 256, passes);
+}
+
+// dlaqge's decision from the three scalars of geequ (values of the working precision held in doubles)
+template <typename T>
+static int laqge_decide(double rowcnd, double colcnd, double amax) {
+    const double thresh = 0.1;
+    const bool rows = !(rowcnd >= thresh && amax >= LaqgeLim<T>::small_ && amax <= LaqgeLim<T>::large_);
+    const bool cols = !(colcnd >= thresh);
+    return (rows ? LSX_EQUED_ROW : 0) | (cols ? LSX_EQUED_COL : 0);
+}
+
+// LAPACK's laqge on device data: one scaling launch or none; dCopy (may be null) receives the scaled matrix too when
+// there is a launch.  Asynchronous.
+template <typename T>
+static int laqge_dev(lsx_handle_t h, int m, int n, T *dA, int lda, const T *d_r, const T *d_c, double rowcnd,
+                     double colcnd, double amax, int *equed, T *dCopy = nullptr, int ldc = 0) {
+    LSX_ARG(m >= 0 && n >= 0 && lda >= n && equed);
+    *equed = LSX_EQUED_NONE;
+    if (m == 0 || n == 0) return LSX_OK;
+    LSX_ARG(dA && d_r && d_c);
+    const int e = laqge_decide<T>(rowcnd, colcnd, amax);
+    *equed = e;
+    return launch_laqge<T>(h, m, n, dA, lda, (e & LSX_EQUED_ROW) ? d_r : nullptr, (e & LSX_EQUED_COL) ? d_c : nullptr,
+                           dCopy, ldc);
+}
+
+// What gesvx_dev tells the host-buffer form beyond LAPACK's outputs.
+struct GesvxDone {
+    bool scales = false;   // d_r / d_c hold geequ's factors (equil and geequ's info == 0)
+    bool solved = false;   // dX was written: a solution, or NaN throughout for a matrix with a NaN
+};
+
+// LAPACK's gesvx (dgesvx.f step for step, fact = 'N' / 'E') on device data with LAPACK's in / out contract: dA leaves
+// equilibrated, dB scaled, dLU / d_ipiv hold the factors of the equilibrated matrix.  Every scalar result is a host
+// variable; the host reads a small record after geequ, after the factorisation and inside gecon / gerfs, so this
+// synchronises the handle's stream.
+template <typename T>
+static int gesvx_dev(lsx_handle_t h, int equil, int trans, int n, int nrhs, T *dA, int lda, T *dLU, int ldlu,
+                     int32_t *d_ipiv, T *dB, int ldb, T *dX, int ldx, T *d_r, T *d_c, int *equed, double *rowcnd_out,
+                     double *colcnd_out, double *rcond, double *ferr, double *berr, double *rpvgrw, int *info,
+                     GesvxDone *done = nullptr) {
+    LSX_ARG((equil == 0 || equil == 1) && (trans == 0 || trans == 1) && n >= 0 && nrhs >= 0 && lda >= n && ldlu >= n &&
+            ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(equed && rcond && rpvgrw && info && (nrhs == 0 || (ferr && berr)));
+    *equed = LSX_EQUED_NONE;
+    *rcond = 1.0;
+    *rpvgrw = 1.0;
+    *info = 0;
+    if (rowcnd_out) *rowcnd_out = 1.0;
+    if (colcnd_out) *colcnd_out = 1.0;
+    h->gerfs_steps = 0;
+    h->gerfs_solves = 0;
+    h->gecon_solves = 0;
+    for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = 0.0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(dA && dLU && d_ipiv && (nrhs == 0 || (dB && dX)) && (equil == 0 || (d_r && d_c)));
+    const int norm = trans ? LSX_NORM_INF : LSX_NORM_ONE;
+    LSX_TRY(ensure_equil_ws(h, std::max(geequ_work_bytes(n, n, sizeof(T)), maxabs_work_bytes(n))));
+    // records: [0..4) geequ's stats, [4] anorm, [5] max |A|, [6] max |U|, then the factorisation's info word
+    double *rec = (double *)h->ws9, *work = (double *)((char *)h->ws9 + 256);
+    int *dinfo = (int *)(rec + 8);
+    double hrec[8] = {1, 1, 0, 0, 0, 0, 0, 0};
+    double rowcnd = 1.0, colcnd = 1.0;
+    bool copied = false;                                             // dLU holds a copy of the (equilibrated) matrix
+    if (equil) {
+        LSX_TRY(geequ_dev<T>(h, n, n, dA, lda, d_r, d_c, rec));
+        LSX_HIP(hipMemcpyAsync(hrec, rec, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        if (hrec[3] == 0.0 && done) done->scales = true;             // geequ's info == 0: r and c are handed out
+        if (hrec[3] == 0.0 && hrec[2] == hrec[2]) {                  // ... and amax is no NaN: laqge decides
+            rowcnd = hrec[0];
+            colcnd = hrec[1];
+            LSX_TRY(laqge_dev<T>(h, n, n, dA, lda, d_r, d_c, rowcnd, colcnd, hrec[2], equed, dLU, ldlu));
+            copied = *equed != LSX_EQUED_NONE;
+        }
+    }
+    if (rowcnd_out) *rowcnd_out = rowcnd;
+    if (colcnd_out) *colcnd_out = colcnd;
+    const bool rowequ = (*equed & LSX_EQUED_ROW) != 0, colequ = (*equed & LSX_EQUED_COL) != 0;
+    if (nrhs > 0) {
+        if (!trans && rowequ) LSX_TRY(launch_laqge<T>(h, n, nrhs, dB, ldb, d_r, nullptr, nullptr, 0));
+        if (trans && colequ) LSX_TRY(launch_laqge<T>(h, n, nrhs, dB, ldb, d_c, nullptr, nullptr, 0));
+    }
+    // the norm first: a NaN in the matrix shows in it, and such a matrix is not factored at all
+    LSX_TRY(lange_dev<T>(h, norm, n, n, dA, lda, rec + 4));
+    LSX_HIP(hipMemcpyAsync(hrec + 4, rec + 4, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    const double anorm = hrec[4];
+    if (anorm != anorm) {                                            // no output is left unwritten: X is all NaN
+        *rcond = *rpvgrw = NAN;
+        for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = NAN;
+        if (nrhs > 0) {
+            LSX_HIP(hipMemset2DAsync(dX, (size_t)ldx * sizeof(T), 0xFF, (size_t)nrhs * sizeof(T), n, h->stream));
+            if (done) done->solved = true;
+        }
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        return LSX_OK;
+    }
+    int hinfo = 0;
+    for (int attempt = 0;; ++attempt) {                              // as factor_from_host: per-column panels after a time-out
+        if (!copied) LSX_TRY(d2d<T>(h, n, n, dA, lda, dLU, ldlu));
+        copied = false;
+        LSX_TRY(getrf_dev<T>(h, n, dLU, ldlu, d_ipiv, dinfo, attempt == 1));
+        if (attempt == 1) h->panel_fallbacks += 1;
+        LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        if (hinfo >= 0) break;
+        LSX_HIP(hipMemsetAsync(h->dev_status, 0, 3 * sizeof(int), h->stream));
+        if (attempt == 1) {
+            set_error("panel exchange timed out on the device, and so did the per-column fallback");
+            return LSX_ERR_INTERNAL;
+        }
+    }
+    // reciprocal pivot growth max |A| / max |U|, over the leading info columns when the factorisation broke down
+    const int k = hinfo > 0 ? hinfo : n;
+    LSX_TRY(launch_maxabs<T>(h, n, k, dA, lda, 0, work, rec + 5));
+    LSX_TRY(launch_maxabs<T>(h, k, k, dLU, ldlu, 1, work, rec + 6));
+    LSX_HIP(hipMemcpyAsync(hrec + 5, rec + 5, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    *rpvgrw = hrec[6] == 0.0 ? 1.0 : (double)((T)hrec[5] / (T)hrec[6]);
+    *info = hinfo;
+    if (hinfo > 0) {
+        *rcond = 0.0;
+        for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = INFINITY;
+        return LSX_OK;
+    }
+    LSX_TRY(gecon_dev<T>(h, norm, n, dLU, ldlu, d_ipiv, anorm, rcond));
+    if (nrhs > 0) {
+        LSX_TRY(d2d<T>(h, n, nrhs, dB, ldb, dX, ldx));
+        if (trans) LSX_TRY(getrs_t_dev<T>(h, n, nrhs, dLU, ldlu, d_ipiv, dX, ldx, true));
+        else LSX_TRY(getrs_dev<T>(h, n, nrhs, dLU, ldlu, d_ipiv, dX, ldx));
+        LSX_TRY(gerfs_dev<T>(h, trans, n, nrhs, dA, lda, dLU, ldlu, d_ipiv, dB, ldb, dX, ldx, ferr, berr));
+        if (!trans && colequ) {
+            LSX_TRY(launch_laqge<T>(h, n, nrhs, dX, ldx, d_c, nullptr, nullptr, 0));
+            for (int j = 0; j < nrhs; ++j) ferr[j] /= colcnd;
+        } else if (trans && rowequ) {
+            LSX_TRY(launch_laqge<T>(h, n, nrhs, dX, ldx, d_r, nullptr, nullptr, 0));
+            for (int j = 0; j < nrhs; ++j) ferr[j] /= rowcnd;
+        }
+        if (done) done->solved = true;
+    }
+    if (*rcond < Lamch<T>::u) *info = n + 1;
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+// host buffers: A and B are kept, X receives the solution, r / c the scale factors geequ chose
+template <typename T>
+static int gesvx_host(lsx_handle_t h, int equil, int trans, int n, int nrhs, const T *A, int lda, const T *B, int ldb,
+                      T *X, int ldx, int *equed, T *r, T *c, double *rcond, double *ferr, double *berr, double *rpvgrw,
+                      int *info) {
+    LSX_ARG(h && (equil == 0 || equil == 1) && (trans == 0 || trans == 1) && n >= 0 && nrhs >= 0 && lda >= n &&
+            ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(equed && rcond && rpvgrw && info && (nrhs == 0 || (ferr && berr)));
+    if (n == 0)
+        return gesvx_dev<T>(h, equil, trans, 0, nrhs, nullptr, lda, nullptr, lda, nullptr, nullptr, ldb, nullptr, ldx,
+                            nullptr, nullptr, equed, nullptr, nullptr, rcond, ferr, berr, rpvgrw, info);
+    LSX_ARG(A && (nrhs == 0 || (B && X)) && (equil == 0 || (r && c)));
+    const int ld = ld_for(n), ldr = ld_for(nrhs > 0 ? nrhs : 1);
+    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) +
+                             pad256(sizeof(int32_t) * n) + 2 * pad256(sizeof(T) * (size_t)n) + 1024));
+    Carver cv(h->ws);
+    T *dA = cv.take<T>((size_t)n * ld);
+    T *dLU = cv.take<T>((size_t)n * ld);
+    T *dB = cv.take<T>((size_t)n * ldr);
+    T *dX = cv.take<T>((size_t)n * ldr);
+    int32_t *dp = cv.take<int32_t>(n);
+    T *dr = cv.take<T>(n);
+    T *dc = cv.take<T>(n);
+    LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
+    if (nrhs > 0) LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
+    GesvxDone done;
+    LSX_TRY(gesvx_dev<T>(h, equil, trans, n, nrhs, dA, ld, dLU, ld, dp, dB, ldr, dX, ldr, dr, dc, equed, nullptr, nullptr,
+                         rcond, ferr, berr, rpvgrw, info, &done));
+    if (done.scales) {
+        LSX_HIP(hipMemcpyAsync(r, dr, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        LSX_HIP(hipMemcpyAsync(c, dc, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (done.solved) LSX_TRY(d2h<T>(h, n, nrhs, dX, ldr, X, ldx));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
 }  // namespace lsx
 
 using namespace lsx;
@@ -1355,6 +1564,7 @@ int lsx_destroy(lsx_handle_t h) {
     if (h->ws6) (void)hipFree(h->ws6);
     if (h->ws7) (void)hipFree(h->ws7);
     if (h->ws8) (void)hipFree(h->ws8);
+    if (h->ws9) (void)hipFree(h->ws9);
     if (h->xchg) (void)hipFree(h->xchg);
     if (h->ws5) (void)hipFree(h->ws5);
     if (h->scratch) (void)hipFree(h->scratch);
@@ -1995,6 +2205,44 @@ int lsx_rcond_f32(lsx_handle_t h, int norm, int n, const float *A, int lda, doub
     LSX_DEVICE_GUARD(h);
     return rcond_host<float>(h, norm, n, A, lda, rcond, info);
 }
+
+// ---- equilibration and the expert driver
+#define LSX_GESVX_ABI(sfx, T)                                                                                              \
+    int lsx_geequ_##sfx##_dev(lsx_handle_t h, int m, int n, const T *dA, int lda, T *d_r, T *d_c, double *d_stats) {       \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        LSX_ARG(h);                                                                                                        \
+        return geequ_dev<T>(h, m, n, dA, lda, d_r, d_c, d_stats);                                                          \
+    }                                                                                                                      \
+    int lsx_diag_geequ_pass_##sfx##_dev(lsx_handle_t h, int passes, int m, int n, const T *dA, int lda, T *d_r, T *d_c,    \
+                                        double *d_stats) {                                                                 \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        LSX_ARG(h);                                                                                                        \
+        return geequ_dev<T>(h, m, n, dA, lda, d_r, d_c, d_stats, passes);                                                  \
+    }                                                                                                                      \
+    int lsx_laqge_##sfx##_dev(lsx_handle_t h, int m, int n, T *dA, int lda, const T *d_r, const T *d_c, double rowcnd,     \
+                              double colcnd, double amax, int *equed) {                                                    \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        LSX_ARG(h);                                                                                                        \
+        return laqge_dev<T>(h, m, n, dA, lda, d_r, d_c, rowcnd, colcnd, amax, equed);                                      \
+    }                                                                                                                      \
+    int lsx_gesvx_##sfx(lsx_handle_t h, int equil, int trans, int n, int nrhs, const T *A, int lda, const T *B, int ldb,   \
+                        T *X, int ldx, int *equed, T *r, T *c, double *rcond, double *ferr, double *berr, double *rpvgrw,  \
+                        int *info) {                                                                                       \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        return gesvx_host<T>(h, equil, trans, n, nrhs, A, lda, B, ldb, X, ldx, equed, r, c, rcond, ferr, berr, rpvgrw,     \
+                             info);                                                                                        \
+    }                                                                                                                      \
+    int lsx_gesvx_##sfx##_dev(lsx_handle_t h, int equil, int trans, int n, int nrhs, T *dA, int lda, T *dLU, int ldlu,     \
+                              int32_t *d_ipiv, T *dB, int ldb, T *dX, int ldx, int *equed, T *d_r, T *d_c, double *rowcnd, \
+                              double *colcnd, double *rcond, double *ferr, double *berr, double *rpvgrw, int *info) {      \
+        LSX_DEVICE_GUARD(h);                                                                                               \
+        LSX_ARG(h);                                                                                                        \
+        return gesvx_dev<T>(h, equil, trans, n, nrhs, dA, lda, dLU, ldlu, d_ipiv, dB, ldb, dX, ldx, d_r, d_c, equed,       \
+                            rowcnd, colcnd, rcond, ferr, berr, rpvgrw, info);                                              \
+    }
+LSX_GESVX_ABI(f64, double)
+LSX_GESVX_ABI(f32, float)
+#undef LSX_GESVX_ABI
 
 // ---- device-pointer entry points
 int lsx_getrf_f64_dev(lsx_handle_t h, int n, double *dA, int lda, int32_t *d_ipiv, int *d_info) {

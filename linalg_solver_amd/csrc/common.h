@@ -128,6 +128,8 @@ struct lsx_handle_s {
     size_t ws8_bytes = 0;
     int gerfs_steps = 0;     // read-only option: most refinement steps any column of the last gerfs took
     int gerfs_solves = 0;    // read-only option: single-right-hand-side estimator solves of the last gerfs
+    void *ws9 = nullptr;     // equilibration (geequ, gesvx): row maxima, partial column maxima, the drivers' records
+    size_t ws9_bytes = 0;
     int getrs_t_blocked_min = 64;   // transposed solve: smallest nrhs that takes the blocked (MFMA) sweeps when n > 128; 0 = never
     int getrs_t_path = 0;    // read-only option: 1 if the last lsx_getrs_t_* call took the blocked sweeps
     // gather lists (int2[256] each) emitted by the cooperative panel kernels: storage only, a launch is told which one
@@ -368,6 +370,18 @@ int launch_ferr_weight(lsx_handle_t h, int n, const T *Rj, const T *Wj, int ldr,
                        T *out);
 template <typename T>
 int launch_vec_mul(lsx_handle_t h, int n, const T *wt, T *v);
+// equilibration (kernels_equil.hip): geequ's scale factors and stats = {rowcnd, colcnd, amax, info}, laqge's scaling
+// (r or c null: that side unscaled; D2: a second copy of the result, or null), max |a_ij| over the first k columns
+// (upper: on and above the diagonal only)
+size_t geequ_work_bytes(int m, int n, size_t elem);
+template <typename T>
+int launch_geequ(lsx_handle_t h, int m, int n, const T *A, int lda, T *r, T *c, double *stats, void *d_work,
+                 int passes = 3);
+template <typename T>
+int launch_laqge(lsx_handle_t h, int m, int n, T *A, int lda, const T *r, const T *c, T *D2, int ld2);
+size_t maxabs_work_bytes(int m);
+template <typename T>
+int launch_maxabs(lsx_handle_t h, int m, int k, const T *A, int lda, int upper, double *d_work, double *d_out);
 int diag_mfma_peak(lsx_handle_t h, int is_f32, int iters, int blocks_per_cu, double *tflops, double *clock_mhz);
 int diag_cu_mask_probe(lsx_handle_t h, const uint32_t *mask_words, int nwords, int nblocks, unsigned *out_host);
 int getrf_mg_f64(lsx_handle_t *hs, int P, int n, double *const *dA, const int *lda, int32_t *const *d_ipiv,

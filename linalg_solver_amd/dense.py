@@ -271,6 +271,49 @@ def solve_bounded(a, b, trans: bool = False, dtype=np.float64, handle: Optional[
     return (None if info.value else X), ferr, berr, info.value
 
 
+def solve_expert(a, b, trans: bool = False, equilibrate: bool = True, dtype=np.float64,
+                 handle: Optional[N.Handle] = None):
+    """LAPACK's expert driver gesvx in one call (lsx_gesvx_*): equilibrate the matrix if its rows or columns are badly
+    scaled (geequ / laqge; equilibrate=False is fact='N'), factor, estimate the condition of the equilibrated matrix,
+    solve A X = B (trans=True: A^T X = B), refine and bound.  Returns (x, ferr, berr, rcond, rpvgrw, equed, r, c, info):
+    x is None when info is in 1..n (an exactly zero pivot; ferr = berr = +inf, rcond = 0) or when A holds a NaN
+    (rcond, rpvgrw, ferr, berr are NaN; info is 0); info == n + 1 says rcond is below the unit roundoff, x and the bounds are still returned.
+    equed is N.EQUED_NONE / _ROW / _COL / _BOTH and r, c the scale factors (ones where geequ chose none).  ferr / berr
+    are floats for a vector b and arrays for a matrix; ferr is LAPACK's, divided by colcnd / rowcnd after a column /
+    row equilibration, which can make it vacuous (include/lsx.h).  b may have zero columns: the equilibrated condition
+    number alone."""
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    n = A.shape[0]
+    if A.ndim != 2 or A.shape[1] != n:
+        raise ValueError("solve_expert needs a square matrix")
+    if np.shape(b)[:1] != (n,):
+        raise ValueError("right-hand side has the wrong number of rows")
+    h = _h(handle)
+    B = np.ascontiguousarray(b, dtype=dtype)
+    vec = B.ndim == 1
+    if vec:
+        B = B.reshape(n, 1)
+    nrhs = B.shape[1]
+    X = np.zeros((n, nrhs), dtype=dtype)
+    r, c = np.ones(max(n, 1), dtype=dtype), np.ones(max(n, 1), dtype=dtype)
+    ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+    equed, info = C.c_int(0), C.c_int(0)
+    rc, growth = C.c_double(0.0), C.c_double(0.0)
+    ld, ldr = max(n, 1), max(nrhs, 1)
+    name = f"lsx_gesvx_{sfx}"
+    N.check(getattr(h.lib, name)(h.ptr, int(bool(equilibrate)), int(bool(trans)), n, nrhs, _ptr(A, ct), ld, _ptr(B, ct),
+                                 ldr, _ptr(X, ct), ldr, C.byref(equed), _ptr(r, ct), _ptr(c, ct), C.byref(rc),
+                                 _ptr(ferr, C.c_double), _ptr(berr, C.c_double), C.byref(growth), C.byref(info)), name)
+    ferr, berr = ferr[:nrhs], berr[:nrhs]
+    solved = (info.value == 0 or info.value == n + 1) and not math.isnan(rc.value)
+    if vec:
+        x, ferr, berr = (X[:, 0].copy() if solved else None), float(ferr[0]), float(berr[0])
+    else:
+        x = X if solved else None
+    return x, ferr, berr, rc.value, growth.value, equed.value, r[:n], c[:n], info.value
+
+
 def solve_refined(a, b, sweeps: int = 3, handle: Optional[N.Handle] = None):
     """Mixed-precision solve of A X = B (lsx_gesv_f32_refined): fp32 factors on the fp32 MFMA tile, residuals in
     fp64, `sweeps` corrections.  a and b are taken in fp32 (BASELINE config 5 computes in fp32); returns

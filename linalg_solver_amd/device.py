@@ -139,6 +139,84 @@ class DeviceSolver:
                                         X.stride(0), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp)), name)
         return ferr[:nrhs], berr[:nrhs]
 
+    def geequ(self, A: torch.Tensor):
+        """LAPACK's geequ on a tensor in HBM (lsx_geequ_*_dev): returns (r, c, stats) as device tensors -- the row and
+        column scale factors in A's dtype and stats = [rowcnd, colcnd, amax, info] (4 doubles).  No host sync."""
+        _rowmajor(A, "geequ")
+        m, n = A.shape
+        r = torch.ones(max(m, 1), dtype=A.dtype, device=A.device)
+        c = torch.ones(max(n, 1), dtype=A.dtype, device=A.device)
+        stats = torch.zeros(4, dtype=torch.float64, device=A.device)
+        name = f"lsx_geequ_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, m, n, A.data_ptr(), A.stride(0), r.data_ptr(), c.data_ptr(),
+                                        stats.data_ptr()), name)
+        return r[:m], c[:n], stats
+
+    def laqge_(self, A: torch.Tensor, r: torch.Tensor, c: torch.Tensor, rowcnd: float, colcnd: float, amax: float) -> int:
+        """LAPACK's laqge (lsx_laqge_*_dev): scale A in place by the factors of `geequ` if rowcnd, colcnd and amax
+        (host floats: stats.tolist()[:3]) say it is worth it.  Returns equed (N.EQUED_*)."""
+        import ctypes as C
+
+        _rowmajor(A, "laqge_")
+        m, n = A.shape
+        for v, k, w in ((r, m, "r"), (c, n, "c")):
+            if v.dtype != A.dtype or not v.is_cuda or v.dim() != 1 or (k > 1 and v.stride(0) != 1) or v.numel() < k:
+                raise ValueError(f"laqge_: {w} must be a contiguous GPU vector of A's dtype with one entry per "
+                                 f"{'row' if w == 'r' else 'column'}")
+        equed = C.c_int(0)
+        name = f"lsx_laqge_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, m, n, A.data_ptr(), A.stride(0), r.data_ptr(), c.data_ptr(),
+                                        float(rowcnd), float(colcnd), float(amax), C.byref(equed)), name)
+        return equed.value
+
+    def gesvx_(self, A: torch.Tensor, B: torch.Tensor, trans: bool = False, equilibrate: bool = True,
+               LU: Optional[torch.Tensor] = None, X: Optional[torch.Tensor] = None):
+        """LAPACK's expert driver on tensors in HBM (lsx_gesvx_*_dev) with LAPACK's in / out contract: A leaves
+        EQUILIBRATED and B scaled, in place.  Returns a dict: X (the solution of the system as passed in), LU, ipiv
+        (factors of the equilibrated matrix), r, c (device tensors), equed, rowcnd, colcnd, rcond, rpvgrw, info (host
+        scalars) and ferr, berr (numpy arrays).  B may have zero columns.  Synchronises the stream.
+        X is a solution only when info is 0 or n + 1 AND rcond is no NaN: info in 1..n (an exactly zero pivot) leaves X
+        as it was (all NaN when this method allocated it), and a NaN in A gives info = 0 with rcond = NaN and X all
+        NaN."""
+        import ctypes as C
+
+        import numpy as np
+
+        _rowmajor(A, "gesvx_ A")
+        n = A.shape[0]
+        if B.dim() != 2 or A.shape[1] != n or B.shape[0] != n:
+            raise ValueError("gesvx_: need a square matrix and a right-hand side with as many rows")
+        nrhs = B.shape[1]
+        if nrhs == 0:                      # no right-hand sides: whatever strides an empty tensor reports
+            B = torch.empty(n, 0, dtype=B.dtype, device=B.device)
+            X = None
+        _rowmajor(B, "gesvx_ B")
+        if LU is None:
+            LU = torch.empty(n, n, dtype=A.dtype, device=A.device)
+        if X is None:       # NaN, not whatever the allocator hands out: an exactly zero pivot leaves X unwritten
+            X = torch.full((n, nrhs), float("nan"), dtype=A.dtype, device=A.device)
+        _rowmajor(LU, "gesvx_ LU")
+        _rowmajor(X, "gesvx_ X")
+        if tuple(LU.shape) != (n, n) or tuple(X.shape) != (n, nrhs) or not (A.dtype == B.dtype == LU.dtype == X.dtype):
+            raise ValueError("gesvx_: LU must be n x n, X n x nrhs, all of one dtype")
+        ipiv = torch.empty(max(n, 1), dtype=torch.int32, device=A.device)
+        r = torch.ones(max(n, 1), dtype=A.dtype, device=A.device)
+        c = torch.ones(max(n, 1), dtype=A.dtype, device=A.device)
+        ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+        equed, info = C.c_int(0), C.c_int(0)
+        rowcnd, colcnd, rc, growth = C.c_double(1.0), C.c_double(1.0), C.c_double(0.0), C.c_double(0.0)
+        dp = C.POINTER(C.c_double)
+        name = f"lsx_gesvx_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, int(bool(equilibrate)), int(bool(trans)), n, nrhs, A.data_ptr(),
+                                        max(A.stride(0), 1), LU.data_ptr(), max(LU.stride(0), 1), ipiv.data_ptr(),
+                                        B.data_ptr(), max(B.stride(0), 1), X.data_ptr(), max(X.stride(0), 1),
+                                        C.byref(equed), r.data_ptr(), c.data_ptr(), C.byref(rowcnd), C.byref(colcnd),
+                                        C.byref(rc), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp), C.byref(growth),
+                                        C.byref(info)), name)
+        return dict(X=X, LU=LU, ipiv=ipiv[:n], r=r[:n], c=c[:n], equed=equed.value, rowcnd=rowcnd.value,
+                    colcnd=colcnd.value, rcond=rc.value, rpvgrw=growth.value, info=info.value, ferr=ferr[:nrhs],
+                    berr=berr[:nrhs])
+
     def getri(self, LU: torch.Tensor, ipiv: torch.Tensor, out: Optional[torch.Tensor] = None):
         _rowmajor(LU, "getri")
         n = LU.shape[0]

@@ -324,13 +324,58 @@ class Matrix:
         X, ferr, berr = dense.lu_refine(A, LU, ipiv, B, X, trans=trans)
         return (X[:, 0], float(ferr[0]), float(berr[0])) if vec else (X, ferr, berr)
 
-    def solve_array(self, rhs, trans: bool = False, bounds: bool = False):
+    def _solve_equilibrated(self, rhs, trans: bool, bounds: bool):
+        """solve_array(equilibrate=True): LAPACK's expert driver (lsx_gesvx_*); NoSolution by LAPACK's criterion, info in
+        1..n (an exactly zero pivot) or info == n + 1 (rcond of the equilibrated matrix below the unit roundoff)."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            import torch
+
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            n = A.shape[0]
+            if A.shape[1] != n:
+                raise ValueError("solve_array needs a square matrix")
+            B = rhs if hasattr(rhs, "is_cuda") else torch.as_tensor(np.asarray(rhs, dtype=np.float64))
+            B = B.to(device=A.device, dtype=torch.float64)
+            vec = B.dim() == 1
+            if B.shape[0] != n:
+                raise ValueError("Matrix dimensions must match")
+            dev = DeviceSolver(self._dev.device.index)
+            out = dev.gesvx_(A.clone(), B.reshape(n, -1).contiguous().clone(), trans=trans)   # the driver scales in place
+            X, ferr, berr, info = out["X"], out["ferr"], out["berr"], out["info"]
+            if math.isnan(out["rcond"]):        # a NaN in the matrix: nothing was solved (the host path's x = None)
+                X = None
+        else:
+            A = self._array()
+            n = A.shape[0]
+            if A.shape[1] != n:
+                raise ValueError("solve_array needs a square matrix")
+            B = np.asarray(rhs, dtype=np.float64)
+            vec = B.ndim == 1
+            if B.shape[0] != n:
+                raise ValueError("Matrix dimensions must match")
+            X, ferr, berr, _, _, _, _, _, info = dense.solve_expert(A, B.reshape(n, -1), trans=trans)
+        if info != 0 or X is None:
+            return Matrix.NoSolution()
+        if vec:
+            return (X[:, 0], float(ferr[0]), float(berr[0])) if bounds else X[:, 0]
+        return (X, ferr, berr) if bounds else X
+
+    def solve_array(self, rhs, trans: bool = False, bounds: bool = False, equilibrate: bool = False):
         """Unique solution(s) of self * X = rhs for a square matrix (rhs: vector or matrix) as an ndarray;
         NoSolution() when the matrix is singular to working precision (use find_preimage_of for the
         general affine answer).  trans=True solves self^T * X = rhs (x * self = rhs^T for rows) from the factors of
         self: no transposed copy, no second factorisation.  bounds=True refines the solution (LAPACK's gerfs) and
         returns (x, ferr, berr): per right-hand side a bound of max|x - x_true| / max|x| and the componentwise
-        backward error (floats for a vector rhs, arrays for a matrix)."""
+        backward error (floats for a vector rhs, arrays for a matrix).
+        equilibrate=True goes through LAPACK's expert driver (gesvx: row and column scaling where the matrix needs it,
+        then factor, solve, refine): a matrix that is merely badly scaled -- which the pivot-ratio rule calls singular
+        -- is solved, and NoSolution() is LAPACK's criterion instead (an exactly zero pivot, or the reciprocal condition
+        number of the EQUILIBRATED matrix below 2^-53).  With bounds=True ferr is LAPACK's, which after a column
+        scaling is divided by the scales' spread and can be vacuous (include/lsx.h); berr is not affected."""
+        if equilibrate:
+            return self._solve_equilibrated(rhs, trans, bounds)
         if bounds:
             return self._solve_bounded(rhs, trans)
         if getattr(self, "_dev", None) is not None and self._items is None:
@@ -347,11 +392,33 @@ class Matrix:
             return Matrix.NoSolution()
         return X[:, 0] if vec else X
 
-    def rcond(self, norm=1) -> float:
+    def _rcond_equilibrated(self, norm) -> float:
+        """gesvx without right-hand sides: trans picks the norm (the infinity-norm of A is the 1-norm of A^T)."""
+        trans = dense._norm_code(norm) == dense.N.NORM_INF
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            import torch
+
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            if A.shape[0] != A.shape[1]:
+                raise ValueError("rcond needs a square matrix")
+            dev = DeviceSolver(self._dev.device.index)
+            B = torch.empty(A.shape[0], 0, dtype=torch.float64, device=A.device)
+            return dev.gesvx_(A.clone(), B, trans=trans)["rcond"]
+        A = self._array()
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("rcond needs a square matrix")
+        return dense.solve_expert(A, np.zeros((A.shape[0], 0)), trans=trans)[3]
+
+    def rcond(self, norm=1, equilibrate: bool = False) -> float:
         """Reciprocal condition number 1 / (||A|| ||A^-1||) in the 1-norm (norm=1) or the infinity-norm
         (norm=inf): LAPACK's gecon estimate from the LU factors (lsx_rcond_f64 / lsx_gecon_f64_dev).  0.0 for a
         matrix with an exactly zero pivot.  Unlike the pivot ratio behind NoSolution it sees ill-conditioning that
-        leaves every pivot large."""
+        leaves every pivot large.  equilibrate=True: of the matrix after LAPACK's row / column equilibration
+        (lsx_gesvx_* without right-hand sides) -- what is left of the conditioning once bad scaling is taken out."""
+        if equilibrate:
+            return self._rcond_equilibrated(norm)
         if getattr(self, "_dev", None) is not None and self._items is None:
             from .device import DeviceSolver
 
@@ -372,9 +439,9 @@ class Matrix:
             raise ValueError("rcond needs a square matrix")
         return dense.rcond(A, norm)[0]
 
-    def cond(self, norm=1) -> float:
-        """Estimated condition number 1 / rcond(norm); inf when rcond is 0."""
-        r = self.rcond(norm)
+    def cond(self, norm=1, equilibrate: bool = False) -> float:
+        """Estimated condition number 1 / rcond(norm, equilibrate); inf when rcond is 0."""
+        r = self.rcond(norm, equilibrate)
         return float("inf") if r == 0.0 else 1.0 / r
 
     def inverse_array(self) -> "np.ndarray | Matrix.NoSolution":

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | gecon | gerfs [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | gecon | gerfs | equil [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -524,6 +524,87 @@ def main():
                       f"(rounds {rounds[0]:.3f} / {rounds[1]:.3f}; {dev.h.get_option('gerfs_steps')} steps, "
                       f"{dev.h.get_option('gerfs_solves')} estimator solves, {min(rounds) / t_lu * 100:.1f} % of getrf)  "
                       f"berr {berr.max():.2e} ferr {ferr.max():.2e}", flush=True)
+    if "equil" in args.what:
+        # equilibration (kernels_equil.hip): each pass of geequ beside the lange call that reads the same bytes -- the row
+        # pass beside the infinity-norm, the column pass beside the 1-norm -- then laqge, and a whole gesvx with its share
+        # spent on equilibration.  Median of 21 timed calls after 3 warm-up calls, two alternating rounds (the smaller
+        # median is reported, both are printed); gesvx synchronises, so it is timed with the host clock.
+        HBM = 8.0e12
+        lib, hp = dev.lib, dev.h.ptr
+
+        def med(fn):
+            return timeit(fn, reps=21, warm=3)[1]
+        for n in (4096, 8192):
+            for dt in (torch.float64, torch.float32):
+                sfx = "f64" if dt == torch.float64 else "f32"
+                # the recipe of tests/cpu_refine.scaled_system: columns 2^-30 .. 2^30, every third row 2^-20
+                A64 = torch.empty(n, n, dtype=torch.float64, device="cuda")
+                dev.fill_(A64, gen.U11, 1)
+                torch.cuda.synchronize()
+                scales = torch.randint(-30, 31, (n,), generator=torch.Generator().manual_seed(n)).double()
+                A64 *= (2.0 ** scales).cuda()[None, :]
+                A64[::3] *= 2.0 ** -20
+                A0 = A64.to(dt)
+                del A64
+                A = A0.clone()
+                r, c = torch.empty(n, dtype=dt, device="cuda"), torch.empty(n, dtype=dt, device="cuda")
+                st, out = torch.zeros(4, dtype=torch.float64, device="cuda"), torch.zeros(1, dtype=torch.float64, device="cuda")
+                gp = getattr(lib, f"lsx_diag_geequ_pass_{sfx}_dev")
+                ln = getattr(lib, f"lsx_lange_{sfx}_dev")
+                runs = {"row pass": lambda: gp(hp, 1, n, n, A0.data_ptr(), n, r.data_ptr(), c.data_ptr(), st.data_ptr()),
+                        "lange inf": lambda: ln(hp, N.NORM_INF, n, n, A0.data_ptr(), n, out.data_ptr()),
+                        "column pass": lambda: gp(hp, 2, n, n, A0.data_ptr(), n, r.data_ptr(), c.data_ptr(), st.data_ptr()),
+                        "lange one": lambda: ln(hp, N.NORM_ONE, n, n, A0.data_ptr(), n, out.data_ptr()),
+                        "geequ": lambda: gp(hp, 3, n, n, A0.data_ptr(), n, r.data_ptr(), c.data_ptr(), st.data_ptr())}
+                for k, f in runs.items():           # a refused call must not be timed as a very fast pass
+                    N.check(f(), k)
+                res = {k: [] for k in runs}
+                for _ in range(2):
+                    for k, f in runs.items():
+                        res[k].append(med(f))
+                rowcnd, colcnd, amax, ginfo = st.tolist()
+                by = float(n) * n * A0.element_size()
+                print(f"geequ {sfx} n={n}: " + "  ".join(
+                    f"{k} {min(v) * 1e3:.1f} us (rounds {v[0] * 1e3:.1f} / {v[1] * 1e3:.1f}; "
+                    f"{(2 if k == 'geequ' else 1) * by / (min(v) * 1e-3) / HBM * 100:.1f} % of 8 TB/s)" for k, v in res.items())
+                    + f"  row / inf {min(res['row pass']) / min(res['lange inf']):.2f}  column / one "
+                      f"{min(res['column pass']) / min(res['lange one']):.2f}", flush=True)
+
+                def scale():
+                    A.copy_(A0)
+                    return dev.laqge_(A, r, c, rowcnd, colcnd, amax)
+                t_copy = min(med(lambda: A.copy_(A0)) for _ in range(2))
+                t_laq = min(med(scale) for _ in range(2)) - t_copy
+                print(f"laqge {sfx} n={n}: {t_laq * 1e3:.1f} us (equed {scale()}; read + write "
+                      f"{2 * by / (t_laq * 1e-3) / HBM * 100:.1f} % of 8 TB/s; the copy that resets the matrix "
+                      f"{t_copy * 1e3:.1f} us is subtracted)", flush=True)
+                B0 = torch.empty(n, 1, dtype=dt, device="cuda")
+                dev.fill_(B0, gen.U11, 2)
+                B = B0.clone()
+                LU, X = torch.empty(n, n, dtype=dt, device="cuda"), torch.empty(n, 1, dtype=dt, device="cuda")
+
+                def host_med(fn, reps=7, warm=2):
+                    for _ in range(warm):
+                        fn()
+                    ts = []
+                    for _ in range(reps):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        fn()
+                        torch.cuda.synchronize()
+                        ts.append((time.perf_counter() - t0) * 1e3)
+                    return sorted(ts)[len(ts) // 2]
+
+                def driver(equil):
+                    A.copy_(A0)
+                    B.copy_(B0)
+                    return dev.gesvx_(A, B, equilibrate=equil, LU=LU, X=X)
+                t_e, t_n = host_med(lambda: driver(True)), host_med(lambda: driver(False))
+                o = driver(True)
+                t_eq = min(res["geequ"]) + t_laq
+                print(f"gesvx {sfx} n={n} nrhs=1: equilibrated {t_e:.3f} ms (equed {o['equed']}, rcond {o['rcond']:.2e}, berr "
+                      f"{o['berr'][0]:.1e}), fact='N' {t_n:.3f} ms; geequ + laqge {t_eq:.3f} ms = {t_eq / t_e * 100:.1f} % of "
+                      f"the equilibrated call", flush=True)
     if "lu" in args.what:
         n = args.n
         A0 = torch.empty(n, n, dtype=torch.float32 if args.f32 else torch.float64, device="cuda")
