@@ -114,7 +114,15 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value);
 /* ---- host-buffer entry points (fp64) ------------------------------------ */
 /* In-place LU with partial pivoting, P*A = L*U, unit-lower L below the diagonal.
  * ipiv[k] = 0-based row exchanged with row k at step k.  *info = 0, or k+1 for
- * the first k whose pivot was exactly zero (factorisation continues). */
+ * the first k whose pivot was exactly zero (factorisation continues).
+ * Numeric domain: the results are equivariant under power-of-two scaling while the intermediates are normal numbers
+ * -- A diag(2^d) gives the same pivots, the same bits of L and the columns of U times 2^d, bit for bit; the solves, the
+ * inverse, the determinant (exp2 moves by sum d), the condition estimate and the row reductions follow suit.
+ * Subnormal pivots are handled as LAPACK's getf2 handles them: the column is divided by the pivot (here: scaled by
+ * 2^64, fp32 2^32, exactly, then by the reciprocal), not multiplied by a reciprocal that is not a finite number.
+ * That holds for lsx_getrf_* and for lsx_rref_* under LSX_PIVOT_MAX; the solves, the inverse and the blocked
+ * first-non-zero reduction (fp64, m * bar_col >= 256 * 256) form inverses of pivot blocks and need pivots whose
+ * reciprocal is a finite number. */
 int lsx_getrf_f64(lsx_handle_t h, int n, double *A, int lda, int32_t *ipiv, int *info);
 /* Solve A X = B from the factors; B (n x nrhs, row-major) is overwritten by X. */
 int lsx_getrs_f64(lsx_handle_t h, int n, int nrhs, const double *LU, int lda,
@@ -135,7 +143,8 @@ int lsx_det_f64(lsx_handle_t h, int n, const double *A, int lda, double *sign, d
  * remaining columns carried along (row_reduce, linalg.py:534-630).  bar_col <= 0
  * means n-1 (linalg.py:543).  pivots holds *rank pairs (row, col), 0-based.
  * Pivot tolerance: |a| <= tol counts as zero; tol < 0 selects 32*eps*max(m,n)*max|working matrix left of bar_col|
- * (the running maximum, re-evaluated as the elimination proceeds; the carried-along columns do not count).
+ * (the running maximum, re-evaluated as the elimination proceeds; the carried-along columns and the finished pivot
+ * rows, which are normalised, do not count).
  * pivot_rule LSX_PIVOT_FIRST takes the first row at or below the pivot row whose
  * entry is non-zero -- the reference's rule (linalg.py:548-552), which also fixes
  * the carried-along columns of rank-deficient / tall inputs; LSX_PIVOT_MAX takes

@@ -225,7 +225,7 @@ struct Real<float> {
     static constexpr float eps = 1.1920929e-07f;
 };
 
-// 1/x for the pivot scaling of every panel kernel (the same function everywhere so the three
+// 1/x for the pivot scaling of every panel kernel, through pivot_recip below (the same function everywhere so the three
 // panel modes stay bit-identical): hardware reciprocal + Newton, <= 1 ulp; an IEEE division
 // costs ~40 instructions on the per-column critical path.
 template <typename T>
@@ -239,6 +239,22 @@ __device__ __forceinline__ T fast_recip(T x) {
     float r = __builtin_amdgcn_rcpf((float)x);
     r = r * (2.0f - (float)x * r);
     return (T)r;
+}
+
+// a / p for the pivot scaling, as (a * c) * rinv with rinv = fast_recip(p * c): c = 1 for a normal pivot (a * 1 is
+// exact: the same bits as a * fast_recip(p)), c = 2^64 (fp32: 2^32) for a subnormal one, whose reciprocal is not a
+// finite number -- LAPACK's getf2 divides below sfmin for the same reason.  p * c is then normal and a * c exact
+// (|a| <= |p|).  One value per column, uniform over the wave; every kernel that scales by a pivot takes it from here.
+template <typename T>
+struct PivotRecip {
+    T c, rinv;
+    __device__ __forceinline__ T apply(T a) const { return (a * c) * rinv; }
+};
+template <typename T>
+__device__ __forceinline__ PivotRecip<T> pivot_recip(T p) {
+    const T safmin = sizeof(T) == 8 ? (T)0x1p-1022 : (T)0x1p-126f;
+    const T c = (p < T(0) ? -p : p) < safmin ? (sizeof(T) == 8 ? (T)0x1p64 : (T)0x1p32f) : T(1);
+    return PivotRecip<T>{c, fast_recip<T>(p * c)};
 }
 
 

@@ -83,10 +83,11 @@ __global__ __launch_bounds__(256) void panel_update_kernel(int m, int jb, T *__r
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r0 = (j + 1) + blockIdx.x * PROWS;
     const int nc = j + 1;  // column whose arg-max we prepare
-    T piv = T(1), rinv = T(0);
+    T piv = T(1);
+    PivotRecip<T> rinv{T(1), T(0)};
     if (j >= 0) {
         piv = P[(size_t)j * ldp + j];
-        rinv = (piv != T(0)) ? fast_recip<T>(piv) : T(0);
+        if (piv != T(0)) rinv = pivot_recip<T>(piv);
     }
     T best = T(-1);
     int besti = 0x7fffffff;
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(256) void panel_update_kernel(int m, int jb, T *__r
         T *row = P + (size_t)i * ldp;
         T l = T(0);
         if (j >= 0) {
-            l = row[j] * rinv;
+            l = rinv.apply(row[j]);
             if (piv == T(0)) l = row[j];  // singular column: leave entries untouched (LAPACK)
         }
         for (int c0 = 0; c0 < jb; c0 += 64) {

@@ -346,7 +346,7 @@ __device__ __forceinline__ void panel_pipe_body(const int G, const int g, int m,
             for (int c = JC; c < 8; ++c) uu[c] = readlane_t(usrc, ub + c);
             const T piv = uu[JC];
             const bool act = valid & !failed_now & (piv != T(0));
-            const T rinv = act ? fast_recip<T>(piv) : T(0);
+            const PivotRecip<T> rinv = act ? pivot_recip<T>(piv) : PivotRecip<T>{T(1), T(0)};
             const bool own = tx == txo;
             if (own) {
                 if (valid && bg == g) {
@@ -356,7 +356,7 @@ __device__ __forceinline__ void panel_pipe_body(const int G, const int g, int m,
                 T l[RT];
 #pragma unroll
                 for (int r = 0; r < RT; ++r) {
-                    const T v = a[r][JC] * rinv;
+                    const T v = rinv.apply(a[r][JC]);
                     l[r] = ((frozen >> r) & 1u) ? T(0) : v;
                     s_l[par][NTY * r + ty] = l[r];
                     a[r][JC] = (act & (((frozen >> r) & 1u) == 0u)) ? l[r] : a[r][JC];

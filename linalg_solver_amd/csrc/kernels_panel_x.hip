@@ -468,8 +468,8 @@ __device__ __forceinline__ void panel_x_body(const int G, const int g, int m, in
         u4 nq = u4{0u, 0u, 0u, 0u};
         const int noff = (par * G + bg) * PX_REC + 16 * (lane & 7);
         if (fetch) nq = __builtin_amdgcn_raw_buffer_load_b128(r_rec, noff, opaque_zero(), 16);
-        const T rabs = act ? fast_recip<T>((T)pabs) : T(0);
-        const T rinv = pneg ? -rabs : rabs;   // fast_recip is odd: the same bits as fast_recip(pivot)
+        PivotRecip<T> rinv = act ? pivot_recip<T>((T)pabs) : PivotRecip<T>{T(1), T(0)};
+        if (pneg) rinv.rinv = -rinv.rinv;   // fast_recip is odd: the same bits as pivot_recip(pivot)
         if (valid && bg == g) {
             const int wl = win - base;
             if ((wl & 63) == lane) frozen |= 1u << (wl >> 6);
@@ -478,7 +478,7 @@ __device__ __forceinline__ void panel_x_body(const int G, const int g, int m, in
         T l[RT];
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
-            const T v = a[r][CJ] * rinv;
+            const T v = rinv.apply(a[r][CJ]);
             l[r] = ((frozen >> r) & 1u) ? T(0) : v;
             s_l[par][64 * r + lane] = l[r];
             a[r][CJ] = (act & (((frozen >> r) & 1u) == 0u)) ? l[r] : a[r][CJ];

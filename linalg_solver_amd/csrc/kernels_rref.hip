@@ -38,7 +38,7 @@ struct RrefState {
     int skip;     // 1: current column has no pivot
     int pad[3];
     double tol;        // fixed tolerance (user) or < 0: eps_scale * amax, re-evaluated per column
-    double amax;       // running max |entry| of the working matrix left of the bar (grows with elimination)
+    double amax;       // running max |entry| of the working matrix left of the bar, pivot row and below (grows with elimination)
     double eps_scale;  // eps * max(m, n)
 };
 
@@ -90,8 +90,9 @@ __global__ __launch_bounds__(256) void rref_pivot_kernel(int m, int n, int pj, i
     int vi = 0x7fffffff;
     for (int i = pi + tid; i < m; i += 256) {
         double a = fabs((double)R[(size_t)i * ldr + pj]);
-        // FIRST rule: every non-zero entry scores the same, so the lowest row index wins below
-        if (pivot_rule == LSX_PIVOT_FIRST) a = (a > tol) ? 1.0e300 : 0.0;
+        // FIRST rule: every non-zero entry scores the same, so the lowest row index wins below (the score is above
+        // any tolerance: a finite one would make a matrix of entries near 2^1000 with a tolerance to match rank 0)
+        if (pivot_rule == LSX_PIVOT_FIRST) a = (a > tol) ? __builtin_huge_val() : 0.0;
         if (a > v) { v = a; vi = i; }
     }
     s_v[tid] = v; s_i[tid] = vi;
@@ -127,7 +128,9 @@ __global__ __launch_bounds__(256) void rref_pivot_kernel(int m, int n, int pj, i
 // held the pivot (p) receives the displaced row, eliminated; every other row
 // with a non-zero entry in column pj is eliminated in place.  The running maximum behind the default tolerance is
 // taken over the columns left of `bar` only, as the blocked forms take it: the carried-along columns are updated but
-// do not count, or a large right-hand side would raise the tolerance above the pivots of the left block.
+// do not count, or a large right-hand side would raise the tolerance above the pivots of the left block.  The rows
+// above the pivot row do not count either (the blocked forms look at the live rows only): they are normalised pivot
+// rows, of magnitude 1 whatever the scale of the data, and would hide every pivot of a matrix of small entries.
 template <typename T>
 __global__ __launch_bounds__(256) void rref_sweep_kernel(int m, int n, int bar, int pj, T *__restrict__ R,
                                                          int ldr, RrefState *st,
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(256) void rref_sweep_kernel(int m, int n, int bar, 
     for (int c = pj + lane; c < n; c += 64) {
         const T v = src[c] - f * prow[c];
         row[c] = v;
-        if (c < bar) vmax = fmax(vmax, fabs((double)v));
+        if (c < bar && i > pi) vmax = fmax(vmax, fabs((double)v));
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) vmax = fmax(vmax, __shfl_down(vmax, off, 64));

@@ -175,10 +175,11 @@ __global__ __launch_bounds__(256) void rrb_update_kernel(int m, T *__restrict__ 
     const int first = skip ? rc : rc + 1;      // rows that are candidates for the next column
     const int r0 = first + blockIdx.x * RRB_ROWS;   // rows per workgroup (cand index = blockIdx.x)
     const int nc = col + 1;
-    T piv = T(1), rinv = T(0);
+    T piv = T(1);
+    PivotRecip<T> rinv{T(1), T(0)};
     if (!skip) {
         piv = W[(size_t)rc * ldw + col];
-        rinv = fast_recip<T>(piv);
+        rinv = pivot_recip<T>(piv);
     }
     T best = T(-1);
     int besti = 0x7fffffff;
@@ -187,7 +188,7 @@ __global__ __launch_bounds__(256) void rrb_update_kernel(int m, T *__restrict__ 
         if (i >= m) break;
         T *row = W + (size_t)i * ldw;
         T l = T(0);
-        if (!skip) l = row[col] * rinv;
+        if (!skip) l = rinv.apply(row[col]);
         for (int cc = col - c0 + lane; cc < w; cc += 64) {   // columns col .. c0 + w - 1
             const int c = c0 + cc;
             T v = row[c];
@@ -260,6 +261,21 @@ __global__ __launch_bounds__(256) void rrb_gather_u_kernel(int nrows, int jb, co
     const int t = threadIdx.x & 127;
     if (i >= nrows || t >= jb) return;
     G[(size_t)i * RB_W + t] = W[(size_t)i * ldw + pivots[2 * (kb + t) + 1]];
+}
+// Before phase 2: a pivot row whose pivot is subnormal is multiplied by 2^64 (fp32: 2^32), exactly.  The reduced row
+// does not depend on the scale of the row it is made from, and the inverse of the pivot block, which phase 2 forms,
+// is not a finite number while a pivot is subnormal.  One workgroup per pivot row; a normal pivot: nothing is written.
+template <typename T>
+__global__ __launch_bounds__(256) void rrb_lift_kernel(int rank, int n, T *__restrict__ W, int ldw,
+                                                       const int32_t *__restrict__ pivots) {
+    for (int i = blockIdx.x; i < rank; i += gridDim.x) {
+        const int pc = pivots[2 * i + 1];
+        T *row = W + (size_t)i * ldw;
+        const T c = pivot_recip<T>(row[pc]).c;
+        __syncthreads();   // every thread has read the pivot before it is scaled
+        if (c != T(1))
+            for (int j = pc + threadIdx.x; j < n; j += 256) row[j] *= c;
+    }
 }
 // pivot columns -> exact unit vectors; rows >= rank -> exact zeros left of the bar
 template <typename T>
@@ -354,6 +370,7 @@ int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *
         LSX_HIP(hipMemcpyAsync(hp.data(), d_pivots, sizeof(int32_t) * 2 * rank, hipMemcpyDeviceToHost, s));
         LSX_HIP(hipStreamSynchronize(s));
     }
+    if (rank > 0) hipLaunchKernelGGL(rrb_lift_kernel<T>, dim3(std::min(rank, 4096)), dim3(256), 0, s, rank, n, W, ldw, d_pivots);
     const int last = rank > 0 ? ((rank - 1) / RB_W) * RB_W : -1;
     for (int kb = last; kb >= 0; kb -= RB_W) {
         const int jb = std::min(RB_W, rank - kb);

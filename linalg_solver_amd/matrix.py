@@ -43,6 +43,26 @@ from . import dense
 _NUMERIC = (int, float, np.integer, np.floating)
 
 
+def _pow2_shift(amax: float) -> int:
+    """The k for which amax * 2^k lies in [1/2, 1) when amax is further than 2^500 from 1, else 0.  solve_array and
+    the inverse multiply such a matrix (and right-hand side) by 2^k before the factorisation and take the power back
+    out of the result, so that the block inverses the solves form -- whose entries are reciprocals of pivots -- stay
+    finite for a matrix of entries near the ends of the exponent range.  The first step is exact for every entry that
+    is still a normal number after it: an entry more than about 2^1022 below the largest one underflows (in
+    diag(1e200, 1e-200) one entry becomes 0; the pivot-ratio rule calls such a matrix singular at any scale).  The
+    second step is one IEEE multiplication: exact unless the true result overflows (inf) or is subnormal."""
+    if not (amax > 0.0) or math.isinf(amax):
+        return 0
+    e = math.frexp(amax)[1]
+    return -e if abs(e) > 500 else 0
+
+
+def _ldexp_t(t, k: int):
+    """torch tensor * 2^k in two steps (2^k itself may not be a finite number); the first leaves every entry that
+    the product keeps normal exact, so the result is rounded once at most."""
+    return t if k == 0 else (t * math.ldexp(1.0, k // 2)) * math.ldexp(1.0, k - k // 2)
+
+
 def _as_array(items: List[List[Any]]) -> np.ndarray:
     for row in items:
         for v in row:
@@ -235,22 +255,27 @@ class Matrix:
         if A.shape[1] != n:
             raise ValueError("solve_array needs a square matrix")
         dev = DeviceSolver(self._dev.device.index)
+        ka = _pow2_shift(float(A.abs().max())) if n else 0
+        A = _ldexp_t(A, ka)
         LU = A.clone()
         ipiv, info = dev.getrf_(LU)
         if rhs is None:
-            X = dev.getri(LU, ipiv)
+            X = _ldexp_t(dev.getri(LU, ipiv), ka)
         else:
             B = rhs if hasattr(rhs, "is_cuda") else torch.as_tensor(np.asarray(rhs, dtype=np.float64))
             B = B.to(device=A.device, dtype=torch.float64)
             vec = B.dim() == 1
             if B.shape[0] != n:
                 raise ValueError("Matrix dimensions must match")
-            X = B.reshape(n, -1).contiguous().clone()
+            kb = _pow2_shift(float(B.abs().max())) if B.numel() else 0
+            X = _ldexp_t(B.reshape(n, -1).contiguous(), kb).clone()
             dev.getrs_(LU, ipiv, X, trans=trans)
+            X = _ldexp_t(X, ka - kb)
             if vec:
                 X = X[:, 0]
         # singular to working precision: the same test as the host path (smallest |pivot| against the largest entry)
-        ratio = float(LU.diagonal().abs().min() / A.abs().max().clamp_min(1e-300))
+        amax = float(A.abs().max()) if n else 0.0
+        ratio = float(LU.diagonal().abs().min()) / amax if amax > 0 else 0.0
         code = int(info.item())
         if code < 0:
             # a cooperative kernel timed out on the device (lsx.h: lsx_check_status): that is a failure of the run,
@@ -287,6 +312,8 @@ class Matrix:
             if A.shape[1] != n:
                 raise ValueError("solve_array needs a square matrix")
             dev = DeviceSolver(self._dev.device.index)
+            ka = _pow2_shift(float(A.abs().max())) if n else 0
+            A = _ldexp_t(A, ka)          # a copy when ka != 0: the caller's tensor is never written
             LU = A.clone()
             ipiv, info = dev.getrf_(LU)
             B = rhs if hasattr(rhs, "is_cuda") else torch.as_tensor(np.asarray(rhs, dtype=np.float64))
@@ -294,17 +321,20 @@ class Matrix:
             vec = B.dim() == 1
             if B.shape[0] != n:
                 raise ValueError("Matrix dimensions must match")
-            B = B.reshape(n, -1).contiguous()
+            kb = _pow2_shift(float(B.abs().max())) if B.numel() else 0
+            B = _ldexp_t(B.reshape(n, -1).contiguous(), kb)
             code = int(info.item())
             if code < 0:
                 dev.h.check_status()
                 raise RuntimeError(f"device factorisation failed (info = {code})")
-            ratio = float(LU.diagonal().abs().min() / A.abs().max().clamp_min(1e-300)) if n else 1.0
+            amax = float(A.abs().max()) if n else 0.0
+            ratio = float(LU.diagonal().abs().min()) / amax if amax > 0 else 0.0
             if code != 0 or not (ratio > dense.EPS64 * n):
                 return Matrix.NoSolution()
             X = B.clone()
             dev.getrs_(LU, ipiv, X, trans=trans)
-            ferr, berr = dev.gerfs_(A, LU, ipiv, B, X, trans=trans)
+            ferr, berr = dev.gerfs_(A, LU, ipiv, B, X, trans=trans)   # both bounds are relative: scale-free
+            X = _ldexp_t(X, ka - kb)
             return (X[:, 0], float(ferr[0]), float(berr[0])) if vec else (X, ferr, berr)
         A = self._array()
         n = A.shape[0]
@@ -314,14 +344,17 @@ class Matrix:
         vec = B.ndim == 1
         if B.shape[0] != n:
             raise ValueError("Matrix dimensions must match")
-        B = B.reshape(n, -1)
+        ka = _pow2_shift(float(np.abs(A).max(initial=0.0)))
+        kb = _pow2_shift(float(np.abs(B).max(initial=0.0)))
+        A, B = np.ldexp(A, ka), np.ldexp(B.reshape(n, -1), kb)
         LU, ipiv, info = dense.lu_factor(A)
         amax = float(np.max(np.abs(A))) if n else 0.0
         ratio = float(np.min(np.abs(np.diagonal(LU)))) / amax if amax > 0 else 0.0
         if info != 0 or not (ratio > dense.EPS64 * n):
             return Matrix.NoSolution()
         X = dense.lu_solve(LU, ipiv, B, trans=trans)
-        X, ferr, berr = dense.lu_refine(A, LU, ipiv, B, X, trans=trans)
+        X, ferr, berr = dense.lu_refine(A, LU, ipiv, B, X, trans=trans)   # both bounds are relative: scale-free
+        X = np.ldexp(X, ka - kb)
         return (X[:, 0], float(ferr[0]), float(berr[0])) if vec else (X, ferr, berr)
 
     def _solve_equilibrated(self, rhs, trans: bool, bounds: bool):
@@ -387,9 +420,12 @@ class Matrix:
         vec = B.ndim == 1
         if B.shape[0] != A.shape[0]:
             raise ValueError("Matrix dimensions must match")
-        X, info, ratio = dense.solve(A, B.reshape(A.shape[0], -1), trans=trans)
+        ka = _pow2_shift(float(np.abs(A).max(initial=0.0)))
+        kb = _pow2_shift(float(np.abs(B).max(initial=0.0)))
+        X, info, ratio = dense.solve(np.ldexp(A, ka), np.ldexp(B.reshape(A.shape[0], -1), kb), trans=trans)
         if info != 0 or not (ratio > dense.EPS64 * A.shape[0]):
             return Matrix.NoSolution()
+        X = np.ldexp(X, ka - kb)
         return X[:, 0] if vec else X
 
     def _rcond_equilibrated(self, norm) -> float:
@@ -452,10 +488,12 @@ class Matrix:
         A = self._array()
         if A.shape[0] != A.shape[1]:
             raise ValueError("Matrix must be square to invert.")
-        X, info, ratio = dense.inv(A)
+        ka = _pow2_shift(float(np.abs(A).max(initial=0.0)))
+        X, info, ratio = dense.inv(np.ldexp(A, ka))
         if info != 0 or not (ratio > dense.EPS64 * A.shape[0]):
             return Matrix.NoSolution()
-        return X
+        with np.errstate(over="ignore"):   # the inverse of a matrix of tiny entries may not be representable: inf there
+            return np.ldexp(X, ka)
 
     def transpose(self) -> "Matrix":
         return Matrix([[self.items[j][i] for j in range(self.rows)] for i in range(self.cols)])
@@ -702,10 +740,12 @@ class Matrix:
                     if abs(items[i][j] - (1.0 if i == j else 0.0)) > 1e-12:
                         return Matrix.NoSolution()  # :737
             return Matrix([row[n:] for row in items])
-        X, info, ratio = dense.inv(A)
+        ka = _pow2_shift(float(np.abs(A).max(initial=0.0)))
+        X, info, ratio = dense.inv(np.ldexp(A, ka))
         if info != 0 or not (ratio > dense.EPS64 * n):
             return Matrix.NoSolution()  # :701 / :737
-        return Matrix(X.tolist())
+        with np.errstate(over="ignore"):
+            return Matrix(np.ldexp(X, ka).tolist())
 
     def determinant(self, log_permutation_details: bool = False, use_optimal: bool = True) -> Any:
         """linalg.py:183-207.  sign * prod(diag U) from the pivoted LU."""

@@ -125,7 +125,8 @@ def default_tol_at_input(A, bar, dtype):
 def reduce_reference(A, bar, dtype, rule, tol=-1.0, amax_cols="left"):
     """The documented row reduction in numpy, in `dtype`: per column, first-non-zero or largest-magnitude pivot below
     the pivot row, |a| <= tol counts as zero (the column is cleared from the pivot row down and skipped), default
-    tolerance 32 eps max(m, n) * (running maximum of the working matrix left of the bar), elimination above and below
+    tolerance 32 eps max(m, n) * (running maximum of the working matrix left of the bar, the finished pivot rows
+    above the current one left out: they are normalised, not at the scale of the data), elimination above and below
     in one sweep.  amax_cols="all" takes the running maximum over the carried-along columns too: NOT the documented
     rule, kept to show what it does to a large right-hand side.  Returns R, pivots."""
     a = np.array(A, dtype=dtype)
@@ -158,7 +159,7 @@ def reduce_reference(A, bar, dtype, rule, tol=-1.0, amax_cols="left"):
         rows = np.nonzero(f)[0]
         if len(rows):
             a[rows, pj:] -= np.outer(f[rows], a[pi, pj:])
-            amax = max(amax, float(np.abs(a[rows, pj:hi]).max(initial=0.0)))
+            amax = max(amax, float(np.abs(a[rows[rows > pi], pj:hi]).max(initial=0.0)))
         piv.append((pi, pj))
         pi += 1
     return a, piv
