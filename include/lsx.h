@@ -377,6 +377,53 @@ int lsx_gesvx_f32_dev(lsx_handle_t h, int equil, int trans, int n, int nrhs, flo
                       int32_t *d_ipiv, float *dB, int ldb, float *dX, int ldx, int *equed, float *d_r, float *d_c,
                       double *rowcnd, double *colcnd, double *rcond, double *ferr, double *berr, double *rpvgrw, int *info);
 
+/* ---- Cholesky factorisation and solves for symmetric positive definite matrices (LAPACK's potrf, potrs, posv) ---- */
+/* Storage: row-major, UPPER.  On return the upper triangle of A holds U with A = U^T U and u_ii > 0.  Only the upper
+ * triangle of A is read; the strictly lower triangle is never read and never written by any kernel, not inside a
+ * diagonal 128-block either (LAPACK's uplo contract): it may hold anything, NaN included.  Symmetry is the caller's
+ * assertion and is not checked.
+ * lsx_potrf_*_dev: asynchronous on the handle's stream.  d_info is a device int and may be NULL.  *d_info = 0, or j + 1
+ * (1-based) for the first j whose pivot a_jj - sum_{k<j} u_kj^2 is <= 0 or NaN (dpotf2's test).  With info = j + 1 the
+ * leading j x j upper triangle is the factor of the leading j x j submatrix, as in LAPACK; the rest of the upper triangle
+ * is unspecified.  Right-looking over 128-row steps on one stream: the diagonal block in one workgroup (rows in dpotf2's
+ * order, the row scaled by the reciprocal of u_jj as dpotf2 does), the block row through the TN form of the MFMA tile,
+ * the trailing update on the tiles on and above the diagonal only.  No launch after a failed pivot faults or spins: the
+ * later diagonal launches read the info word and return, the products between them run on harmless data.  There is no
+ * time-out outcome: nothing here is cooperative, no kernel waits on another workgroup, lsx_check_status has nothing to
+ * report.  No look-ahead.
+ * lsx_potrs_*_dev: B <- inv(U) inv(U^T) B, B n x nrhs row-major.  Any nrhs >= 1 goes through 128-row block sweeps on the
+ * MFMA tile (U^T Y = B in the TN form, then U X = Y); a latency path for few right-hand sides like "trsv" = 2 of
+ * lsx_getrs_* is out of scope: one right-hand side costs what 128 cost.  Extra work space 2 n x nrhs elements.
+ * Host-buffer forms lsx_potrf_* / lsx_potrs_* / lsx_posv_*: copy in, compute, copy out, like lsx_gesv_*; each 128-row
+ * block row is moved from its first diagonal column on (inside a diagonal block the elements below the diagonal make the
+ * round trip unchanged).  lsx_posv_*: A is not modified, B is overwritten by X, *info as above (may be NULL); with
+ * info > 0 B is left untouched.
+ * Arguments as lsx_getrs_*: lda >= n, ldb >= nrhs; n == 0 or nrhs == 0 is LSX_OK with nothing touched; pointers must be
+ * non-NULL otherwise.  Any alignment and any leading dimension: 16-byte forms where the operands allow, element-wise
+ * forms otherwise, same bits.  Deterministic: two calls give identical bits.  (Nothing is promised about a column's
+ * bits being independent of the columns passed with it: the backward sweep may pick kernels by nrhs.)
+ * Numeric domain: the power-of-two note of lsx_getrf_* does not carry over unexamined (sqrt halves exponents: A 4^d
+ * scales U by 2^d, an odd power of two does not scale it by a power of two).  What holds: the factorisation itself
+ * forms the reciprocal of every u_jj, and both it and lsx_potrs_* form inverses of 128 x 128 diagonal blocks of U, so
+ * every u_jj needs a reciprocal that is a finite number, as the LU solves already require of their pivots. */
+int lsx_potrf_f64_dev(lsx_handle_t h, int n, double *dA, int lda, int *d_info);
+int lsx_potrf_f32_dev(lsx_handle_t h, int n, float *dA, int lda, int *d_info);
+int lsx_potrs_f64_dev(lsx_handle_t h, int n, int nrhs, const double *dU, int lda, double *dB, int ldb);
+int lsx_potrs_f32_dev(lsx_handle_t h, int n, int nrhs, const float *dU, int lda, float *dB, int ldb);
+int lsx_potrf_f64(lsx_handle_t h, int n, double *A, int lda, int *info);
+int lsx_potrf_f32(lsx_handle_t h, int n, float *A, int lda, int *info);
+int lsx_potrs_f64(lsx_handle_t h, int n, int nrhs, const double *U, int lda, double *B, int ldb);
+int lsx_potrs_f32(lsx_handle_t h, int n, int nrhs, const float *U, int lda, float *B, int ldb);
+int lsx_posv_f64(lsx_handle_t h, int n, int nrhs, const double *A, int lda, double *B, int ldb, int *info);
+int lsx_posv_f32(lsx_handle_t h, int n, int nrhs, const float *A, int lda, float *B, int ldb, int *info);
+/* The trailing update on its own: the upper triangle of dC (n x n) -= dA^T * dA with dA stored k x n, row-major,
+ * lda >= n, ldc >= n.  The strictly lower triangle of dC is neither read nor written.  k is taken in ascending order and
+ * the tiles above the diagonal take the forms lsx_gemm_tn_sub_*_dev(n, n, k, dA, lda, dA, lda, dC, ldc) gives them, so
+ * every element of the upper triangle has the bits of that call.  A zero extent leaves dC untouched (pointers may then
+ * be NULL); LSX_ERR_ARG for negative sizes, lda < n, ldc < n or a NULL pointer with non-zero sizes. */
+int lsx_syrk_tn_sub_f64_dev(lsx_handle_t h, int n, int k, const double *dA, int lda, double *dC, int ldc);
+int lsx_syrk_tn_sub_f32_dev(lsx_handle_t h, int n, int k, const float *dA, int lda, float *dC, int ldc);
+
 /* ---- device-pointer entry points (asynchronous on the handle's stream) ---- */
 /* d_info: device int (may be NULL).  d_ipiv: device int32[n].
  * *d_info < 0 after the call means the in-kernel pivot exchange timed out (LSX_ERR_INTERNAL

@@ -112,6 +112,18 @@ _SIGS = {
     "lsx_gemm_tn_sub_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i],
     "lsx_gemm_tn_sub_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i],
     "lsx_gemm_tn_add_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i],
+    "lsx_potrf_f64_dev": [_vp, _i, _vp, _i, _vp],
+    "lsx_potrf_f32_dev": [_vp, _i, _vp, _i, _vp],
+    "lsx_potrs_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _i],
+    "lsx_potrs_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _i],
+    "lsx_potrf_f64": [_vp, _i, _dp, _i, C.POINTER(_i)],
+    "lsx_potrf_f32": [_vp, _i, _fp, _i, C.POINTER(_i)],
+    "lsx_potrs_f64": [_vp, _i, _i, _dp, _i, _dp, _i],
+    "lsx_potrs_f32": [_vp, _i, _i, _fp, _i, _fp, _i],
+    "lsx_posv_f64": [_vp, _i, _i, _dp, _i, _dp, _i, C.POINTER(_i)],
+    "lsx_posv_f32": [_vp, _i, _i, _fp, _i, _fp, _i, C.POINTER(_i)],
+    "lsx_syrk_tn_sub_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _i],
+    "lsx_syrk_tn_sub_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _i],
     "lsx_matmul_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i],
     "lsx_fill_f64_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],
     "lsx_fill_f32_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],

@@ -896,6 +896,162 @@ static int gemm_tn_dev(lsx_handle_t h, int plus, int m, int n, int k, const T *d
     return launch_gemm_tn_acc<T>(h, plus, m, n, k, dA, lda, dB, ldb, dC, ldc);
 }
 
+// ---------------------------------------------------------------- Cholesky: A = U^T U, row-major, upper
+// Right-looking over 128-row steps on one stream, no look-ahead:
+//   U11, inv(U11)     <- the diagonal block, one workgroup (kernels_chol.hip)                      [PANEL]
+//   U12 = inv(U11)^T A12: the TN tile in its C = A^T B mode; it cannot run in place, so A12 is copied to a
+//                        jb x rest work strip and multiplied back                                   [TRSM]
+//   A22(upper) -= U12^T U12: the TN tile over the tiles on and above the diagonal only               [GEMM]
+// The info word lives in the work space (the caller's may be null) and is copied out at the end.  After a failed pivot
+// the later diagonal launches see the word and write an identity for the strip product, which then runs on the
+// untouched strip: nothing waits, nothing faults, and the leading rows stay as they were.
+template <typename T>
+static int potrf_dev(lsx_handle_t h, int n, T *A, int lda, int *d_info) {
+    LSX_ARG(h && n >= 0 && lda >= n);
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A);
+    const int sb = 128, ldw = ld_for(n);
+    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, 256 + pad256(sizeof(T) * sb * sb)));
+    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(T) * (size_t)sb * ldw)));
+    int *winfo = (int *)h->ws2;
+    T *Vinv = (T *)((char *)h->ws2 + 256);
+    T *W = (T *)h->ws3;
+    LSX_HIP(hipMemsetAsync(winfo, 0, sizeof(int), h->stream));
+    for (int kb = 0; kb < n; kb += sb) {
+        const int jb = (n - kb < sb) ? n - kb : sb, rest = n - kb - jb;
+        T *Akk = A + (size_t)kb * lda + kb, *A12 = Akk + jb, *A22 = A12 + (size_t)jb * lda;
+        LSX_TRY(launch_chol_diag<T>(h, jb, Akk, lda, kb, Vinv, winfo));
+        if (rest <= 0) break;
+        {
+            ProfScope ps(h, LSX_PROF_TRSM, 0, 2.0 * sizeof(T) * jb * (double)rest);
+            LSX_TRY(launch_copy2d<T>(h, jb, rest, A12, lda, W, ldw));
+        }
+        LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, rest, jb, Vinv, sb, W, ldw, A12, lda, LSX_PROF_TRSM));
+        LSX_TRY(launch_syrk_tn_sub<T>(h, rest, jb, A12, lda, A22, lda));
+    }
+    if (d_info) LSX_HIP(hipMemcpyAsync(d_info, winfo, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    return LSX_OK;
+}
+
+// B <- inv(U) inv(U^T) B: the U half of lu_solve_transposed_blocked (U^T Y = B on the TN tile), then sweep_backward
+// (U X = Y).  The block inverses come from the upper triangle alone (launch_chol_inv): what lies below the diagonal of
+// the factor array is never loaded, it may hold anything.  Every nrhs >= 1 takes these sweeps.
+template <typename T>
+static int potrs_dev(lsx_handle_t h, int n, int nrhs, const T *U, int lda, T *B, int ldb) {
+    LSX_ARG(h && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs);
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(U && B);
+    const int sb = 128, ldw = ld_for(nrhs);
+    const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
+    const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
+    const size_t arr = pad256(sizeof(T) * (size_t)n * ldw);
+    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, b64 + b128));
+    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, 2 * arr));
+    T *inv64 = (T *)h->ws2, *inv128 = (T *)((char *)h->ws2 + b64);
+    T *W = (T *)h->ws3, *Y = (T *)((char *)h->ws3 + arr);
+    auto Up = [&](int r, int c) { return U + (size_t)r * lda + c; };
+    auto Wp = [&](int r) { return W + (size_t)r * ldw; };
+    auto Yp = [&](int r) { return Y + (size_t)r * ldw; };
+    LSX_TRY(launch_chol_inv<T>(h, n, U, lda, inv64, inv128));
+    LSX_TRY(launch_copy2d<T>(h, n, nrhs, B, ldb, W, ldw));
+    for (int kb = 0; kb < n; kb += sb) {
+        const int jb = (n - kb < sb) ? n - kb : sb;
+        LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nrhs, jb, inv128 + (size_t)(kb / sb) * sb * sb, sb, Wp(kb), ldw, Yp(kb), ldw));
+        LSX_TRY(launch_gemm_tn_sub<T>(h, n - kb - jb, nrhs, jb, Up(kb, kb + jb), lda, Yp(kb), ldw, Wp(kb + jb), ldw));
+    }
+    LSX_TRY(sweep_backward<T>(h, n, nrhs, sweep_pairs(h, n, nrhs), U, lda, inv64, Y, ldw));
+    return launch_copy2d<T>(h, n, nrhs, Y, ldw, B, ldb);
+}
+
+// Host <-> device traffic of the upper form: block row kb moves from its first diagonal column on, so nothing left
+// of the diagonal blocks is touched on either side (inside a diagonal block the elements below the diagonal make the
+// round trip unchanged; no kernel loads them).
+template <typename T>
+static int upper_h2d(lsx_handle_t h, int n, const T *A, int lda, T *dA, int ld) {
+    for (int kb = 0; kb < n; kb += 128)
+        LSX_TRY(h2d<T>(h, std::min(128, n - kb), n - kb, A + (size_t)kb * lda + kb, lda, dA + (size_t)kb * ld + kb, ld));
+    return LSX_OK;
+}
+template <typename T>
+static int upper_d2h(lsx_handle_t h, int n, const T *dA, int ld, T *A, int lda) {
+    for (int kb = 0; kb < n; kb += 128)
+        LSX_TRY(d2h<T>(h, std::min(128, n - kb), n - kb, dA + (size_t)kb * ld + kb, ld, A + (size_t)kb * lda + kb, lda));
+    return LSX_OK;
+}
+
+template <typename T>
+static int potrf_host(lsx_handle_t h, int n, T *A, int lda, int *info) {
+    LSX_ARG(h && n >= 0 && lda >= n);
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A);
+    if (info) *info = 0;
+    const int ld = ld_for(n);
+    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + 512));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    int *dinfo = c.take<int>(1);
+    int hinfo = 0;
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
+    LSX_TRY(potrf_dev<T>(h, n, dA, ld, dinfo));
+    LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LSX_TRY(upper_d2h<T>(h, n, dA, ld, A, lda));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (info) *info = hinfo;
+    return LSX_OK;
+}
+
+template <typename T>
+static int potrs_host(lsx_handle_t h, int n, int nrhs, const T *U, int lda, T *B, int ldb) {
+    LSX_ARG(h && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs);
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(U && B);
+    const int ld = ld_for(n), ldx = ld_for(nrhs);
+    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(T) * (size_t)n * ldx) + 512));
+    Carver c(h->ws);
+    T *dU = c.take<T>((size_t)n * ld);
+    T *dB = c.take<T>((size_t)n * ldx);
+    LSX_TRY(upper_h2d<T>(h, n, U, lda, dU, ld));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
+    LSX_TRY(potrs_dev<T>(h, n, nrhs, dU, ld, dB, ldx));
+    LSX_TRY(d2h<T>(h, n, nrhs, dB, ldx, B, ldb));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+template <typename T>
+static int posv_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, T *B, int ldb, int *info) {
+    LSX_ARG(h && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs);
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(A && B);
+    if (info) *info = 0;
+    const int ld = ld_for(n), ldx = ld_for(nrhs);
+    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(T) * (size_t)n * ldx) + 512));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    T *dB = c.take<T>((size_t)n * ldx);
+    int *dinfo = c.take<int>(1);
+    int hinfo = 0;
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
+    LSX_TRY(potrf_dev<T>(h, n, dA, ld, dinfo));
+    LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (info) *info = hinfo;
+    if (hinfo != 0) return LSX_OK;   // not positive definite: B is left untouched
+    LSX_TRY(potrs_dev<T>(h, n, nrhs, dA, ld, dB, ldx));
+    LSX_TRY(d2h<T>(h, n, nrhs, dB, ldx, B, ldb));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+template <typename T>
+static int syrk_tn_dev(lsx_handle_t h, int n, int k, const T *dA, int lda, T *dC, int ldc) {
+    LSX_ARG(h && n >= 0 && k >= 0 && lda >= n && ldc >= n);
+    if (n == 0 || k == 0) return LSX_OK;
+    LSX_ARG(dA && dC);
+    return launch_syrk_tn_sub<T>(h, n, k, dA, lda, dC, ldc);
+}
+
 // A^T X = B from the factors (kernels_trsvt.hip).  Work space as in getrs_dev, so the two share what they grow.
 // may_block = false: the single-column solves inside the estimators, which keep the grouped path whatever the option says.
 template <typename T>
@@ -2427,6 +2583,36 @@ int lsx_gemm_tn_sub_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dA
     LSX_DEVICE_GUARD(h);
     return gemm_tn_dev<float>(h, 0, m, n, k, dA, lda, dB, ldb, dC, ldc);
 }
+
+// ---- Cholesky
+#define LSX_CHOL_ENTRIES(SFX, T)                                                                                          \
+    int lsx_potrf_##SFX##_dev(lsx_handle_t h, int n, T *dA, int lda, int *d_info) {                                       \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return potrf_dev<T>(h, n, dA, lda, d_info);                                                                       \
+    }                                                                                                                     \
+    int lsx_potrs_##SFX##_dev(lsx_handle_t h, int n, int nrhs, const T *dU, int lda, T *dB, int ldb) {                    \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return potrs_dev<T>(h, n, nrhs, dU, lda, dB, ldb);                                                                \
+    }                                                                                                                     \
+    int lsx_syrk_tn_sub_##SFX##_dev(lsx_handle_t h, int n, int k, const T *dA, int lda, T *dC, int ldc) {                 \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return syrk_tn_dev<T>(h, n, k, dA, lda, dC, ldc);                                                                 \
+    }                                                                                                                     \
+    int lsx_potrf_##SFX(lsx_handle_t h, int n, T *A, int lda, int *info) {                                                \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return potrf_host<T>(h, n, A, lda, info);                                                                         \
+    }                                                                                                                     \
+    int lsx_potrs_##SFX(lsx_handle_t h, int n, int nrhs, const T *U, int lda, T *B, int ldb) {                            \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return potrs_host<T>(h, n, nrhs, U, lda, B, ldb);                                                                 \
+    }                                                                                                                     \
+    int lsx_posv_##SFX(lsx_handle_t h, int n, int nrhs, const T *A, int lda, T *B, int ldb, int *info) {                  \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return posv_host<T>(h, n, nrhs, A, lda, B, ldb, info);                                                            \
+    }
+LSX_CHOL_ENTRIES(f64, double)
+LSX_CHOL_ENTRIES(f32, float)
+#undef LSX_CHOL_ENTRIES
 
 int lsx_fill_f64_dev(lsx_handle_t h, int kind, uint64_t seed, int m, int n, double *dA, int lda,
                      int row_off, int col_off) {

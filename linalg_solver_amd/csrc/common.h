@@ -269,10 +269,14 @@ int launch_gemm_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, co
 template <typename T>
 int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, int lda, const T *B, int ldb,
                     T *C, int ldc, const GemmPlan &plan = GemmPlan(), GemmDone *done = nullptr);
-// TN form on the same tile, A stored k x m: C -= A^T*B (mode 0), C += A^T*B (1), C = A^T*B (3)
+// TN form on the same tile, A stored k x m: C -= A^T*B (mode 0), C += A^T*B (1), C = A^T*B (3); bucket: where the
+// launch is accounted (the Cholesky strip product counts as a block solve)
 template <typename T>
 int launch_gemm_tn_acc(lsx_handle_t h, int mode, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C,
-                       int ldc);
+                       int ldc, int bucket = LSX_PROF_GEMM);
+// upper triangle of C (n x n) -= A^T*A, A stored k x n; the strictly lower triangle of C is neither read nor written
+template <typename T>
+int launch_syrk_tn_sub(lsx_handle_t h, int n, int k, const T *A, int lda, T *C, int ldc);
 template <typename T>
 int launch_gemm_tn_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C, int ldc);
 // traced reference-order row reduction (kernels_trace.hip); d_out = {pivots, steps, overflow}
@@ -407,5 +411,15 @@ int diag_xchg_probe(lsx_handle_t h, int mode, int G, int stride, int wt, int epo
                     int *xcc_ids, int *nfail);
 template <typename T>
 int launch_copy2d(lsx_handle_t h, int m, int n, const T *S, int lds, T *D, int ldd);
+// Cholesky (kernels_chol.hip).  launch_chol_diag: the jb x jb (jb <= 128) upper diagonal block at A is factored in
+// place, A = U^T U, and inv(U) goes to Vinv (128 x 128, natural orientation, identity outside the block); col0 = the
+// block's first column in the whole matrix, *info (never null) = 0 on entry or the launch does nothing but write the
+// identity to Vinv; a pivot <= 0 or NaN at local row j sets *info = col0 + j + 1.
+// launch_chol_inv: for every 128-row diagonal block of the upper factor U, inv128[blk] (natural orientation, identity
+// outside the matrix) and its two 64 x 64 diagonal blocks in the layout of launch_trtri (inv64[kb / 64]).
+template <typename T>
+int launch_chol_diag(lsx_handle_t h, int jb, T *A, int lda, int col0, T *Vinv, int *info);
+template <typename T>
+int launch_chol_inv(lsx_handle_t h, int n, const T *U, int lda, T *inv64, T *inv128);
 
 }  // namespace lsx

@@ -78,7 +78,11 @@ struct ASlab {
 // into the same AS_AT layout: a wave writes one k-row of 128 consecutive elements, which no pair stride can make
 // conflict.  The MFMA loop and the C traffic are those of the plain form.  plus bit 1 (TA only): the accumulators
 // start from zero instead of from C, so plus = 3 is C = A^T * B.
-template <typename T, bool FULL, int NWN, int BM_, bool TA = false>
+// TRI: the tile belongs to a symmetric update of which the upper triangle alone is kept: elements of C with col < row
+// are neither loaded nor stored (their accumulators start from zero and are dropped), the others go through exactly the
+// operations of the plain form.  With FULL the k-slabs keep their unpredicated 16-byte loads and only the C traffic
+// goes element by element (a diagonal tile among the complete ones).
+template <typename T, bool FULL, int NWN, int BM_, bool TA = false, bool TRI = false>
 __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__restrict__ A, int lda,
                                               const T *__restrict__ B, int ldb, T *__restrict__ C, int ldc,
                                               int m0, int n0, T (*As)[BK / 2][ASlab<T, BM_>::PAIR], T (*Bs)[BK][BN + LPAD],
@@ -201,16 +205,16 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
 #pragma unroll
             for (int t = 0; t < TN; ++t) v[t] = T(0);
             if (from_zero) {
-            } else if (FULL) {
+            } else if (FULL && !TRI) {
 #pragma unroll
                 for (int t = 0; t < TN; t += 2) {
                     const v2 x = *(const v2 *)(p + t);
                     v[t] = x[0]; v[t + 1] = x[1];
                 }
-            } else if (row < M) {
+            } else if (FULL || row < M) {
 #pragma unroll
                 for (int t = 0; t < TN; ++t)
-                    if (col + t < N) v[t] = p[t];
+                    if ((FULL || col + t < N) && (!TRI || col + t >= row)) v[t] = p[t];
             }
 #pragma unroll
             for (int t = 0; t < TN; ++t) acc[s][t][r] = v[t];
@@ -255,17 +259,17 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
             const int row = m0 + wm + 16 * s + Mfma<T>::crow(lane_e, r);
             const int col = n0 + wn + TN * lc_e;
             T *p = C + (size_t)row * ldc + col;
-            if (FULL) {
+            if (FULL && !TRI) {
 #pragma unroll
                 for (int t = 0; t < TN; t += 2) {
                     v2 x;
                     x[0] = acc[s][t][r]; x[1] = acc[s][t + 1][r];
                     *(v2 *)(p + t) = x;
                 }
-            } else if (row < M) {
+            } else if (FULL || row < M) {
 #pragma unroll
                 for (int t = 0; t < TN; ++t)
-                    if (col + t < N) p[t] = acc[s][t][r];
+                    if ((FULL || col + t < N) && (!TRI || col + t >= row)) p[t] = acc[s][t][r];
             }
         }
 }
@@ -350,6 +354,72 @@ __global__ __launch_bounds__(BM * NWN, (sizeof(T) == 4 && NWN == 4) ? 6 : NWN) v
     grouped_tile((int)blockIdx.x, tiles_m * tiles_n, tiles_m, tiles_n, tile_m, tile_n);
     gemm_sub_tile<T, FULL, NWN, BM, true>(M, N, K, A, lda, B, ldb, C, ldc, (tile_m + tm_off) * BM, (tile_n + tn_off) * BN, As,
                                           Bs, plus & 3);
+}
+
+// Symmetric rank-k update in the TN form, upper triangle only: C (N x N) -= A^T * A with A stored K x N, for the trailing
+// update of the Cholesky factorisation (api.hip, potrf_dev).  Only tiles with tile_n >= tile_m exist in the grid.
+// upper_tile: place `bid` of nwg in the sequence over the tiles (tile_m, tile_n), tile_n >= tile_m, of a
+// tiles x tiles grid -- the order of grouped_tile (workgroups of one XCD take consecutive places; bands of 8 tile rows
+// walked column by column) with the tiles left of the diagonal left out.  Column first + c of a band holds
+// min(c + 1, gsize) tiles: a triangular head of gsize (gsize - 1) / 2 tiles, then complete columns.
+__device__ __forceinline__ void upper_tile(int bid, int nwg, int tiles, int &tile_m, int &tile_n) {
+    {
+        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+    }
+    constexpr int GROUP = 8;
+    tile_m = tile_n = 0;
+    for (int first = 0; first < tiles; first += GROUP) {
+        const int gsize = min(tiles - first, GROUP);
+        const int head = gsize * (gsize - 1) / 2;
+        const int col_full = first + gsize - 1;   // first column that holds all gsize rows of the band
+        const int band = head + gsize * (tiles - col_full);
+        if (bid < band) {
+            if (bid < head) {
+                int c = 0;
+                while (bid > c) { bid -= c + 1; ++c; }
+                tile_n = first + c;
+                tile_m = first + bid;
+            } else {
+                bid -= head;
+                tile_n = col_full + bid / gsize;
+                tile_m = first + bid % gsize;
+            }
+            return;
+        }
+        bid -= band;
+    }
+}
+
+// FULL = true: the tiles on and above the diagonal among the `full` x `full` complete, aligned tiles.  Above the
+// diagonal: the instantiation of gemm_sub_tile that launch_gemm_tn_acc's interior kernel uses; on the diagonal: the same
+// 16-byte slab loads with the C traffic element by element under the predicate col >= row.
+// FULL = false: every other tile on or above the diagonal, bounds-checked, with the same predicate (true everywhere off
+// the diagonal): all of them when full == 0, else the ragged last tile column (rows 0 .. full - 1) and its diagonal
+// tile.  k ascending in every form, so an element of the upper triangle gets the bits the full product gives it;
+// nothing below the diagonal is read or written.
+template <typename T, int NWN, bool FULL>
+__global__ __launch_bounds__(BM * NWN, (sizeof(T) == 4 && NWN == 4) ? 6 : NWN) void gemm_tn_upper_kernel(
+    int N, int K, const T *__restrict__ A, int lda, T *__restrict__ C, int ldc, int tiles, int full) {
+    __shared__ T As[2][BK / 2][ASlab<T, BM>::PAIR];  // AS_AT(buf, k, m) = -A[k][m]
+    __shared__ T Bs[2][BK][BN + LPAD];
+    const int bid = (int)blockIdx.x;
+    int tile_m, tile_n;
+    if (FULL) {
+        upper_tile(bid, (int)gridDim.x, full, tile_m, tile_n);
+        if (tile_m == tile_n)
+            gemm_sub_tile<T, true, NWN, BM, true, true>(N, N, K, A, lda, A, lda, C, ldc, tile_m * BM, tile_n * BN, As, Bs, 0);
+        else
+            gemm_sub_tile<T, true, NWN, BM, true, false>(N, N, K, A, lda, A, lda, C, ldc, tile_m * BM, tile_n * BN, As, Bs, 0);
+        return;
+    }
+    if (full == 0) {
+        upper_tile(bid, (int)gridDim.x, tiles, tile_m, tile_n);
+    } else {   // tiles == full + 1: the last tile column
+        tile_m = bid;
+        tile_n = full;
+    }
+    gemm_sub_tile<T, false, NWN, BM, true, true>(N, N, K, A, lda, A, lda, C, ldc, tile_m * BM, tile_n * BN, As, Bs, 0);
 }
 
 // The same interior tiles handed out by a work queue instead of one workgroup per tile: the look-ahead driver
@@ -537,10 +607,10 @@ int launch_gemm_acc(lsx_handle_t h, int plus, int m, int n, int k, const T *A, i
 // column of C has the same bits whatever the other columns of the call are.
 template <typename T>
 int launch_gemm_tn_acc(lsx_handle_t h, int mode, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C,
-                       int ldc) {
+                       int ldc, int bucket) {
     if (m <= 0 || n <= 0 || (k <= 0 && mode != 3)) return LSX_OK;
     if (k < 0) k = 0;
-    ProfScope ps(h, LSX_PROF_GEMM, 2.0 * m * n * (double)k, (mode == 3 ? 1.0 : 2.0) * sizeof(T) * m * (double)n);
+    ProfScope ps(h, bucket, 2.0 * m * n * (double)k, (mode == 3 ? 1.0 : 2.0) * sizeof(T) * m * (double)n);
     const int tm = (m + BM - 1) / BM, tn = (n + BN - 1) / BN;
     const int elems16 = 16 / (int)sizeof(T);
     const bool aligned = ((size_t)A % 16 == 0) && ((size_t)B % 16 == 0) && ((size_t)C % 16 == 0) && (lda % elems16 == 0) &&
@@ -561,7 +631,27 @@ int launch_gemm_tn_acc(lsx_handle_t h, int mode, int m, int n, int k, const T *A
 
 template <typename T>
 int launch_gemm_tn_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C, int ldc) {
-    return launch_gemm_tn_acc<T>(h, 0, m, n, k, A, lda, B, ldb, C, ldc);
+    return launch_gemm_tn_acc<T>(h, 0, m, n, k, A, lda, B, ldb, C, ldc, LSX_PROF_GEMM);
+}
+
+// upper triangle of C (n x n) -= A^T A, A stored k x n: the tiles on and above the diagonal only (gemm_tn_upper_kernel)
+template <typename T>
+int launch_syrk_tn_sub(lsx_handle_t h, int n, int k, const T *A, int lda, T *C, int ldc) {
+    if (n <= 0 || k <= 0) return LSX_OK;
+    ProfScope ps(h, LSX_PROF_GEMM, (double)n * n * (double)k, sizeof(T) * (double)n * n);
+    const int t = (n + BM - 1) / BM;
+    const int elems16 = 16 / (int)sizeof(T);
+    const bool aligned = ((size_t)A % 16 == 0) && ((size_t)C % 16 == 0) && (lda % elems16 == 0) && (ldc % elems16 == 0) &&
+                         (k % BK == 0);
+    const int f = aligned ? n / BM : 0;   // complete tiles per side: the interior of launch_gemm_tn_acc
+    constexpr int NWN = sizeof(T) == 8 ? 4 : 2;
+    if (f > 0)
+        hipLaunchKernelGGL((gemm_tn_upper_kernel<T, NWN, true>), dim3(f * (f + 1) / 2), dim3(BM * NWN), 0, h->stream, n, k, A, lda, C, ldc, t, f);
+    const int edge = f == 0 ? t * (t + 1) / 2 : (t > f ? f + 1 : 0);
+    if (edge > 0)
+        hipLaunchKernelGGL((gemm_tn_upper_kernel<T, NWN, false>), dim3(edge), dim3(BM * NWN), 0, h->stream, n, k, A, lda, C, ldc, t, f);
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
 }
 
 template <typename T>
@@ -574,8 +664,10 @@ template int launch_gemm_acc<double>(lsx_handle_t, int, int, int, int, const dou
                                      int, double *, int, const GemmPlan &, GemmDone *);
 template int launch_gemm_acc<float>(lsx_handle_t, int, int, int, int, const float *, int, const float *, int,
                                     float *, int, const GemmPlan &, GemmDone *);
-template int launch_gemm_tn_acc<double>(lsx_handle_t, int, int, int, int, const double *, int, const double *, int, double *, int);
-template int launch_gemm_tn_acc<float>(lsx_handle_t, int, int, int, int, const float *, int, const float *, int, float *, int);
+template int launch_gemm_tn_acc<double>(lsx_handle_t, int, int, int, int, const double *, int, const double *, int, double *, int, int);
+template int launch_gemm_tn_acc<float>(lsx_handle_t, int, int, int, int, const float *, int, const float *, int, float *, int, int);
+template int launch_syrk_tn_sub<double>(lsx_handle_t, int, int, const double *, int, double *, int);
+template int launch_syrk_tn_sub<float>(lsx_handle_t, int, int, const float *, int, float *, int);
 template int launch_gemm_tn_sub<double>(lsx_handle_t, int, int, int, const double *, int, const double *, int, double *, int);
 template int launch_gemm_tn_sub<float>(lsx_handle_t, int, int, int, const float *, int, const float *, int, float *, int);
 template int launch_gemm_sub<double>(lsx_handle_t, int, int, int, const double *, int,

@@ -48,6 +48,44 @@ def lu_factor(a, handle: Optional[N.Handle] = None, dtype=np.float64) -> Tuple[n
     return LU, ipiv[:n], info.value
 
 
+def cho_factor(a, handle: Optional[N.Handle] = None, dtype=np.float64) -> Tuple[np.ndarray, int]:
+    """Cholesky factorisation A = U^T U of a symmetric positive definite matrix (lsx_potrf_*).  Only the upper triangle
+    of a is used; symmetry is not checked.  Returns (U, info): U is upper triangular with zeros below the diagonal;
+    info = j + 1 says the leading minor of order j + 1 is not positive definite (then only U[:j, :j] is meaningful)."""
+    ct, sfx = _ct(dtype)
+    U = np.array(a, dtype=dtype, order="C", copy=True)
+    n = U.shape[0]
+    if U.ndim != 2 or U.shape[1] != n:
+        raise ValueError("cho_factor needs a square matrix")
+    h = _h(handle)
+    info = C.c_int(0)
+    if n:
+        N.check(getattr(h.lib, f"lsx_potrf_{sfx}")(h.ptr, n, _ptr(U, ct), n, C.byref(info)), f"lsx_potrf_{sfx}")
+    return np.triu(U), info.value
+
+
+def cho_solve(U: np.ndarray, b, handle: Optional[N.Handle] = None) -> np.ndarray:
+    """Solve A X = B from the factor of cho_factor: X = inv(U) inv(U^T) B (lsx_potrs_*).  Only the upper triangle of U
+    is used."""
+    U = np.asarray(U)
+    if U.ndim != 2 or U.shape[0] != U.shape[1]:
+        raise ValueError("cho_solve needs the square factor matrix")
+    ct, sfx = _ct(U.dtype)
+    n = U.shape[0]
+    if np.shape(b)[:1] != (n,):
+        raise ValueError("right-hand side has the wrong number of rows")
+    h = _h(handle)
+    U = np.ascontiguousarray(U)
+    X = np.array(b, dtype=U.dtype, order="C", copy=True)
+    vec = X.ndim == 1
+    if vec:
+        X = X.reshape(n, 1).copy()
+    if n and X.shape[1]:
+        N.check(getattr(h.lib, f"lsx_potrs_{sfx}")(h.ptr, n, X.shape[1], _ptr(U, ct), n, _ptr(X, ct), X.shape[1]),
+                f"lsx_potrs_{sfx}")
+    return X[:, 0].copy() if vec else X
+
+
 def _norm_code(which) -> int:
     """1 / "1" / "one" -> the 1-norm (max column sum); inf / "inf" / "I" -> the infinity-norm (max row sum)."""
     if which in (1, "1", "one", "O", "o"):
@@ -97,9 +135,13 @@ def _solve_trans(h, A, X, dtype):
     return info, ratio
 
 
-def solve(a, b, handle: Optional[N.Handle] = None, dtype=np.float64, trans: bool = False):
+def solve(a, b, handle: Optional[N.Handle] = None, dtype=np.float64, trans: bool = False, assume_pos: bool = False):
     """Solve A X = B (trans=True: A^T X = B, from the factors of A -- no transposed copy, no second
-    factorisation).  Returns (X, info, pivot_ratio); X is None when info != 0."""
+    factorisation).  Returns (X, info, pivot_ratio); X is None when info != 0.
+    assume_pos=True: A is symmetric positive definite and goes through the Cholesky factorisation (lsx_posv_*: no
+    pivoting, half the work).  Only the upper triangle of a is used and symmetry is not checked; trans makes no
+    difference; info = j + 1 says the leading minor of order j + 1 is not positive definite; pivot_ratio is 1.0
+    (nothing is pivoted)."""
     A = np.ascontiguousarray(a, dtype=dtype)
     n = A.shape[0]
     if A.ndim != 2 or A.shape[1] != n:
@@ -113,6 +155,17 @@ def solve(a, b, handle: Optional[N.Handle] = None, dtype=np.float64, trans: bool
         X = X.reshape(n, 1).copy()
     if X.shape[0] != n:
         raise ValueError("right-hand side has the wrong number of rows")
+    if assume_pos:
+        ct, sfx = _ct(dtype)
+        pinfo = C.c_int(0)
+        if n and X.shape[1]:
+            N.check(getattr(h.lib, f"lsx_posv_{sfx}")(h.ptr, n, X.shape[1], _ptr(A, ct), n, _ptr(X, ct), X.shape[1],
+                                                       C.byref(pinfo)), f"lsx_posv_{sfx}")
+        elif n:
+            pinfo = C.c_int(cho_factor(A, h, dtype)[1])
+        if pinfo.value != 0:
+            return None, pinfo.value, 1.0
+        return (X[:, 0].copy() if vec else X), 0, 1.0
     if trans:
         _ct(dtype)
         tinfo, tratio = _solve_trans(h, A, X, dtype)

@@ -74,6 +74,52 @@ class DeviceSolver:
                                         B.data_ptr(), B.stride(0)), name)
         return B
 
+    def potrf_(self, A: torch.Tensor, info: Optional[torch.Tensor] = None):
+        """In-place Cholesky factorisation A = U^T U of a symmetric positive definite matrix in HBM, upper storage
+        (lsx_potrf_*_dev): the upper triangle of A is overwritten by U, the strictly lower triangle is neither read
+        nor written.  Returns info (int32[1] device tensor: 0, or j + 1 for the first non-positive pivot); no host
+        sync."""
+        _rowmajor(A, "potrf_")
+        n = A.shape[0]
+        if A.shape[1] != n:
+            raise ValueError("potrf_ needs a square matrix")
+        if info is None:
+            info = torch.zeros(1, dtype=torch.int32, device=A.device)
+        elif info.dtype != torch.int32 or info.device != A.device or info.numel() < 1 or not info.is_contiguous():
+            raise ValueError("potrf_: info must be a contiguous int32 tensor with at least one entry on A's device")
+        name = f"lsx_potrf_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, n, A.data_ptr(), max(A.stride(0), 1), info.data_ptr()), name)
+        return info
+
+    def potrs_(self, U: torch.Tensor, B: torch.Tensor):
+        """B <- inv(U) inv(U^T) B in place from the factor of potrf_ (lsx_potrs_*_dev); only the upper triangle of U
+        is read."""
+        _rowmajor(U, "potrs_")
+        _rowmajor(B, "potrs_")
+        if U.shape[0] != U.shape[1] or B.shape[0] != U.shape[0]:
+            raise ValueError("potrs_: need the square factor and a right-hand side with as many rows")
+        if B.dtype != U.dtype:
+            raise TypeError("potrs_: factor and right-hand side must have the same dtype")
+        name = f"lsx_potrs_{self._suffix(U)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, U.shape[0], B.shape[1], U.data_ptr(), max(U.stride(0), 1),
+                                        B.data_ptr(), max(B.stride(0), 1)), name)
+        return B
+
+    def syrk_tn_sub_(self, C: torch.Tensor, A: torch.Tensor):
+        """Upper triangle of C (n x n) -= A.T @ A with A stored k x n, on the MFMA kernel; the strictly lower triangle
+        of C is untouched (lsx_syrk_tn_sub_*_dev)."""
+        _rowmajor(C, "syrk_tn_sub_ C")
+        _rowmajor(A, "syrk_tn_sub_ A")
+        k, n = A.shape
+        if tuple(C.shape) != (n, n):
+            raise ValueError("syrk_tn_sub_: need A (k x n) and C (n x n)")
+        if A.dtype != C.dtype:
+            raise TypeError("syrk_tn_sub_: both operands must have the same dtype")
+        name = f"lsx_syrk_tn_sub_{self._suffix(C)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, n, k, A.data_ptr(), max(A.stride(0), 1), C.data_ptr(),
+                                        max(C.stride(0), 1)), name)
+        return C
+
     @staticmethod
     def _norm_code(which) -> int:
         if which in (1, "1", "one", "O", "o"):

@@ -395,7 +395,74 @@ class Matrix:
             return (X[:, 0], float(ferr[0]), float(berr[0])) if bounds else X[:, 0]
         return (X, ferr, berr) if bounds else X
 
-    def solve_array(self, rhs, trans: bool = False, bounds: bool = False, equilibrate: bool = False):
+    @staticmethod
+    def _not_pos_def(info: int) -> ValueError:
+        return ValueError(f"matrix is not positive definite: its leading minor of order {info} is not (pos_def=True "
+                          "was the caller's assertion; without it the system may well have a solution)")
+
+    def cholesky_array(self):
+        """The upper Cholesky factor U (self = U^T U, zeros below the diagonal) of a symmetric positive definite
+        matrix: an ndarray, or a device tensor for a matrix built from one.  Only the upper triangle of self is used;
+        symmetry is not checked.  ValueError when a leading minor is not positive definite."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            if A.shape[0] != A.shape[1]:
+                raise ValueError("cholesky_array needs a square matrix")
+            U = A.clone()
+            info = int(DeviceSolver(self._dev.device.index).potrf_(U).item()) if A.shape[0] else 0
+            if info != 0:
+                raise self._not_pos_def(info)
+            return U.triu()
+        A = self._array()
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("cholesky_array needs a square matrix")
+        U, info = dense.cho_factor(A)
+        if info != 0:
+            raise self._not_pos_def(info)
+        return U
+
+    def _solve_pos_def(self, rhs):
+        """solve_array(pos_def=True): Cholesky factorisation and solve (lsx_potrf_* / lsx_potrs_*, lsx_posv_*)."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            import torch
+
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            n = A.shape[0]
+            if A.shape[1] != n:
+                raise ValueError("solve_array needs a square matrix")
+            B = rhs if hasattr(rhs, "is_cuda") else torch.as_tensor(np.asarray(rhs, dtype=np.float64))
+            B = B.to(device=A.device, dtype=torch.float64)
+            vec = B.dim() == 1
+            if B.shape[0] != n:
+                raise ValueError("Matrix dimensions must match")
+            dev = DeviceSolver(self._dev.device.index)
+            U = A.clone()
+            info = int(dev.potrf_(U).item()) if n else 0
+            if info != 0:
+                raise self._not_pos_def(info)
+            X = B.reshape(n, -1).contiguous().clone()
+            if n and X.shape[1]:
+                dev.potrs_(U, X)
+            return X[:, 0] if vec else X
+        A = self._array()
+        n = A.shape[0]
+        if A.shape[1] != n:
+            raise ValueError("solve_array needs a square matrix")
+        B = np.asarray(rhs, dtype=np.float64)
+        vec = B.ndim == 1
+        if B.shape[0] != n:
+            raise ValueError("Matrix dimensions must match")
+        X, info, _ = dense.solve(A, B.reshape(n, -1), assume_pos=True)
+        if info != 0:
+            raise self._not_pos_def(info)
+        return X[:, 0] if vec else X
+
+    def solve_array(self, rhs, trans: bool = False, bounds: bool = False, equilibrate: bool = False,
+                    pos_def: bool = False):
         """Unique solution(s) of self * X = rhs for a square matrix (rhs: vector or matrix) as an ndarray;
         NoSolution() when the matrix is singular to working precision (use find_preimage_of for the
         general affine answer).  trans=True solves self^T * X = rhs (x * self = rhs^T for rows) from the factors of
@@ -406,7 +473,16 @@ class Matrix:
         then factor, solve, refine): a matrix that is merely badly scaled -- which the pivot-ratio rule calls singular
         -- is solved, and NoSolution() is LAPACK's criterion instead (an exactly zero pivot, or the reciprocal condition
         number of the EQUILIBRATED matrix below 2^-53).  With bounds=True ferr is LAPACK's, which after a column
-        scaling is divided by the scales' spread and can be vacuous (include/lsx.h); berr is not affected."""
+        scaling is divided by the scales' spread and can be vacuous (include/lsx.h); berr is not affected.
+        pos_def=True asserts that self is symmetric positive definite and takes the Cholesky factorisation (no pivoting,
+        half the work).  Only the upper triangle of self is used and symmetry is NOT checked.  trans is accepted and
+        makes no difference (self is symmetric); bounds=True or equilibrate=True with it is a ValueError.  If a leading
+        minor turns out not to be positive definite the assertion was false: ValueError naming the minor, not
+        NoSolution() -- the system may well have a solution."""
+        if pos_def:
+            if bounds or equilibrate:
+                raise ValueError("solve_array: pos_def=True cannot be combined with bounds=True or equilibrate=True")
+            return self._solve_pos_def(rhs)
         if equilibrate:
             return self._solve_equilibrated(rhs, trans, bounds)
         if bounds:

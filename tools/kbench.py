@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | gecon | gerfs | equil [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | gecon | gerfs | equil [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -416,6 +416,55 @@ def main():
                       f"(rounds: grouped {res['grouped'][0]:.3f}/{res['grouped'][1]:.3f} blocked {res['blocked'][0]:.3f}/"
                       f"{res['blocked'][1]:.3f} plain {res['plain'][0]:.3f}/{res['plain'][1]:.3f})", flush=True)
         dev.h.set_option("getrs_t_blocked_min", 64)
+    if "potrf" in args.what:
+        # Cholesky beside LU on the SAME symmetric positive definite matrix, same process: medians of two alternating
+        # rounds, the copy that restores the matrix timed on its own and subtracted.  Then one profiled factorisation
+        # for the split: diagonal block (panel), block row (trsm), trailing update (gemm).
+        for dt in (torch.float64, torch.float32):
+            for n in (4096, 8192):
+                G = torch.empty(n, n, dtype=dt, device="cuda")
+                dev.fill_(G, gen.U11, 1)
+                A0 = G @ G.t() / n + torch.eye(n, dtype=dt, device="cuda")   # plumbing: builds the input only
+                del G
+                A = A0.clone()
+                ipiv = torch.empty(n, dtype=torch.int32, device="cuda")
+                info = torch.zeros(1, dtype=torch.int32, device="cuda")
+                res = {}
+                for rnd in range(2):
+                    t_copy = timeit(lambda: A.copy_(A0), reps=7, warm=2)[1]
+
+                    def chol():
+                        A.copy_(A0)
+                        dev.potrf_(A, info)
+
+                    def lu():
+                        A.copy_(A0)
+                        dev.getrf_(A, ipiv, info)
+                    for name, fn in (("potrf", chol), ("getrf", lu)):
+                        res.setdefault(name, []).append(timeit(fn, reps=7, warm=2)[1] - t_copy)
+                        assert int(info.item()) == 0, (name, int(info.item()))
+                pf, gf = min(res["potrf"]), min(res["getrf"])
+                dev.h.prof_enable(True)
+                split = []
+                for _ in range(2):                      # the second pass is the warm one
+                    A.copy_(A0)
+                    torch.cuda.synchronize()
+                    dev.h.prof_reset()
+                    dev.potrf_(A, info)
+                    dev.h.synchronize()
+                    split = dev.h.prof_read()
+                dev.h.prof_enable(False)
+                tot = sum(v["ms"] for v in split.values()) or 1.0
+                nd = max(split["panel"]["launches"], 1)
+                print(f"potrf {str(dt)[6:]} n={n}: potrf {pf:.3f} ms ({n ** 3 / 3 / pf / 1e9:.1f} TFLOP/s)  getrf {gf:.3f} ms  "
+                      f"| potrf/getrf {pf / gf:.3f}  (rounds: potrf {res['potrf'][0]:.3f}/{res['potrf'][1]:.3f} getrf "
+                      f"{res['getrf'][0]:.3f}/{res['getrf'][1]:.3f}; copy {t_copy:.3f})", flush=True)
+                print(f"    profiled pass: diagonal {split['panel']['ms']:.3f} ms / {split['panel']['launches']} launches = "
+                      f"{split['panel']['ms'] / nd * 1e3:.1f} us each;  strip {split['trsm']['ms']:.3f} ms / "
+                      f"{split['trsm']['launches']};  update {split['gemm']['ms']:.3f} ms / {split['gemm']['launches']} "
+                      f"({split['gemm']['ms'] / tot * 100:.0f} % of the bracketed time, "
+                      f"{split['gemm']['flops'] / max(split['gemm']['ms'], 1e-9) / 1e9:.1f} TFLOP/s)", flush=True)
+                del A, A0
     if "gecon" in args.what:
         # the condition estimate beside the factorisation it follows (fp64, 1-norm; medians)
         for n in (1024, 4096, 8192):
