@@ -98,6 +98,9 @@ const char *lsx_last_error(void);
  *   "getrs_t_blocked_min"  transposed solve with n > 128: the smallest nrhs that takes the blocked sweeps on the MFMA
  *                   tile instead of groups of 8 columns; any value >= 1, 0 = never [64; measured break-even 32: DESIGN 3.4]
  *   "getrs_t_path"  (read only) 1 if the last lsx_getrs_t_* call on this handle took the blocked sweeps, else 0
+ *   "potrs_few_max" Cholesky solve: the largest nrhs that takes the few-column step kernels instead of the block
+ *                   sweeps; 0 .. 8, 0 = never [0; measurements: DESIGN 3.8]
+ *   "potrs_path"    (read only) 1 if the last lsx_potrs_* call on this handle took the few-column step kernels, else 0
  *   "gemm_waves", "gemm_stagger", "panel_rt", "panel_nt", "hybrid", "xrows_limit", "rref_blocked",
  *   "getri_structured"                      tuning / cross-check switches, see DESIGN.md
  *   "panel_spin_limit", "trsv_spin_limit", "chain_wait_limit"   bounded-spin limits (tests inject time-outs)
@@ -392,8 +395,11 @@ int lsx_gesvx_f32_dev(lsx_handle_t h, int equil, int trans, int n, int nrhs, flo
  * time-out outcome: nothing here is cooperative, no kernel waits on another workgroup, lsx_check_status has nothing to
  * report.  No look-ahead.
  * lsx_potrs_*_dev: B <- inv(U) inv(U^T) B, B n x nrhs row-major.  Any nrhs >= 1 goes through 128-row block sweeps on the
- * MFMA tile (U^T Y = B in the TN form, then U X = Y); a latency path for few right-hand sides like "trsv" = 2 of
- * lsx_getrs_* is out of scope: one right-hand side costs what 128 cost.  Extra work space 2 n x nrhs elements.
+ * MFMA tile (U^T Y = B in the TN form, then U X = Y): one right-hand side costs what 128 cost.  Extra work space
+ * 2 n x nrhs elements.  With the option "potrs_few_max" = m (0 .. 8, default 0) a call with 1 <= nrhs <= m takes the
+ * few-column path instead: one launch per 128-row block step and direction on a dense copy of the columns, the tiles read
+ * straight into registers, still nothing cooperative and no time-out outcome ("potrs_path" reads back which path the
+ * last call took).  The two paths round differently; each is deterministic.
  * Host-buffer forms lsx_potrf_* / lsx_potrs_* / lsx_posv_*: copy in, compute, copy out, like lsx_gesv_*; each 128-row
  * block row is moved from its first diagonal column on (inside a diagonal block the elements below the diagonal make the
  * round trip unchanged).  lsx_posv_*: A is not modified, B is overwritten by X, *info as above (may be NULL); with
@@ -423,6 +429,71 @@ int lsx_posv_f32(lsx_handle_t h, int n, int nrhs, const float *A, int lda, float
  * be NULL); LSX_ERR_ARG for negative sizes, lda < n, ldc < n or a NULL pointer with non-zero sizes. */
 int lsx_syrk_tn_sub_f64_dev(lsx_handle_t h, int n, int k, const double *dA, int lda, double *dC, int ldc);
 int lsx_syrk_tn_sub_f32_dev(lsx_handle_t h, int n, int k, const float *dA, int lda, float *dC, int ldc);
+
+/* ---- Cholesky: condition estimate and error bounds (LAPACK's lansy, pocon, porfs) ---- */
+/* Storage as above: row-major, UPPER, A = U^T U.  The strictly lower triangle of A and of U is never loaded and never
+ * written by any of these, inside a diagonal tile or block included: it may hold NaN.  Nothing here is cooperative: no
+ * kernel waits for another workgroup, there is no time-out outcome and lsx_check_status has nothing to report.
+ * Deterministic: every sum has a fixed order, there are no floating-point atomics, two calls give identical bits; any
+ * alignment and leading dimension (16-byte loads where the operands allow, element-wise loads otherwise, same bits).
+ *
+ * lsx_lansy_*_dev: *d_out (a device double) = the 1-norm, which equals the infinity-norm, of the symmetric n x n matrix
+ * given by its upper triangle.  Contract of lsx_lange_*_dev: sums in fp64 in a fixed order, a NaN in the upper triangle
+ * gives NaN, n == 0 gives 0 (dA may then be NULL).  Asynchronous on the handle's stream.  LSX_ERR_ARG for n < 0,
+ * lda < n, a NULL d_out, or a NULL dA with n > 0.
+ *
+ * lsx_pocon_*: LAPACK's pocon, step for step: *rcond = (1 / est) / anorm, est = lacn2's estimate of the 1-norm of
+ * inv(A) from 4 .. 11 single-right-hand-side solves x <- inv(U) inv(U^T) x (1 for n == 1; the option "pocon_solves"
+ * reads back how many the last call took).  anorm: the 1-norm of the unfactored matrix (lsx_lansy_*_dev).  Outcomes, as
+ * values like lsx_gecon_*: n == 0 gives 1; anorm == 0, an exactly zero or NaN u_ii, or an estimate that is not a finite
+ * number give 0; a NaN or negative anorm is LSX_ERR_ARG.  The host form stages the upper triangle of U; the _dev form
+ * takes a device factor; both synchronise the handle's stream.
+ * lsx_porcond_*: norm, factorisation and estimate of a host matrix in one call; A is not modified.  *info as
+ * lsx_potrf_* (may be NULL); with info > 0 *rcond = 0.
+ *
+ * lsx_porfs_*: LAPACK's porfs, step for step, on the caller's factor: the loop of lsx_gerfs_* (the same code) with the
+ * residual r = b - A x and the bound |b| + |A| |x| formed from the upper triangle of A alone (every stored a_ij, j > i,
+ * loaded once and used for rows i and j; sums in fp64, rounded once) and corrections by single-right-hand-side solves
+ * with U^T and U.  ITMAX = 5, the same stopping rule, safe1 / safe2 guards and per-column lacn2 bound:
+ *   berr[j] = max_i |r_i| / (|b| + |A| |x|)_i of column j of the returned X,
+ *   ferr[j] >= an estimate of max_i |x_i - xtrue_i| / max_i |x_i|.
+ * X holds a solution on entry (lsx_potrs_*) and the refined one on return; A, U and B are not modified.  A column's bits
+ * do not depend on the columns passed with it.  Outcomes as lsx_gerfs_*: n == 0 or nrhs == 0 gives zeros and touches
+ * nothing; an exactly zero or NaN u_ii leaves X untouched with ferr = berr = +inf; a NaN in the upper triangle of A, in
+ * B or in X gives NaN bounds for the columns it reaches and no step for them.  The options "porfs_steps" (most steps
+ * any column took) and "porfs_solves" (estimator solves, 4 .. 11 per column for n > 1) read back the last call.
+ * ferr, berr: host double[nrhs] in all forms.  Synchronises the handle's stream.  LSX_ERR_ARG for negative sizes,
+ * lda < n, ldu < n, ldb < nrhs, ldx < nrhs, or a NULL pointer with non-zero sizes.
+ * lsx_posvr_*: potrf + potrs + porfs for a host system; A and B are kept, X receives the refined solution.  *info as
+ * lsx_potrf_* (may be NULL); with info > 0 X is not written and the bounds are +inf.
+ *
+ * lsx_diag_resid_bound_sym_*_dev (measurement / test hook): dR = dB - A dX and dW = |dB| + |A| |dX| for nrhs <= 8
+ * columns in one pass over the upper triangle of dA, as porfs forms them; ldr: the leading dimension of dR and dW.
+ * nrhs > 8 is LSX_ERR_ARG.  Asynchronous. */
+int lsx_lansy_f64_dev(lsx_handle_t h, int n, const double *dA, int lda, double *d_out);
+int lsx_lansy_f32_dev(lsx_handle_t h, int n, const float *dA, int lda, double *d_out);
+int lsx_pocon_f64(lsx_handle_t h, int n, const double *U, int lda, double anorm, double *rcond);
+int lsx_pocon_f32(lsx_handle_t h, int n, const float *U, int lda, double anorm, double *rcond);
+int lsx_pocon_f64_dev(lsx_handle_t h, int n, const double *dU, int lda, double anorm, double *rcond);
+int lsx_pocon_f32_dev(lsx_handle_t h, int n, const float *dU, int lda, double anorm, double *rcond);
+int lsx_porcond_f64(lsx_handle_t h, int n, const double *A, int lda, double *rcond, int *info);
+int lsx_porcond_f32(lsx_handle_t h, int n, const float *A, int lda, double *rcond, int *info);
+int lsx_porfs_f64(lsx_handle_t h, int n, int nrhs, const double *A, int lda, const double *U, int ldu, const double *B,
+                  int ldb, double *X, int ldx, double *ferr, double *berr);
+int lsx_porfs_f32(lsx_handle_t h, int n, int nrhs, const float *A, int lda, const float *U, int ldu, const float *B,
+                  int ldb, float *X, int ldx, double *ferr, double *berr);
+int lsx_porfs_f64_dev(lsx_handle_t h, int n, int nrhs, const double *dA, int lda, const double *dU, int ldu,
+                      const double *dB, int ldb, double *dX, int ldx, double *ferr, double *berr);
+int lsx_porfs_f32_dev(lsx_handle_t h, int n, int nrhs, const float *dA, int lda, const float *dU, int ldu,
+                      const float *dB, int ldb, float *dX, int ldx, double *ferr, double *berr);
+int lsx_posvr_f64(lsx_handle_t h, int n, int nrhs, const double *A, int lda, const double *B, int ldb, double *X, int ldx,
+                  double *ferr, double *berr, int *info);
+int lsx_posvr_f32(lsx_handle_t h, int n, int nrhs, const float *A, int lda, const float *B, int ldb, float *X, int ldx,
+                  double *ferr, double *berr, int *info);
+int lsx_diag_resid_bound_sym_f64_dev(lsx_handle_t h, int n, int nrhs, const double *dA, int lda, const double *dB, int ldb,
+                                     const double *dX, int ldx, double *dR, double *dW, int ldr);
+int lsx_diag_resid_bound_sym_f32_dev(lsx_handle_t h, int n, int nrhs, const float *dA, int lda, const float *dB, int ldb,
+                                     const float *dX, int ldx, float *dR, float *dW, int ldr);
 
 /* ---- device-pointer entry points (asynchronous on the handle's stream) ---- */
 /* d_info: device int (may be NULL).  d_ipiv: device int32[n].

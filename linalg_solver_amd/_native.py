@@ -122,6 +122,22 @@ _SIGS = {
     "lsx_potrs_f32": [_vp, _i, _i, _fp, _i, _fp, _i],
     "lsx_posv_f64": [_vp, _i, _i, _dp, _i, _dp, _i, C.POINTER(_i)],
     "lsx_posv_f32": [_vp, _i, _i, _fp, _i, _fp, _i, C.POINTER(_i)],
+    "lsx_lansy_f64_dev": [_vp, _i, _vp, _i, _vp],
+    "lsx_lansy_f32_dev": [_vp, _i, _vp, _i, _vp],
+    "lsx_pocon_f64": [_vp, _i, _dp, _i, C.c_double, _dp],
+    "lsx_pocon_f32": [_vp, _i, _fp, _i, C.c_double, _dp],
+    "lsx_pocon_f64_dev": [_vp, _i, _vp, _i, C.c_double, _dp],
+    "lsx_pocon_f32_dev": [_vp, _i, _vp, _i, C.c_double, _dp],
+    "lsx_porcond_f64": [_vp, _i, _dp, _i, _dp, C.POINTER(_i)],
+    "lsx_porcond_f32": [_vp, _i, _fp, _i, _dp, C.POINTER(_i)],
+    "lsx_porfs_f64": [_vp, _i, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _dp],
+    "lsx_porfs_f32": [_vp, _i, _i, _fp, _i, _fp, _i, _fp, _i, _fp, _i, _dp, _dp],
+    "lsx_porfs_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _dp, _dp],
+    "lsx_porfs_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _dp, _dp],
+    "lsx_posvr_f64": [_vp, _i, _i, _dp, _i, _dp, _i, _dp, _i, _dp, _dp, C.POINTER(_i)],
+    "lsx_posvr_f32": [_vp, _i, _i, _fp, _i, _fp, _i, _fp, _i, _dp, _dp, C.POINTER(_i)],
+    "lsx_diag_resid_bound_sym_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_diag_resid_bound_sym_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i],
     "lsx_syrk_tn_sub_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _i],
     "lsx_syrk_tn_sub_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _i],
     "lsx_matmul_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i],

@@ -933,14 +933,48 @@ static int potrf_dev(lsx_handle_t h, int n, T *A, int lda, int *d_info) {
     return LSX_OK;
 }
 
+// Few right-hand sides (kernels_posx.hip): one launch per 128-row block step and direction on a dense n x nr copy of
+// the columns, nothing cooperative.  prepare forms the block inverses once (pocon and porfs solve many times with one
+// factor); nothing else may grow ws2 or ws3 between prepare and the last apply.
+template <typename T>
+struct PotrsFew {
+    const T *inv128 = nullptr;
+    T *W = nullptr;
+};
+template <typename T>
+static int potrs_few_prepare(lsx_handle_t h, int n, const T *U, int lda, PotrsFew<T> *pf) {
+    const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
+    const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
+    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, b64 + b128));
+    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(T) * (size_t)n * 8)));
+    pf->inv128 = (const T *)((char *)h->ws2 + b64);
+    pf->W = (T *)h->ws3;
+    return launch_chol_inv<T>(h, n, U, lda, (T *)h->ws2, (T *)((char *)h->ws2 + b64));
+}
+// B (n x nrhs, 1 <= nrhs <= 8) <- inv(U) inv(U^T) B
+template <typename T>
+static int potrs_few_apply(lsx_handle_t h, int n, int nrhs, const T *U, int lda, const PotrsFew<T> &pf, T *B, int ldb) {
+    const int nr = nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8;
+    LSX_TRY(launch_trsvt_forward_upper<T>(h, n, nr, nrhs, U, lda, pf.inv128, (const T *)B, ldb, 0, pf.W));
+    return launch_posx_backward<T>(h, n, nr, nrhs, U, lda, pf.inv128, pf.W, B, ldb, 0);
+}
+
 // B <- inv(U) inv(U^T) B: the U half of lu_solve_transposed_blocked (U^T Y = B on the TN tile), then sweep_backward
 // (U X = Y).  The block inverses come from the upper triangle alone (launch_chol_inv): what lies below the diagonal of
-// the factor array is never loaded, it may hold anything.  Every nrhs >= 1 takes these sweeps.
+// the factor array is never loaded, it may hold anything.  Every nrhs >= 1 takes these sweeps unless the option
+// potrs_few_max (default 0) sends 1 <= nrhs <= potrs_few_max through the few-column path above.
 template <typename T>
 static int potrs_dev(lsx_handle_t h, int n, int nrhs, const T *U, int lda, T *B, int ldb) {
     LSX_ARG(h && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs);
+    h->potrs_path = 0;
     if (n == 0 || nrhs == 0) return LSX_OK;
     LSX_ARG(U && B);
+    if (nrhs <= h->potrs_few_max) {
+        PotrsFew<T> pf;
+        LSX_TRY(potrs_few_prepare<T>(h, n, U, lda, &pf));
+        h->potrs_path = 1;
+        return potrs_few_apply<T>(h, n, nrhs, U, lda, pf, B, ldb);
+    }
     const int sb = 128, ldw = ld_for(nrhs);
     const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
     const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
@@ -1209,27 +1243,23 @@ template <typename T> struct Lamch;
 template <> struct Lamch<double> { static constexpr double u = 0x1p-53, safmin = 0x1p-1022; };
 template <> struct Lamch<float> { static constexpr double u = 0x1p-24, safmin = 0x1p-126; };
 
-// LAPACK's gerfs (dgerfs.f step for step) on device data: refine X with the caller's factors until the componentwise
-// backward error stops improving, then bound the forward error of every column with lacn2 on inv(op A) diag(W).
-// Residual and bound of up to 8 columns come from one pass over A (kernels_refine.hip); a correction is a single
-// right-hand-side solve of the column that asked for it, so a column gets the same bits whatever rides along.
-// The host reads one record per step.  Synchronises the handle's stream.
-template <typename T>
-static int gerfs_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int lda, const T *LU, int ldlu,
-                     const int32_t *d_ipiv, const T *B, int ldb, T *X, int ldx, double *ferr, double *berr,
-                     bool *singular = nullptr) {
-    LSX_ARG((trans == 0 || trans == 1) && n >= 0 && nrhs >= 0 && lda >= n && ldlu >= n && ldb >= nrhs && ldx >= nrhs);
-    LSX_ARG(nrhs == 0 || (ferr && berr));
-    if (singular) *singular = false;
-    h->gerfs_steps = 0;
-    h->gerfs_solves = 0;
-    for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = 0.0;
-    if (n == 0 || nrhs == 0) return LSX_OK;
-    LSX_ARG(A && LU && d_ipiv && B && X);
+// The refinement loop and forward bound of LAPACK's gerfs / porfs (dgerfs.f, dporfs.f step for step), shared by
+// gerfs_dev and porfs_dev, which differ only in how a residual and a solve are made:
+//   resid(g, B, X, Rg, Wg, ldr, work)  residual and componentwise bound of g <= 8 columns in one pass over the matrix
+//   solve(transposed, v)               v <- inv(op A) v, or inv(op A)^T v, one vector
+// F (ldf) holds the factors: an exactly zero or NaN diagonal entry means there is no solution to refine.  work_bytes:
+// what resid wants behind the loop's own arrays in ws8.  *steps / *solves: the read-back counters of the caller.
+// Refine X until the componentwise backward error stops improving, then bound the forward error of every column with
+// lacn2 on inv(op A) diag(W).  A correction is a single right-hand-side solve of the column that asked for it, so a
+// column gets the same bits whatever rides along.  The host reads one record per step.  Synchronises the stream.
+template <typename T, typename Resid, typename Solve>
+static int refine_loop(lsx_handle_t h, int n, int nrhs, const T *F, int ldf, const T *B, int ldb, T *X, int ldx,
+                       double *ferr, double *berr, bool *singular, size_t work_bytes, int *steps_max, int *solves,
+                       Resid resid, Solve solve) {
     constexpr int G = 8, ITMAX = 5;
     const double u = Lamch<T>::u, safe1 = (n + 1.0) * Lamch<T>::safmin, safe2 = safe1 / u, nu = (n + 1.0) * u;
     const size_t gb = pad256(sizeof(T) * (size_t)n * G), vb = pad256(sizeof(T) * (size_t)n), sb = pad256((size_t)n);
-    LSX_TRY(grow(&h->ws8, &h->ws8_bytes, 2 * gb + 2 * vb + sb + 512 + resid_bound_work_bytes(trans, n)));
+    LSX_TRY(grow(&h->ws8, &h->ws8_bytes, 2 * gb + 2 * vb + sb + 512 + work_bytes));
     char *w8 = (char *)h->ws8;
     T *Rg = (T *)w8;                                    // residuals of the group, n x 8
     T *Wg = (T *)(w8 + gb);                             // bounds of the group
@@ -1238,9 +1268,9 @@ static int gerfs_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int
     signed char *isgn = (signed char *)(w8 + 2 * gb + 2 * vb);
     double *rec = (double *)(w8 + 2 * gb + 2 * vb + sb);   // 16 doubles: berr[8], max|x|[8]
     double *erec = rec + 16;                               // the estimator's record (8 doubles)
-    double *part = rec + 64;                               // partial sums of the transposed residual
+    double *part = rec + 64;                               // the residual pass's partial sums
     double r[16];
-    LSX_TRY(launch_diag_minabs<T>(h, n, LU, ldlu, rec));   // writes its second slot: rec[1]
+    LSX_TRY(launch_diag_minabs<T>(h, n, F, ldf, rec));     // writes its second slot: rec[1]
     LSX_HIP(hipMemcpyAsync(r, rec, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     LSX_HIP(hipStreamSynchronize(h->stream));
     if (!(r[1] > 0)) {                                      // an exactly zero (or NaN) pivot: no solution to refine
@@ -1248,11 +1278,6 @@ static int gerfs_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int
         if (singular) *singular = true;
         return LSX_OK;
     }
-    // x <- inv(op A) x (transposed: inv(op A)^T x) for one vector, with the caller's interchanges
-    auto solve = [&](const bool transposed) -> int {
-        return (trans != 0) != transposed ? getrs_t_dev<T>(h, n, 1, LU, ldlu, d_ipiv, v, 1)
-                                          : getrs_dev<T>(h, n, 1, LU, ldlu, d_ipiv, v, 1);
-    };
     for (int c0 = 0; c0 < nrhs; c0 += G) {
         const int g = std::min(G, nrhs - c0);
         int steps[G] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1260,7 +1285,7 @@ static int gerfs_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int
         bool active[G];
         for (int j = 0; j < G; ++j) { lstres[j] = 3.0; active[j] = j < g; }
         for (;;) {
-            LSX_TRY(launch_resid_bound<T>(h, trans, n, g, A, lda, B + c0, ldb, X + c0, ldx, Rg, Wg, G, part));
+            LSX_TRY(resid(g, B + c0, X + c0, Rg, Wg, G, part));
             LSX_TRY(launch_berr<T>(h, n, g, Rg, Wg, G, X + c0, ldx, safe1, safe2, rec));
             LSX_HIP(hipMemcpyAsync(r, rec, sizeof(r), hipMemcpyDeviceToHost, h->stream));
             LSX_HIP(hipStreamSynchronize(h->stream));
@@ -1271,11 +1296,11 @@ static int gerfs_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int
                 berr[c0 + j] = be;
                 if (be > u && 2.0 * be <= lstres[j] && steps[j] < ITMAX) {
                     LSX_TRY(launch_refine_take<T>(h, n, Rg + j, G, v));
-                    LSX_TRY(solve(false));
+                    LSX_TRY(solve(false, v));
                     LSX_TRY(launch_refine_add<T>(h, n, v, X + c0 + j, ldx));
                     lstres[j] = be;
                     steps[j] += 1;
-                    h->gerfs_steps = std::max(h->gerfs_steps, steps[j]);
+                    *steps_max = std::max(*steps_max, steps[j]);
                     any = true;
                 } else {
                     active[j] = false;                      // a NaN compares false: no step
@@ -1291,19 +1316,49 @@ static int gerfs_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int
             LSX_TRY(launch_est_fill<T>(h, n, 0, v, (int32_t *)nullptr));
             // lacn2 on M = diag(W) inv(op A)^T: its 1-norm is the infinity-norm of inv(op A) diag(W)
             auto apply = [&](const int kase) -> int {
-                h->gerfs_solves += 1;
+                *solves += 1;
                 if (kase == 1) {
-                    LSX_TRY(solve(true));
+                    LSX_TRY(solve(true, v));
                     return launch_vec_mul<T>(h, n, wt, v);
                 }
                 LSX_TRY(launch_vec_mul<T>(h, n, wt, v));
-                return solve(false);
+                return solve(false, v);
             };
             double est = 0;
             LSX_TRY((lacn2_dev<T>(h, n, v, isgn, erec, apply, &est)));
             ferr[c0 + j] = xmax != 0 ? est / xmax : est;
         }
     }
+    return LSX_OK;
+}
+
+// LAPACK's gerfs on device data with the caller's factors: refine_loop around the general residual pass
+// (kernels_refine.hip) and single right-hand-side solves with L U and its transpose.
+template <typename T>
+static int gerfs_dev(lsx_handle_t h, int trans, int n, int nrhs, const T *A, int lda, const T *LU, int ldlu,
+                     const int32_t *d_ipiv, const T *B, int ldb, T *X, int ldx, double *ferr, double *berr,
+                     bool *singular = nullptr) {
+    LSX_ARG((trans == 0 || trans == 1) && n >= 0 && nrhs >= 0 && lda >= n && ldlu >= n && ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(nrhs == 0 || (ferr && berr));
+    if (singular) *singular = false;
+    h->gerfs_steps = 0;
+    h->gerfs_solves = 0;
+    for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = 0.0;
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(A && LU && d_ipiv && B && X);
+    auto resid = [&](int g, const T *Bc, const T *Xc, T *Rg, T *Wg, int ldr, double *part) -> int {
+        return launch_resid_bound<T>(h, trans, n, g, A, lda, Bc, ldb, Xc, ldx, Rg, Wg, ldr, part);
+    };
+    // x <- inv(op A) x (transposed: inv(op A)^T x) for one vector, with the caller's interchanges
+    auto solve = [&](const bool transposed, T *v) -> int {
+        return (trans != 0) != transposed ? getrs_t_dev<T>(h, n, 1, LU, ldlu, d_ipiv, v, 1)
+                                          : getrs_dev<T>(h, n, 1, LU, ldlu, d_ipiv, v, 1);
+    };
+    bool sing = false;
+    LSX_TRY((refine_loop<T>(h, n, nrhs, LU, ldlu, B, ldb, X, ldx, ferr, berr, &sing, resid_bound_work_bytes(trans, n),
+                            &h->gerfs_steps, &h->gerfs_solves, resid, solve)));
+    if (singular) *singular = sing;
+    if (sing) return LSX_OK;
     return check_dev_status(h);                             // a timed-out solve is a failure, not a bound
 }
 
@@ -1420,6 +1475,187 @@ static int rcond_host(lsx_handle_t h, int norm, int n, const T *A, int lda, doub
 }
 
 // ---------------------------------------------------------------- equilibration and the expert driver (gesvx)
+// ---------------------------------------------------------------- Cholesky: condition estimate and error bounds
+// The 1-norm (= infinity-norm) of a symmetric matrix from its upper triangle, lsx_lange_*_dev's contract otherwise.
+template <typename T>
+static int lansy_dev(lsx_handle_t h, int n, const T *dA, int lda, double *d_out) {
+    LSX_ARG(n >= 0 && lda >= n && d_out);
+    LSX_ARG(n == 0 || dA);
+    LSX_TRY(ensure_scratch(h, resid_bound_sym_work_bytes(n, 1) + 256));
+    return launch_lansy<T>(h, n, dA, lda, (double *)h->scratch, d_out);
+}
+
+// LAPACK's pocon: lacn2's iteration around x <- inv(U) inv(U^T) x.  The operator is symmetric, so both kase values
+// apply the same solve.  Synchronises the handle's stream.
+template <typename T>
+static int pocon_dev(lsx_handle_t h, int n, const T *U, int lda, double anorm, double *rcond) {
+    LSX_ARG(n >= 0 && lda >= n && rcond);
+    *rcond = 1.0;
+    h->pocon_solves = 0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(U);
+    if (anorm != anorm || anorm < 0) {
+        set_error("bad argument: anorm must be a norm of the unfactored matrix, not NaN or negative");
+        return LSX_ERR_ARG;
+    }
+    *rcond = 0.0;
+    if (anorm == 0) return LSX_OK;
+    const size_t xb = pad256(sizeof(T) * (size_t)n), sb = pad256((size_t)n);
+    LSX_TRY(grow(&h->ws7, &h->ws7_bytes, xb + sb + 256));
+    T *x = (T *)h->ws7;
+    signed char *isgn = (signed char *)((char *)h->ws7 + xb);
+    double *rec = (double *)((char *)h->ws7 + xb + sb);          // 8 doubles; rec[5] = min |u_ii|
+    double r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    LSX_HIP(hipMemsetAsync(isgn, 0, (size_t)n, h->stream));
+    LSX_TRY(launch_diag_minabs<T>(h, n, U, lda, rec + 4));       // writes its second slot: rec[5]
+    LSX_TRY(launch_est_fill<T>(h, n, 0, x, (int32_t *)nullptr));
+    LSX_HIP(hipMemcpyAsync(r, rec, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (!(r[5] > 0)) return LSX_OK;                               // an exactly zero (or NaN) u_ii: rcond = 0
+    PotrsFew<T> pf;
+    LSX_TRY(potrs_few_prepare<T>(h, n, U, lda, &pf));
+    auto solve = [&](const int) -> int {
+        h->pocon_solves += 1;
+        return potrs_few_apply<T>(h, n, 1, U, lda, pf, x, 1);
+    };
+    double est = 0;
+    LSX_TRY((lacn2_dev<T>(h, n, x, isgn, rec, solve, &est)));
+    if (est > 0 && est - est == 0) *rcond = (1.0 / est) / anorm;  // non-finite estimate: 0
+    return LSX_OK;
+}
+
+// LAPACK's porfs on device data: refine_loop around the symmetric residual pass and the few-column Cholesky solve.
+// A and U are read from their upper triangles alone.
+template <typename T>
+static int porfs_dev(lsx_handle_t h, int n, int nrhs, const T *A, int lda, const T *U, int ldu, const T *B, int ldb, T *X,
+                     int ldx, double *ferr, double *berr, bool *singular = nullptr) {
+    LSX_ARG(n >= 0 && nrhs >= 0 && lda >= n && ldu >= n && ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(nrhs == 0 || (ferr && berr));
+    if (singular) *singular = false;
+    h->porfs_steps = 0;
+    h->porfs_solves = 0;
+    for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = 0.0;
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(A && U && B && X);
+    PotrsFew<T> pf;
+    LSX_TRY(potrs_few_prepare<T>(h, n, U, ldu, &pf));          // harmless on a factor with a zero u_ii: not used then
+    auto resid = [&](int g, const T *Bc, const T *Xc, T *Rg, T *Wg, int ldr, double *part) -> int {
+        return launch_resid_bound_sym<T>(h, n, g, A, lda, Bc, ldb, Xc, ldx, Rg, Wg, ldr, part);
+    };
+    auto solve = [&](const bool, T *v) -> int { return potrs_few_apply<T>(h, n, 1, U, ldu, pf, v, 1); };
+    return refine_loop<T>(h, n, nrhs, U, ldu, B, ldb, X, ldx, ferr, berr, singular,
+                          resid_bound_sym_work_bytes(n, std::min(nrhs, 8)), &h->porfs_steps, &h->porfs_solves, resid, solve);
+}
+
+template <typename T>
+static int pocon_host(lsx_handle_t h, int n, const T *U, int lda, double anorm, double *rcond) {
+    LSX_ARG(h && n >= 0 && lda >= n && rcond);
+    if (n == 0) { *rcond = 1.0; h->pocon_solves = 0; return LSX_OK; }
+    LSX_ARG(U);
+    const int ld = ld_for(n);
+    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + 512));
+    Carver c(h->ws);
+    T *dU = c.take<T>((size_t)n * ld);
+    LSX_TRY(upper_h2d<T>(h, n, U, lda, dU, ld));
+    return pocon_dev<T>(h, n, dU, ld, anorm, rcond);
+}
+
+// norm, factorisation and estimate of a host matrix, which is not modified; info as lsx_potrf_* (rcond = 0 then)
+template <typename T>
+static int porcond_host(lsx_handle_t h, int n, const T *A, int lda, double *rcond, int *info) {
+    LSX_ARG(h && n >= 0 && lda >= n && rcond);
+    if (info) *info = 0;
+    *rcond = 1.0;
+    h->pocon_solves = 0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A);
+    const int ld = ld_for(n);
+    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + 1024));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    int *dinfo = c.take<int>(1);
+    double *dnorm = c.take<double>(1);
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
+    LSX_TRY(lansy_dev<T>(h, n, dA, ld, dnorm));
+    double anorm = 0;
+    int hinfo = 0;
+    LSX_HIP(hipMemcpyAsync(&anorm, dnorm, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    LSX_TRY(potrf_dev<T>(h, n, dA, ld, dinfo));
+    LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (info) *info = hinfo;
+    if (hinfo != 0) { *rcond = 0.0; return LSX_OK; }
+    return pocon_dev<T>(h, n, dA, ld, anorm, rcond);
+}
+
+// host buffers: stage the upper triangles of A and U, B and X, refine on the device, bring X back
+template <typename T>
+static int porfs_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, const T *U, int ldu, const T *B, int ldb, T *X,
+                      int ldx, double *ferr, double *berr) {
+    LSX_ARG(h && n >= 0 && nrhs >= 0 && lda >= n && ldu >= n && ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(nrhs == 0 || (ferr && berr));
+    if (n == 0 || nrhs == 0) return porfs_dev<T>(h, n, nrhs, A, lda, U, ldu, B, ldb, X, ldx, ferr, berr);
+    LSX_ARG(A && U && B && X);
+    const int ld = ld_for(n), ldr = ld_for(nrhs);
+    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) + 512));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    T *dU = c.take<T>((size_t)n * ld);
+    T *dB = c.take<T>((size_t)n * ldr);
+    T *dX = c.take<T>((size_t)n * ldr);
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
+    LSX_TRY(upper_h2d<T>(h, n, U, ldu, dU, ld));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
+    LSX_TRY(h2d<T>(h, n, nrhs, X, ldx, dX, ldr));
+    bool singular = false;
+    LSX_TRY(porfs_dev<T>(h, n, nrhs, dA, ld, dU, ld, dB, ldr, dX, ldr, ferr, berr, &singular));
+    if (singular) return LSX_OK;                                    // X is left untouched
+    LSX_TRY(d2h<T>(h, n, nrhs, dX, ldr, X, ldx));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+// factor, solve, refine, bound for a host system; A and B are kept
+template <typename T>
+static int posvr_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, const T *B, int ldb, T *X, int ldx,
+                      double *ferr, double *berr, int *info) {
+    LSX_ARG(h && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs && ldx >= nrhs);
+    LSX_ARG(nrhs == 0 || (ferr && berr));
+    if (info) *info = 0;
+    h->porfs_steps = 0;
+    h->porfs_solves = 0;
+    for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = 0.0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A && (nrhs == 0 || (B && X)));
+    const int ld = ld_for(n), ldr = ld_for(nrhs > 0 ? nrhs : 1);
+    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) + 1024));
+    Carver c(h->ws);
+    T *dA = c.take<T>((size_t)n * ld);
+    T *dU = c.take<T>((size_t)n * ld);
+    T *dB = c.take<T>((size_t)n * ldr);
+    T *dX = c.take<T>((size_t)n * ldr);
+    int *dinfo = c.take<int>(1);
+    int hinfo = 0;
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dU, ld));
+    LSX_TRY(potrf_dev<T>(h, n, dU, ld, dinfo));
+    LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (info) *info = hinfo;
+    if (hinfo != 0) {                                               // not positive definite: X is not written
+        for (int j = 0; j < nrhs; ++j) ferr[j] = berr[j] = INFINITY;
+        return LSX_OK;
+    }
+    if (nrhs == 0) return LSX_OK;
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
+    LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dX, ldr));
+    LSX_TRY(potrs_dev<T>(h, n, nrhs, dU, ld, dX, ldr));
+    LSX_TRY(porfs_dev<T>(h, n, nrhs, dA, ld, dU, ld, dB, ldr, dX, ldr, ferr, berr));
+    LSX_TRY(d2h<T>(h, n, nrhs, dX, ldr, X, ldx));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
 template <typename T> struct LaqgeLim;   // dlaqge's small = safmin / prec with prec = eps * base; large = 1 / small
 template <> struct LaqgeLim<double> { static constexpr double small_ = 0x1p-970, large_ = 0x1p+970; };
 template <> struct LaqgeLim<float> { static constexpr double small_ = 0x1p-103, large_ = 0x1p+103; };
@@ -1853,6 +2089,9 @@ int lsx_set_option(lsx_handle_t h, const char *key, int value) {
     } else if (!strcmp(key, "getrs_t_blocked_min")) {   // transposed solve: smallest nrhs on the blocked sweeps (n > 128); 0 = never
         LSX_ARG(value >= 0);
         h->getrs_t_blocked_min = value;
+    } else if (!strcmp(key, "potrs_few_max")) {   // Cholesky solve: largest nrhs on the few-column step kernels; 0 = never
+        LSX_ARG(value >= 0 && value <= 8);
+        h->potrs_few_max = value;
     } else {
         set_error("unknown option '%s'", key);
         return LSX_ERR_ARG;
@@ -1886,6 +2125,11 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value) {
     else if (!strcmp(key, "gerfs_solves")) *value = h->gerfs_solves;
     else if (!strcmp(key, "getrs_t_blocked_min")) *value = h->getrs_t_blocked_min;
     else if (!strcmp(key, "getrs_t_path")) *value = h->getrs_t_path;
+    else if (!strcmp(key, "potrs_few_max")) *value = h->potrs_few_max;
+    else if (!strcmp(key, "potrs_path")) *value = h->potrs_path;
+    else if (!strcmp(key, "pocon_solves")) *value = h->pocon_solves;
+    else if (!strcmp(key, "porfs_steps")) *value = h->porfs_steps;
+    else if (!strcmp(key, "porfs_solves")) *value = h->porfs_solves;
     else { set_error("unknown option '%s'", key); return LSX_ERR_ARG; }
     return LSX_OK;
 }
@@ -2610,6 +2854,53 @@ int lsx_gemm_tn_sub_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dA
         LSX_DEVICE_GUARD(h);                                                                                              \
         return posv_host<T>(h, n, nrhs, A, lda, B, ldb, info);                                                            \
     }
+#define LSX_POSX_ENTRIES(SFX, T)                                                                                          \
+    int lsx_lansy_##SFX##_dev(lsx_handle_t h, int n, const T *dA, int lda, double *d_out) {                               \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        LSX_ARG(h);                                                                                                       \
+        return lansy_dev<T>(h, n, dA, lda, d_out);                                                                        \
+    }                                                                                                                     \
+    int lsx_pocon_##SFX(lsx_handle_t h, int n, const T *U, int lda, double anorm, double *rcond) {                        \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return pocon_host<T>(h, n, U, lda, anorm, rcond);                                                                 \
+    }                                                                                                                     \
+    int lsx_pocon_##SFX##_dev(lsx_handle_t h, int n, const T *dU, int lda, double anorm, double *rcond) {                 \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        LSX_ARG(h);                                                                                                       \
+        return pocon_dev<T>(h, n, dU, lda, anorm, rcond);                                                                 \
+    }                                                                                                                     \
+    int lsx_porcond_##SFX(lsx_handle_t h, int n, const T *A, int lda, double *rcond, int *info) {                         \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return porcond_host<T>(h, n, A, lda, rcond, info);                                                                \
+    }                                                                                                                     \
+    int lsx_porfs_##SFX(lsx_handle_t h, int n, int nrhs, const T *A, int lda, const T *U, int ldu, const T *B, int ldb,   \
+                        T *X, int ldx, double *ferr, double *berr) {                                                      \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return porfs_host<T>(h, n, nrhs, A, lda, U, ldu, B, ldb, X, ldx, ferr, berr);                                     \
+    }                                                                                                                     \
+    int lsx_porfs_##SFX##_dev(lsx_handle_t h, int n, int nrhs, const T *dA, int lda, const T *dU, int ldu, const T *dB,   \
+                              int ldb, T *dX, int ldx, double *ferr, double *berr) {                                      \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        LSX_ARG(h);                                                                                                       \
+        return porfs_dev<T>(h, n, nrhs, dA, lda, dU, ldu, dB, ldb, dX, ldx, ferr, berr);                                  \
+    }                                                                                                                     \
+    int lsx_posvr_##SFX(lsx_handle_t h, int n, int nrhs, const T *A, int lda, const T *B, int ldb, T *X, int ldx,         \
+                        double *ferr, double *berr, int *info) {                                                          \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return posvr_host<T>(h, n, nrhs, A, lda, B, ldb, X, ldx, ferr, berr, info);                                       \
+    }                                                                                                                     \
+    int lsx_diag_resid_bound_sym_##SFX##_dev(lsx_handle_t h, int n, int nrhs, const T *dA, int lda, const T *dB, int ldb, \
+                                             const T *dX, int ldx, T *dR, T *dW, int ldr) {                               \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        LSX_ARG(h && n >= 0 && nrhs >= 0 && nrhs <= 8 && lda >= n && ldb >= nrhs && ldx >= nrhs && ldr >= nrhs);          \
+        if (n == 0 || nrhs == 0) return LSX_OK;                                                                           \
+        LSX_ARG(dA && dB && dX && dR && dW);                                                                              \
+        LSX_TRY(ensure_scratch(h, resid_bound_sym_work_bytes(n, nrhs) + 256));                                            \
+        return launch_resid_bound_sym<T>(h, n, nrhs, dA, lda, dB, ldb, dX, ldx, dR, dW, ldr, (double *)h->scratch);       \
+    }
+LSX_POSX_ENTRIES(f64, double)
+LSX_POSX_ENTRIES(f32, float)
+#undef LSX_POSX_ENTRIES
 LSX_CHOL_ENTRIES(f64, double)
 LSX_CHOL_ENTRIES(f32, float)
 #undef LSX_CHOL_ENTRIES

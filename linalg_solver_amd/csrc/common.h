@@ -132,6 +132,11 @@ struct lsx_handle_s {
     size_t ws9_bytes = 0;
     int getrs_t_blocked_min = 64;   // transposed solve: smallest nrhs that takes the blocked (MFMA) sweeps when n > 128; 0 = never
     int getrs_t_path = 0;    // read-only option: 1 if the last lsx_getrs_t_* call took the blocked sweeps
+    int potrs_few_max = 0;   // Cholesky solve: largest nrhs (<= 8) that takes the few-column step kernels; 0 = never
+    int potrs_path = 0;      // read-only option: 1 if the last lsx_potrs_* call took the few-column step kernels
+    int pocon_solves = 0;    // read-only option: single-right-hand-side solves of the last lsx_pocon_* / lsx_porcond_*
+    int porfs_steps = 0;     // read-only option: most refinement steps any column of the last porfs took
+    int porfs_solves = 0;    // read-only option: single-right-hand-side estimator solves of the last porfs
     // gather lists (int2[256] each) emitted by the cooperative panel kernels: storage only, a launch is told which one
     void *moves_buf[2] = {nullptr, nullptr};  // the drivers' lists (the shared-CU look-ahead driver alternates)
     void *moves_api = nullptr;       // list of the last lsx_panel_f64_dev call, handed out by lsx_panel_moves_dev
@@ -421,5 +426,23 @@ template <typename T>
 int launch_chol_diag(lsx_handle_t h, int jb, T *A, int lda, int col0, T *Vinv, int *info);
 template <typename T>
 int launch_chol_inv(lsx_handle_t h, int n, const T *U, int lda, T *inv64, T *inv128);
+// Condition estimate and error bounds of the Cholesky family (kernels_posx.hip); nothing below a diagonal is loaded.
+// launch_resid_bound_sym: launch_resid_bound for a symmetric A given by its upper triangle; launch_lansy: its 1-norm
+// (launch_lange's contract); d_work: resid_bound_sym_work_bytes(n, ncols) bytes, ncols = 1 for the norm.
+// Few right-hand sides, X <- inv(U) inv(U^T) B through W (n x nr, dense, nr in {1, 2, 4, 8} >= w): the forward half
+// packs columns [c0, c0 + w) of B and solves with U^T (kernels_trsvt.hip), the backward half solves with U and
+// unpacks; inv128: launch_chol_inv's.
+size_t resid_bound_sym_work_bytes(int n, int ncols);
+template <typename T>
+int launch_resid_bound_sym(lsx_handle_t h, int n, int ncols, const T *A, int lda, const T *B, int ldb, const T *X, int ldx,
+                           T *R, T *W, int ldr, double *d_work);
+template <typename T>
+int launch_lansy(lsx_handle_t h, int n, const T *A, int lda, double *d_work, double *d_out);
+template <typename T>
+int launch_trsvt_forward_upper(lsx_handle_t h, int n, int nr, int w, const T *U, int lda, const T *inv128U, const T *B,
+                               int ldb, int c0, T *W);
+template <typename T>
+int launch_posx_backward(lsx_handle_t h, int n, int nr, int w, const T *U, int lda, const T *inv128, T *W, T *B, int ldb,
+                         int c0);
 
 }  // namespace lsx

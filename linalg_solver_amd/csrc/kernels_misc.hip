@@ -1135,14 +1135,14 @@ __global__ __launch_bounds__(256) void diag_minabs_kernel(int n, const T *__rest
     double v = INFINITY;
     for (int k = threadIdx.x; k < n; k += 256) {
         const double a = fabs((double)LU[(size_t)k * lda + k]);
-        if (!(a >= v)) v = a;  // NaN propagates as "smallest"
+        if (a != a || (v == v && a < v)) v = a;  // a NaN is the "smallest", and stays: nothing replaces it
     }
     s[threadIdx.x] = v;
     __syncthreads();
     for (int k = 128; k > 0; k >>= 1) {
         if (threadIdx.x < k) {
-            const double o = s[threadIdx.x + k];
-            if (!(o >= s[threadIdx.x])) s[threadIdx.x] = o;
+            const double o = s[threadIdx.x + k], m = s[threadIdx.x];
+            if (o != o || (m == m && o < m)) s[threadIdx.x] = o;
         }
         __syncthreads();
     }

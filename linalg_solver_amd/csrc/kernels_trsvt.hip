@@ -265,6 +265,37 @@ static int trsvt_sweeps(lsx_handle_t h, int n, const T *LU, int lda, const T *in
     return LSX_OK;
 }
 
+// The U half alone, for the few-column Cholesky solve (kernels_posx.hip): W (n x nr, dense, nr in {1, 2, 4, 8}) <-
+// columns [c0, c0 + w) of B, then U^T Y = W in place with the same launches as the forward half of trsvt_sweeps.
+// Only tiles strictly above the diagonal blocks of U are read; inv128U is launch_chol_inv's natural-orientation inverse.
+template <typename T>
+int launch_trsvt_forward_upper(lsx_handle_t h, int n, int nr, int w, const T *U, int lda, const T *inv128U, const T *B,
+                               int ldb, int c0, T *W) {
+    if (n <= 0 || w <= 0) return LSX_OK;
+    const int nblk = (n + WB - 1) / WB;
+    ProfScope ps(h, LSX_PROF_TRSM, (double)n * n * w, sizeof(T) * (double)n * n / 2);
+    hipLaunchKernelGGL(trsvt_pack_kernel<T>, dim3((n * nr + 255) / 256), dim3(256), 0, h->stream, n, nr, w, B, ldb, c0, W);
+#define TF_LAUNCH(NRV)                                                                                                      \
+    hipLaunchKernelGGL((trsvt_step_kernel<T, NRV>), dim3(1), dim3(256), 0, h->stream, n, U, lda, inv128U, -1, 0, 0, W);      \
+    for (int k = 0; k + 1 < nblk; ++k)                                                                                      \
+        hipLaunchKernelGGL((trsvt_step_kernel<T, NRV>), dim3(nblk - 1 - k), dim3(256), 0, h->stream, n, U, lda, inv128U, k, \
+                           k + 1, k + 1, W)
+    switch (nr) {
+        case 1: TF_LAUNCH(1); break;
+        case 2: TF_LAUNCH(2); break;
+        case 4: TF_LAUNCH(4); break;
+        case 8: TF_LAUNCH(8); break;
+        default: set_error("launch_trsvt_forward_upper: nr must be 1, 2, 4 or 8"); return LSX_ERR_INTERNAL;
+    }
+#undef TF_LAUNCH
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
+}
+template int launch_trsvt_forward_upper<double>(lsx_handle_t, int, int, int, const double *, int, const double *,
+                                                const double *, int, int, double *);
+template int launch_trsvt_forward_upper<float>(lsx_handle_t, int, int, int, const float *, int, const float *, const float *,
+                                               int, int, float *);
+
 // B (n x nrhs) <- the solution of A^T X = B, any nrhs, in groups of up to 8 columns.  n > 128: inv64* / inv128* are
 // work space for the block inverses (as in the plain solve), perm the gather list, W an n x 8 work vector.
 template <typename T>

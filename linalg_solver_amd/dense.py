@@ -324,6 +324,108 @@ def solve_bounded(a, b, trans: bool = False, dtype=np.float64, handle: Optional[
     return (None if info.value else X), ferr, berr, info.value
 
 
+def cho_rcond(U: np.ndarray, anorm: float, handle: Optional[N.Handle] = None) -> float:
+    """pocon from an existing Cholesky factor (cho_factor): anorm is the 1-norm of the UNFACTORED symmetric matrix
+    (lsx_pocon_*).  Only the upper triangle of U is used."""
+    U = np.asarray(U)
+    if U.ndim != 2 or U.shape[0] != U.shape[1]:
+        raise ValueError("cho_rcond needs the square factor matrix")
+    ct, sfx = _ct(U.dtype)
+    n = U.shape[0]
+    anorm = float(anorm)
+    if math.isnan(anorm) or anorm < 0:
+        raise ValueError("anorm must be a norm of the unfactored matrix (not NaN, not negative)")
+    h = _h(handle)
+    U = np.ascontiguousarray(U)
+    rc = C.c_double(0.0)
+    N.check(getattr(h.lib, f"lsx_pocon_{sfx}")(h.ptr, n, _ptr(U, ct) if n else None, max(n, 1), anorm, C.byref(rc)),
+            f"lsx_pocon_{sfx}")
+    return rc.value
+
+
+def rcond_pos(a, dtype=np.float64, handle: Optional[N.Handle] = None) -> Tuple[float, int]:
+    """Reciprocal condition number (1-norm = infinity-norm) of a symmetric positive definite matrix: norm, Cholesky
+    factorisation and LAPACK's pocon estimate in one call (lsx_porcond_*).  Only the upper triangle of a is used.
+    Returns (rcond, info); info = j + 1 says the leading minor of order j + 1 is not positive definite (rcond 0)."""
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("rcond_pos needs a square matrix")
+    h = _h(handle)
+    n = A.shape[0]
+    rc, info = C.c_double(0.0), C.c_int(0)
+    N.check(getattr(h.lib, f"lsx_porcond_{sfx}")(h.ptr, n, _ptr(A, ct) if n else None, max(n, 1), C.byref(rc),
+                                                  C.byref(info)), f"lsx_porcond_{sfx}")
+    return rc.value, info.value
+
+
+def cho_refine(a, U, b, x, handle: Optional[N.Handle] = None):
+    """LAPACK's porfs from an existing Cholesky factor (lsx_porfs_*): refine the solution x of A X = B until its
+    componentwise backward error stops improving, and bound its error.  a is the UNFACTORED symmetric matrix, U its
+    factor (cho_factor), x a solution (cho_solve); only the upper triangles of a and U are used.  Returns
+    (x, ferr, berr) as lu_refine does: +inf bounds when a u_ii is exactly zero (x is returned as given), NaN for a
+    column with a NaN in its data."""
+    U = np.asarray(U)
+    if U.ndim != 2 or U.shape[0] != U.shape[1]:
+        raise ValueError("cho_refine needs the square factor matrix")
+    ct, sfx = _ct(U.dtype)
+    dt = U.dtype
+    n = U.shape[0]
+    A = np.ascontiguousarray(a, dtype=dt)
+    if A.shape != (n, n):
+        raise ValueError("cho_refine needs the unfactored matrix and its factor: same shape")
+    if np.shape(b)[:1] != (n,) or np.shape(x) != np.shape(b):
+        raise ValueError("right-hand side and solution need as many rows as the matrix, and the same shape")
+    h = _h(handle)
+    U = np.ascontiguousarray(U)
+    B = np.ascontiguousarray(b, dtype=dt)
+    X = np.array(x, dtype=dt, order="C", copy=True)
+    vec = X.ndim == 1
+    if vec:
+        B, X = B.reshape(n, 1), X.reshape(n, 1)
+    nrhs = X.shape[1]
+    ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+    ld, ldr = max(n, 1), max(nrhs, 1)
+    name = f"lsx_porfs_{sfx}"
+    N.check(getattr(h.lib, name)(h.ptr, n, nrhs, _ptr(A, ct), ld, _ptr(U, ct), ld, _ptr(B, ct), ldr, _ptr(X, ct), ldr,
+                                 _ptr(ferr, C.c_double), _ptr(berr, C.c_double)), name)
+    ferr, berr = ferr[:nrhs], berr[:nrhs]
+    if vec:
+        return X[:, 0].copy(), float(ferr[0]), float(berr[0])
+    return X, ferr, berr
+
+
+def solve_pos_bounded(a, b, dtype=np.float64, handle: Optional[N.Handle] = None):
+    """Cholesky-factor, solve, refine and bound in one call (lsx_posvr_*) for a symmetric positive definite matrix:
+    returns (x, ferr, berr, info) with ferr / berr as in cho_refine (floats for a vector b, arrays for a matrix).
+    Only the upper triangle of a is used.  info = j + 1 says the leading minor of order j + 1 is not positive
+    definite: x is None and the bounds are +inf."""
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    n = A.shape[0]
+    if A.ndim != 2 or A.shape[1] != n:
+        raise ValueError("solve_pos_bounded needs a square matrix")
+    if np.shape(b)[:1] != (n,):
+        raise ValueError("right-hand side has the wrong number of rows")
+    h = _h(handle)
+    B = np.ascontiguousarray(b, dtype=dtype)
+    vec = B.ndim == 1
+    if vec:
+        B = B.reshape(n, 1)
+    nrhs = B.shape[1]
+    X = np.zeros((n, nrhs), dtype=dtype)
+    ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+    info = C.c_int(0)
+    ld, ldr = max(n, 1), max(nrhs, 1)
+    name = f"lsx_posvr_{sfx}"
+    N.check(getattr(h.lib, name)(h.ptr, n, nrhs, _ptr(A, ct), ld, _ptr(B, ct), ldr, _ptr(X, ct), ldr,
+                                 _ptr(ferr, C.c_double), _ptr(berr, C.c_double), C.byref(info)), name)
+    ferr, berr = ferr[:nrhs], berr[:nrhs]
+    if vec:
+        return (None if info.value else X[:, 0].copy()), float(ferr[0]), float(berr[0]), info.value
+    return (None if info.value else X), ferr, berr, info.value
+
+
 def solve_expert(a, b, trans: bool = False, equilibrate: bool = True, dtype=np.float64,
                  handle: Optional[N.Handle] = None):
     """LAPACK's expert driver gesvx in one call (lsx_gesvx_*): equilibrate the matrix if its rows or columns are badly

@@ -185,6 +185,61 @@ class DeviceSolver:
                                         X.stride(0), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp)), name)
         return ferr[:nrhs], berr[:nrhs]
 
+    def norm_sym(self, A: torch.Tensor) -> torch.Tensor:
+        """1-norm (= infinity-norm) of a symmetric matrix in HBM given by its upper triangle: a device double[1], no
+        host sync (lsx_lansy_*_dev).  The strictly lower triangle is not read."""
+        _rowmajor(A, "norm_sym")
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("norm_sym needs a square matrix")
+        out = torch.zeros(1, dtype=torch.float64, device=A.device)
+        name = f"lsx_lansy_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, A.shape[0], A.data_ptr(), max(A.stride(0), 1), out.data_ptr()), name)
+        return out
+
+    def pocon(self, U: torch.Tensor, anorm) -> float:
+        """Reciprocal condition number from a Cholesky factor in HBM (lsx_pocon_*_dev); anorm: the 1-norm of the
+        UNFACTORED matrix, a float or the tensor `norm_sym` returned.  Only the upper triangle of U is read.
+        Synchronises the stream: the result is a host float."""
+        import ctypes as C
+        import math
+
+        _rowmajor(U, "pocon")
+        if U.shape[0] != U.shape[1]:
+            raise ValueError("pocon needs the square factor")
+        anorm = float(anorm.item()) if hasattr(anorm, "item") else float(anorm)
+        if math.isnan(anorm) or anorm < 0:
+            raise ValueError("anorm must be a norm of the unfactored matrix (not NaN, not negative)")
+        rc = C.c_double(0.0)
+        name = f"lsx_pocon_{self._suffix(U)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, U.shape[0], U.data_ptr(), max(U.stride(0), 1), anorm, C.byref(rc)),
+                name)
+        return rc.value
+
+    def porfs_(self, A: torch.Tensor, U: torch.Tensor, B: torch.Tensor, X: torch.Tensor):
+        """Refine X (a solution of A X = B) in place from the Cholesky factor U of the symmetric positive definite A
+        and bound its error: LAPACK's porfs on tensors in HBM (lsx_porfs_*_dev).  Only the upper triangles of A and U
+        are read.  Returns (ferr, berr) as numpy arrays, one entry per right-hand side.  Synchronises the stream: the
+        host drives the iteration."""
+        import ctypes as C
+
+        import numpy as np
+
+        for t, w in ((A, "A"), (U, "U"), (B, "B"), (X, "X")):
+            _rowmajor(t, "porfs_ " + w)
+        n = A.shape[0]
+        if A.shape[1] != n or U.shape != A.shape or B.shape[0] != n or X.shape != B.shape:
+            raise ValueError("porfs_: need a square matrix, its factor, and B / X with as many rows")
+        if not (A.dtype == U.dtype == B.dtype == X.dtype):
+            raise TypeError("porfs_: all operands must have the same dtype")
+        nrhs = B.shape[1]
+        ferr, berr = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+        dp = C.POINTER(C.c_double)
+        name = f"lsx_porfs_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, n, nrhs, A.data_ptr(), max(A.stride(0), 1), U.data_ptr(),
+                                        max(U.stride(0), 1), B.data_ptr(), max(B.stride(0), 1), X.data_ptr(),
+                                        max(X.stride(0), 1), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp)), name)
+        return ferr[:nrhs], berr[:nrhs]
+
     def geequ(self, A: torch.Tensor):
         """LAPACK's geequ on a tensor in HBM (lsx_geequ_*_dev): returns (r, c, stats) as device tensors -- the row and
         column scale factors in A's dtype and stats = [rowcnd, colcnd, amax, info] (4 doubles).  No host sync."""

@@ -461,6 +461,83 @@ class Matrix:
             raise self._not_pos_def(info)
         return X[:, 0] if vec else X
 
+    def solve_pos_def_array(self, rhs, bounds: bool = False):
+        """Solution(s) of self * X = rhs for a symmetric positive definite matrix through the Cholesky factorisation:
+        solve_array(rhs, pos_def=True), and with bounds=True refined by LAPACK's porfs (lsx_porfs_* / lsx_posvr_*)
+        and returned as (x, ferr, berr) like solve_array(bounds=True): per right-hand side a bound of
+        max|x - x_true| / max|x| and the componentwise backward error (floats for a vector rhs, arrays for a matrix).
+        One factorisation, no pivoting; only the upper triangle of self is used and symmetry is NOT checked.
+        ValueError naming the minor when a leading minor is not positive definite."""
+        if not bounds:
+            return self._solve_pos_def(rhs)
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            import torch
+
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            n = A.shape[0]
+            if A.shape[1] != n:
+                raise ValueError("solve_pos_def_array needs a square matrix")
+            B = rhs if hasattr(rhs, "is_cuda") else torch.as_tensor(np.asarray(rhs, dtype=np.float64))
+            B = B.to(device=A.device, dtype=torch.float64)
+            vec = B.dim() == 1
+            if B.shape[0] != n:
+                raise ValueError("Matrix dimensions must match")
+            dev = DeviceSolver(self._dev.device.index)
+            U = A.clone()
+            info = int(dev.potrf_(U).item()) if n else 0
+            if info != 0:
+                raise self._not_pos_def(info)
+            B = B.reshape(n, -1).contiguous()
+            X = B.clone()
+            if n and X.shape[1]:
+                dev.potrs_(U, X)
+            ferr, berr = dev.porfs_(A, U, B, X)
+            return (X[:, 0], float(ferr[0]), float(berr[0])) if vec else (X, ferr, berr)
+        A = self._array()
+        n = A.shape[0]
+        if A.shape[1] != n:
+            raise ValueError("solve_pos_def_array needs a square matrix")
+        B = np.asarray(rhs, dtype=np.float64)
+        vec = B.ndim == 1
+        if B.shape[0] != n:
+            raise ValueError("Matrix dimensions must match")
+        X, ferr, berr, info = dense.solve_pos_bounded(A, B.reshape(n, -1))
+        if info != 0:
+            raise self._not_pos_def(info)
+        return (X[:, 0], float(ferr[0]), float(berr[0])) if vec else (X, ferr, berr)
+
+    def rcond_pos_def(self) -> float:
+        """Reciprocal condition number 1 / (||A||_1 ||A^-1||_1) of a symmetric positive definite matrix from its
+        Cholesky factorisation: LAPACK's pocon estimate (lsx_porcond_f64 / lsx_pocon_f64_dev).  Only the upper triangle
+        of self is used.  ValueError naming the minor when a leading minor is not positive definite."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            if A.shape[0] != A.shape[1]:
+                raise ValueError("rcond_pos_def needs a square matrix")
+            dev = DeviceSolver(self._dev.device.index)
+            anorm = dev.norm_sym(A)
+            U = A.clone()
+            info = int(dev.potrf_(U).item()) if A.shape[0] else 0
+            if info != 0:
+                raise self._not_pos_def(info)
+            return dev.pocon(U, anorm)
+        A = self._array()
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("rcond_pos_def needs a square matrix")
+        rc, info = dense.rcond_pos(A)
+        if info != 0:
+            raise self._not_pos_def(info)
+        return rc
+
+    def cond_pos_def(self) -> float:
+        """Estimated 1-norm condition number 1 / rcond_pos_def(); inf when rcond_pos_def is 0."""
+        r = self.rcond_pos_def()
+        return float("inf") if r == 0.0 else 1.0 / r
+
     def solve_array(self, rhs, trans: bool = False, bounds: bool = False, equilibrate: bool = False,
                     pos_def: bool = False):
         """Unique solution(s) of self * X = rhs for a square matrix (rhs: vector or matrix) as an ndarray;
@@ -476,12 +553,14 @@ class Matrix:
         scaling is divided by the scales' spread and can be vacuous (include/lsx.h); berr is not affected.
         pos_def=True asserts that self is symmetric positive definite and takes the Cholesky factorisation (no pivoting,
         half the work).  Only the upper triangle of self is used and symmetry is NOT checked.  trans is accepted and
-        makes no difference (self is symmetric); bounds=True or equilibrate=True with it is a ValueError.  If a leading
+        makes no difference (self is symmetric); bounds=True or equilibrate=True with it is a ValueError
+        (solve_pos_def_array has the bounds).  If a leading
         minor turns out not to be positive definite the assertion was false: ValueError naming the minor, not
         NoSolution() -- the system may well have a solution."""
         if pos_def:
             if bounds or equilibrate:
-                raise ValueError("solve_array: pos_def=True cannot be combined with bounds=True or equilibrate=True")
+                raise ValueError("solve_array: pos_def=True cannot be combined with bounds=True or equilibrate=True "
+                                 "(solve_pos_def_array(rhs, bounds=True) gives the Cholesky solve with error bounds)")
             return self._solve_pos_def(rhs)
         if equilibrate:
             return self._solve_equilibrated(rhs, trans, bounds)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | gecon | gerfs | equil [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | posx | gecon | gerfs | equil [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -465,6 +465,97 @@ def main():
                       f"({split['gemm']['ms'] / tot * 100:.0f} % of the bracketed time, "
                       f"{split['gemm']['flops'] / max(split['gemm']['ms'], 1e-9) / 1e9:.1f} TFLOP/s)", flush=True)
                 del A, A0
+    if "posx" in args.what:
+        # Condition estimate and error bounds of the Cholesky family beside their LU counterparts on the SAME matrix
+        # G G^T / n + I, one process, medians of 7 after warm-up:
+        #   the symmetric residual pass against the general one (GB/s of the bytes each actually reads of A),
+        #   lsx_potrs_* at nrhs = 1 with potrs_few_max = 0 (block sweeps) and 8 (step kernels),
+        #   pocon against gecon on the LU factors, porfs against gerfs at nrhs = 1 and 8.
+        med = lambda fn: timeit(fn, reps=7, warm=2)[1]   # noqa: E731
+        for dt in (torch.float64, torch.float32):
+            sfx, es = ("f64", 8) if dt == torch.float64 else ("f32", 4)
+            for n in (4096, 8192):
+                G = torch.empty(n, n, dtype=dt, device="cuda")
+                dev.fill_(G, gen.U11, 1)
+                A = G @ G.t() / n + torch.eye(n, dtype=dt, device="cuda")   # plumbing: builds the input only
+                del G
+                XT = torch.empty(n, 8, dtype=dt, device="cuda")
+                dev.fill_(XT, gen.U11, 2)
+                B = A @ XT
+                R, W = torch.empty_like(B), torch.empty_like(B)
+                hook_sym = getattr(dev.lib, f"lsx_diag_resid_bound_sym_{sfx}_dev")
+                hook_gen = getattr(dev.lib, f"lsx_diag_resid_bound_{sfx}_dev")
+                for nr in (1, 8):
+                    ts = med(lambda: hook_sym(dev.h.ptr, n, nr, A.data_ptr(), n, B.data_ptr(), 8, XT.data_ptr(), 8,
+                                              R.data_ptr(), W.data_ptr(), 8))
+                    tg = med(lambda: hook_gen(dev.h.ptr, 0, n, nr, A.data_ptr(), n, B.data_ptr(), 8, XT.data_ptr(), 8,
+                                              R.data_ptr(), W.data_ptr(), 8))
+                    print(f"posx {sfx} n={n} resid NR={nr}: symmetric {ts * 1e3:.1f} us ({es * n * (n + 1) / 2 / ts / 1e6:.0f} GB/s "
+                          f"of n(n+1)/2 elements)  general {tg * 1e3:.1f} us ({es * n * n / tg / 1e6:.0f} GB/s of n^2)  "
+                          f"| symmetric/general {ts / tg:.2f}", flush=True)
+                U = A.clone()
+                info = dev.potrf_(U)
+                LU = A.clone()
+                ipiv, linfo = dev.getrf_(LU)
+                assert int(info.item()) == 0 and int(linfo.item()) == 0
+                x = torch.empty(n, 1, dtype=dt, device="cuda")
+                tp = {}
+                for few in (0, 8):
+                    dev.h.set_option("potrs_few_max", few)
+
+                    def solve1():
+                        x.copy_(B[:, :1])
+                        dev.potrs_(U, x)
+                    tp[few] = med(solve1)
+                    assert dev.h.get_option("potrs_path") == (1 if few else 0)
+                dev.h.set_option("potrs_few_max", 0)
+
+                def lusolve1():
+                    x.copy_(B[:, :1])
+                    dev.getrs_(LU, ipiv, x)
+                tl = med(lusolve1)
+                print(f"posx {sfx} n={n} potrs nrhs=1: sweeps {tp[0] * 1e3:.1f} us  step kernels {tp[8] * 1e3:.1f} us  "
+                      f"| steps/sweeps {tp[8] / tp[0]:.2f}   (getrs nrhs=1: {tl * 1e3:.1f} us)", flush=True)
+                anorm = float(dev.norm_sym(A).item())
+                t0 = time.perf_counter()
+                reps = 5
+                for _ in range(reps):
+                    rp = dev.pocon(U, anorm)
+                tpo = (time.perf_counter() - t0) / reps * 1e3
+                sp = dev.h.get_option("pocon_solves")
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    rg = dev.rcond(LU, ipiv, anorm, 1)
+                tge = (time.perf_counter() - t0) / reps * 1e3
+                sg = dev.h.get_option("gecon_solves")
+                print(f"posx {sfx} n={n} pocon {tpo:.3f} ms ({sp} solves, rcond {rp:.3e})  gecon {tge:.3f} ms ({sg} solves, "
+                      f"rcond {rg:.3e})  | pocon/gecon {tpo / tge:.2f}  (host wall clock, both synchronise)", flush=True)
+                for nr in (1, 8):
+                    Bk = B[:, :nr].contiguous()
+                    X0 = Bk.clone()
+                    dev.potrs_(U, X0)
+                    sgn = torch.where(torch.arange(n, device="cuda") % 2 == 0, 1 + 2.0 ** -10, 1 - 2.0 ** -10).to(dt)
+                    X0 = X0 * sgn[:, None]                    # the tests' perturbed start: one to three steps
+                    X = X0.clone()
+                    tt = {}
+                    for name in ("porfs", "gerfs"):
+                        ts_ = []
+                        for _ in range(reps + 1):
+                            X.copy_(X0)
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            if name == "porfs":
+                                dev.porfs_(A, U, Bk, X)
+                            else:
+                                dev.gerfs_(A, LU, ipiv, Bk, X)
+                            ts_.append((time.perf_counter() - t0) * 1e3)
+                        tt[name] = sorted(ts_[1:])[len(ts_[1:]) // 2]
+                        tt[name + "_steps"] = dev.h.get_option(name + "_steps")
+                        tt[name + "_solves"] = dev.h.get_option(name + "_solves")
+                    print(f"posx {sfx} n={n} nrhs={nr}: porfs {tt['porfs']:.3f} ms ({tt['porfs_steps']} steps, "
+                          f"{tt['porfs_solves']} estimator solves)  gerfs {tt['gerfs']:.3f} ms ({tt['gerfs_steps']} steps, "
+                          f"{tt['gerfs_solves']} solves)  | porfs/gerfs {tt['porfs'] / tt['gerfs']:.2f}", flush=True)
+                del A, U, LU, B, XT, R, W
     if "gecon" in args.what:
         # the condition estimate beside the factorisation it follows (fp64, 1-norm; medians)
         for n in (1024, 4096, 8192):
