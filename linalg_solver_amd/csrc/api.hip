@@ -21,25 +21,24 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-static int grow(void **p, size_t *have, size_t need) {
-    if (need <= *have) return LSX_OK;
-    if (*p) {
-        LSX_HIP(hipFree(*p));
-        *p = nullptr;
-        *have = 0;
+int reserve(lsx_handle_t h, DevBuf &b, size_t need, bool *fresh) {
+    if (need <= b.bytes) return LSX_OK;
+    if (b.p) {
+        LSX_HIP(hipStreamSynchronize(h->stream));   // the old block goes: nothing queued may still use it
+        LSX_HIP(hipFree(b.p));
+        b = DevBuf();
     }
     need = (need + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);
-    hipError_t e = hipMalloc(p, need);
+    hipError_t e = hipMalloc(&b.p, need);
     if (e != hipSuccess) {
         set_error("hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-        *p = nullptr;
+        b.p = nullptr;
         return LSX_ERR_ALLOC;
     }
-    *have = need;
+    b.bytes = need;
+    if (fresh) *fresh = true;
     return LSX_OK;
 }
-
-int ensure_ws(lsx_handle_t h, size_t bytes) { return grow(&h->ws, &h->ws_bytes, bytes); }
 
 // Every entry point runs with the handle's device current and puts the caller's back on the way out: with two
 // handles in one process, or torch's current device elsewhere, workspaces and launches would land on the wrong GPU.
@@ -69,12 +68,6 @@ static int check_dev_status(lsx_handle_t h) {
     return LSX_ERR_INTERNAL;
 }
 
-static int ensure_scratch(lsx_handle_t h, size_t bytes) {
-    // growing frees the old block: make sure nothing queued still uses it
-    if (bytes > h->scratch_bytes) LSX_HIP(hipStreamSynchronize(h->stream));
-    return grow(&h->scratch, &h->scratch_bytes, bytes);
-}
-
 ProfScope::ProfScope(lsx_handle_t h_, int bucket, double flops, double bytes) : h(h_), st(h_->stream) {
     Prof &p = h->prof;
     if (!((p.mask >> bucket) & 1u)) return;
@@ -100,20 +93,6 @@ ProfScope::ProfScope(lsx_handle_t h_, int bucket, double flops, double bytes) : 
 ProfScope::~ProfScope() {
     if (idx >= 0) (void)hipEventRecord(h->prof.pending[idx].b, st);
 }
-
-// simple bump carving of a device block
-struct Carver {
-    char *base;
-    size_t off = 0;
-    explicit Carver(void *b) : base((char *)b) {}
-    template <typename U>
-    U *take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        U *p = (U *)(base + off);
-        off += count * sizeof(U);
-        return p;
-    }
-};
 
 static size_t pad256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -172,16 +151,16 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
     // Exchange areas of the pipelined panel: two, used alternately, and cleared HERE on the main stream as
     // soon as their panel has finished -- a clear in front of every panel launch sits on the chain.
     size_t area = panel_pipe_area_bytes(h, pa.mode, pa.nt, pa.rt, n - k0);
-    if (2 * area > h->scratch_bytes) area = 0;
-    if (area) LSX_HIP(hipMemsetAsync(h->scratch, 0, 2 * area, main_s));
+    if (2 * area > h->scratch.bytes) area = 0;
+    if (area) LSX_HIP(hipMemsetAsync(h->scratch.p, 0, 2 * area, main_s));
     // Counted first tile column of the big update (fp64, this driver as the phase in front of getrf_lookahead_x): the
     // chain of step k then waits, inside its first kernel, for update k-1 on the NEXT panel's columns only and runs
     // beside the rest of that update -- the update of step k follows update k-1 without the chain in between
     // (16384^2: the chain was ~45 us of every one of the 64 steps of this phase).
     const int nst = (n - k0 + nb - 1) / nb;
     int *c0words = nullptr;
-    if (sizeof(T) == 8 && k_stop > 0 && area && 2 * area + pad256((size_t)nst * sizeof(int)) <= h->scratch_bytes && !h->x_events) {
-        c0words = (int *)((char *)h->scratch + 2 * area);
+    if (sizeof(T) == 8 && k_stop > 0 && area && 2 * area + pad256((size_t)nst * sizeof(int)) <= h->scratch.bytes && !h->x_events) {
+        c0words = (int *)((char *)h->scratch.p + 2 * area);
         LSX_HIP(hipMemsetAsync(c0words, 0, (size_t)nst * sizeof(int), main_s));
     }
     bool prev_counted = false;
@@ -269,7 +248,7 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
         bool cur_counted = false;
         int cur_tiles = 0;
         // panel k is done with its exchange area; panel k+2 reuses it, behind ev_next below
-        if (area) LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)(step & 1) * area, 0, area, main_s));
+        if (area) LSX_HIP(hipMemsetAsync((char *)h->scratch.p + (size_t)(step & 1) * area, 0, area, main_s));
         if (rest > jb2) {
             LSX_TRY(apply_panel_swaps<T>(h, mv, rest - jb2, A + k + jb + jb2, lda, k, jb, d_ipiv + k));
             LSX_TRY(launch_trsm_block<T>(h, 1, jb, rest - jb2, Akk, lda, Ti, A12 + jb2, lda));
@@ -319,24 +298,24 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
     const size_t pass_bytes = pad256(256 + (size_t)nsteps * sizeof(int)), ctr_bytes = pad256((size_t)nsteps * 8 * sizeof(int));
     const size_t col0_bytes = pad256((size_t)nsteps * 2 * sizeof(int));
     const size_t words = pass_bytes + ctr_bytes + col0_bytes + pad256((size_t)nsteps * sizeof(int));
-    if (area_x == 0 || 3 * area_x + words > h->scratch_bytes) { set_error("getrf_lookahead_x: scratch"); return LSX_ERR_INTERNAL; }
-    LSX_TRY(grow(&h->moves_all, &h->moves_all_bytes, (size_t)nsteps * 2048));
+    if (area_x == 0 || 3 * area_x + words > h->scratch.bytes) { set_error("getrf_lookahead_x: scratch"); return LSX_ERR_INTERNAL; }
+    LSX_TRY(reserve(h, h->moves_all, (size_t)nsteps * 2048));
     JoinSide join{h, side, main_s, main_s};
     // three exchange areas in rotation (panel j uses area j % 3, cleared behind update j), then the words
-    char *wbase = (char *)h->scratch + 3 * area_x;
+    char *wbase = (char *)h->scratch.p + 3 * area_x;
     int *xcc_word = (int *)wbase;                    // 1 + XCC id of the panel's XCD (blocks = 0 mod 8 land on XCC 0)
     int *pass = (int *)(wbase + 256);                // per step: update workgroups that left the panel's XCD
     int *counters = (int *)(wbase + pass_bytes);     // per step: the update's eight strip queues
     int *col0 = (int *)(wbase + pass_bytes + ctr_bytes);   // per step: {ticket, finished tiles} of the update's tile column 0
     int *ready = (int *)(wbase + pass_bytes + ctr_bytes + col0_bytes);   // per step: block inverses finished (fused chain launch)
-    for (int s = 0; s < 3; ++s) LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)s * area_x, 0, area_x, main_s));
+    for (int s = 0; s < 3; ++s) LSX_HIP(hipMemsetAsync((char *)h->scratch.p + (size_t)s * area_x, 0, area_x, main_s));
     LSX_HIP(hipMemsetAsync(wbase, 0, words, main_s));
     LSX_HIP(hipMemsetD32Async((hipDeviceptr_t)xcc_word, 1, 1, main_s));
     pa.area_bytes = area_x;
     pa.xcc_word = xcc_word;
     LSX_HIP(hipEventRecord(h->ev_start, main_s));
     LSX_HIP(hipStreamWaitEvent(side, h->ev_start, 0));
-    auto list = [&](int s) { return (int2 *)((char *)h->moves_all + (size_t)s * 2048); };   // one gather list per panel
+    auto list = [&](int s) { return (int2 *)((char *)h->moves_all.p + (size_t)s * 2048); };   // one gather list per panel
     T *Tinv2[2] = {Tinv, Tinv + (size_t)((nb + 63) / 64) * 4096};
     {
         OnStream g(h, side);
@@ -422,7 +401,7 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
         const bool cur_col0 = did.queued && did.col0_complete;
         // panel k is done with its exchange area and panel k+3 reuses it: cleared behind the update, off the path
         // HEAD -> update start -> panel k+1; the chain of panel k+3 waits for (a part of) update k+1, behind this
-        LSX_HIP(hipMemsetAsync((char *)h->scratch + (size_t)(step % 3) * area_x, 0, area_x, main_s));
+        LSX_HIP(hipMemsetAsync((char *)h->scratch.p + (size_t)(step % 3) * area_x, 0, area_x, main_s));
         LSX_HIP(hipEventRecord(h->ev_next, main_s));
         // panel k's interchanges on the columns LEFT of it: behind the update, where this stream only waits for the next
         // HEAD (one launch for all panels at the very end was 0.3 ms of an 8192^2 factorisation, on the critical path).
@@ -462,16 +441,16 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
     return launch_laswp_left_all<T>(h, A, lda, k0 + left_done * nb, nb, nsteps - left_done, list(left_done));
 }
 
-// Workspaces of one factorisation of order n: scratch (panel partials, gather lists, three XCD-scope exchange areas
-// and the driver's words) and ws2 (block inverses, two sets: the look-ahead driver alternates).  One computation for
-// getrf_dev and the multi-device driver (mg.hip), so the two cannot drift apart.
+// Workspaces of one factorisation of order n: scratch and tinv (block inverses, two sets: the look-ahead driver
+// alternates).  One computation for getrf_dev and the multi-device driver (mg.hip), so the two cannot drift apart.
 int ensure_getrf_workspace(lsx_handle_t h, int n, size_t elem) {
-    LSX_TRY(ensure_scratch(h, pad256(16 * ((size_t)n / 32 + 2)) + 2 * pad256(elem * 2 * (size_t)n) +
-                                  ((size_t)n / 32 + 2) * 5248 + 8192 +
-                                  3 * panel_x_area_bytes(h, h->panel_mode, n, elem) + 16384 +
-                                  ((size_t)n / 16 + 2) * 40));
+    const size_t panel = panel_scratch_bytes(n);                                  // a panel launch that clears its own area
+    const size_t row_bufs = 2 * pad256(elem * 2 * (size_t)n);                      // two buffers of 2 n elements
+    const size_t xcd_areas = 3 * panel_x_area_bytes(h, h->panel_mode, n, elem);    // getrf_lookahead_x rotates three
+    const size_t driver_words = 16384 + ((size_t)n / 16 + 2) * 40;                 // its per-step counters and flags
+    LSX_TRY(reserve(h, h->scratch, panel + row_bufs + xcd_areas + driver_words));
     const size_t tinv_elems = (size_t)((h->nb * h->kblock + 63) / 64) * 64 * 64;
-    return grow(&h->ws2, &h->ws2_bytes, 2 * pad256(tinv_elems * elem));   // x2: the look-ahead driver alternates
+    return reserve(h, h->tinv, 2 * pad256(tinv_elems * elem));   // x2: the look-ahead driver alternates
 }
 
 // ---------------------------------------------------------------- blocked LU driver
@@ -487,7 +466,7 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
     GemmPlan mfma;   // every update of an LU: see GemmPlan
     mfma.mfma_only = true;
     LSX_TRY(ensure_getrf_workspace(h, n, sizeof(T)));
-    T *Tinv = (T *)h->ws2;
+    T *Tinv = (T *)h->tinv.p;
     if (!d_info) d_info = h->dev_status + 2;   // a time-out must be recorded somewhere: lsx_check_status reads it
     LSX_HIP(hipMemsetAsync(d_info, 0, sizeof(int), h->stream));
     // Look-ahead (panel k+1 on a side stream under the update of step k; bit-identical factors).  Measured
@@ -638,13 +617,29 @@ static bool sweep_pairs(lsx_handle_t h, int n, int ncols) {
     return h->getri_pairs && ncols >= 1024 && (n >= 7168 || (n % 128 == 0 && n >= 4096));
 }
 
+// elements of the 64 x 64 (launch_trtri's layout) and of the 128 x 128 diagonal-block inverses of one triangle of order n
+static size_t inv64_elems(int n) { return (size_t)((n + 63) / 64) * 64 * 64; }
+static size_t inv128_elems(int n) { return (size_t)((n + 127) / 128) * 128 * 128; }
+// tinv for the sweeps above: the 64 x 64 block inverses of both triangles
+template <typename T>
+static int carve_inv64(lsx_handle_t h, int n, T **TinvL, T **TinvU) {
+    return carve(h, h->tinv, [&](Carver &c) { *TinvL = c.take<T>(inv64_elems(n)); *TinvU = c.take<T>(inv64_elems(n)); });
+}
+// tinv for the few-column and transposed solves: both sizes, both triangles
+template <typename T> struct BlockInv { T *inv64L = nullptr, *inv64U = nullptr, *inv128L = nullptr, *inv128U = nullptr; };
+template <typename T>
+static int carve_block_inv(lsx_handle_t h, int n, BlockInv<T> *bi) {
+    return carve(h, h->tinv, [&](Carver &c) {
+        bi->inv64L = c.take<T>(inv64_elems(n)); bi->inv64U = c.take<T>(inv64_elems(n));
+        bi->inv128L = c.take<T>(inv128_elems(n)); bi->inv128U = c.take<T>(inv128_elems(n));
+    });
+}
+
 // X <- U^-1 L^-1 X for X already row-permuted (n x nrhs)
 template <typename T>
 static int lu_solve_permuted(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, T *X, int ldx) {
-    const size_t blk = (size_t)((n + 63) / 64) * 64 * 64;
-    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, 2 * pad256(blk * sizeof(T))));
-    T *TinvL = (T *)h->ws2;
-    T *TinvU = (T *)((char *)h->ws2 + pad256(blk * sizeof(T)));
+    T *TinvL = nullptr, *TinvU = nullptr;
+    LSX_TRY(carve_inv64(h, n, &TinvL, &TinvU));
     LSX_TRY(launch_trtri<T>(h, 1, n, LU, lda, TinvL));
     LSX_TRY(launch_trtri<T>(h, 0, n, LU, lda, TinvU));
     const bool pairs = sweep_pairs(h, n, nrhs);
@@ -661,36 +656,32 @@ static int getrs_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, cons
     // few right-hand sides: the solve-latency path (kernels_trsv.hip) works on 1, 2, 4 or 8 columns
     const int nr = nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8;
     if (nrhs <= 8 && n > 128) {
-        const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
-        const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
-        const size_t vec = pad256(sizeof(T) * (size_t)n * nr);
-        LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(int32_t) * n) + 3 * vec));
-        LSX_TRY(grow(&h->ws2, &h->ws2_bytes, 2 * b64 + 2 * b128));
-        LSX_TRY(ensure_scratch(h, 512 + 2 * (size_t)((n + 127) / 128) * 128 * nr * 16));  // the solve's exchange area
-        int32_t *perm = (int32_t *)h->ws3;
-        T *Bc = (T *)((char *)h->ws3 + pad256(sizeof(int32_t) * n));  // copy of B, zero-padded to nr columns
-        T *Bp = (T *)((char *)Bc + vec);                               // P * B, work space of the solve
-        T *X = (T *)((char *)Bp + vec);
-        char *w2 = (char *)h->ws2;
+        int32_t *perm = nullptr; T *Bc = nullptr, *Bp = nullptr, *X = nullptr;
+        LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) {
+            perm = c.take<int32_t>(n);
+            Bc = c.take<T>((size_t)n * nr);   // copy of B, zero-padded to nr columns
+            Bp = c.take<T>((size_t)n * nr);   // P * B, work space of the solve
+            X = c.take<T>((size_t)n * nr);
+        }));
+        BlockInv<T> bi;
+        LSX_TRY(carve_block_inv<T>(h, n, &bi));
+        LSX_TRY(reserve(h, h->scratch, few_rhs_scratch_bytes(n, nr)));
         if (h->trsv_mode == 2) {   // 128-row steps, helper workgroups, interchanges + gather fused into the preparation launch
-            const int r2 = lu_solve_few_rhs2<T>(h, n, nrhs, nr, LU, lda, d_ipiv, B, ldb, (T *)w2, (T *)(w2 + b64),
-                                                (T *)(w2 + 2 * b64), (T *)(w2 + 2 * b64 + b128), Bp, X);
+            const int r2 = lu_solve_few_rhs2<T>(h, n, nrhs, nr, LU, lda, d_ipiv, B, ldb, bi.inv64L, bi.inv64U, bi.inv128L,
+                                                bi.inv128U, Bp, X);
             if (r2 != 1) return r2;
         }
         LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
         if (nr != nrhs) LSX_HIP(hipMemsetAsync(Bc, 0, sizeof(T) * (size_t)n * nr, h->stream));
         LSX_TRY(launch_copy2d<T>(h, n, nrhs, B, ldb, Bc, nr));
         LSX_TRY(launch_gather_rows<T>(h, n, nr, perm, Bc, nr, Bp, nr));
-        char *w = (char *)h->ws2;
-        LSX_TRY(lu_solve_few_rhs<T>(h, n, nr, LU, lda, Bp, nr, X, (T *)w, (T *)(w + b64), (T *)(w + 2 * b64),
-                                    (T *)(w + 2 * b64 + b128)));
+        LSX_TRY(lu_solve_few_rhs<T>(h, n, nr, LU, lda, Bp, nr, X, bi.inv64L, bi.inv64U, bi.inv128L, bi.inv128U));
         return launch_copy2d<T>(h, n, nrhs, X, nr, B, ldb);
     }
     // perm + a copy of B for the row gather
-    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(int32_t) * n) + pad256(sizeof(T) * (size_t)n * nrhs)));
-    int32_t *perm = (int32_t *)h->ws3;
-    T *Bc = (T *)((char *)h->ws3 + pad256(sizeof(int32_t) * n));
-    LSX_TRY(ensure_scratch(h, 8 * (size_t)n + 256));   // index arrays of the permutation conversion
+    int32_t *perm = nullptr; T *Bc = nullptr;
+    LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) { perm = c.take<int32_t>(n); Bc = c.take<T>((size_t)n * nrhs); }));
+    LSX_TRY(reserve(h, h->scratch, ipiv_to_perm_scratch_bytes(n)));
     LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
     LSX_TRY(launch_copy2d<T>(h, n, nrhs, B, ldb, Bc, nrhs));
     LSX_TRY(launch_gather_rows<T>(h, n, nrhs, perm, Bc, nrhs, B, ldb));
@@ -702,9 +693,9 @@ static int getri_dev(lsx_handle_t h, int n, const T *LU, int lda, const int32_t 
                      int ldi) {
     LSX_ARG(n >= 0 && lda >= n && ldi >= n && LU && d_ipiv && Inv);
     if (n == 0) return LSX_OK;
-    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(int32_t) * n)));
-    int32_t *perm = (int32_t *)h->ws3;
-    LSX_TRY(ensure_scratch(h, 8 * (size_t)n + 256));
+    int32_t *perm = nullptr;
+    LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) { perm = c.take<int32_t>(n); }));
+    LSX_TRY(reserve(h, h->scratch, ipiv_to_perm_scratch_bytes(n)));
     LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
     if (n >= 512 && !h->getri_plain) {
         // A^-1 = U^-1 L^-1 P with the permutation applied LAST: L^-1 of the identity is lower triangular, so the
@@ -712,13 +703,10 @@ static int getri_dev(lsx_handle_t h, int n, const T *LU, int lda, const int32_t 
         // of n^3 (4/3 n^3 for the inverse, LAPACK's getri count, instead of 2 n^3).  The skipped operations are
         // multiplications by exact zeros, so every entry has the bits the plain form below gives it.
         const int ldw = (n + 15) & ~15;
-        LSX_TRY(grow(&h->ws5, &h->ws5_bytes, sizeof(T) * (size_t)n * ldw));
-        T *W = (T *)h->ws5;
+        T *W = nullptr, *TinvL = nullptr, *TinvU = nullptr;
+        LSX_TRY(carve(h, h->getri_work, [&](Carver &c) { W = c.take<T>((size_t)n * ldw); }));
         LSX_TRY(launch_set_identity_perm<T>(h, n, nullptr, W, ldw));
-        const size_t blk = (size_t)((n + 63) / 64) * 64 * 64;
-        LSX_TRY(grow(&h->ws2, &h->ws2_bytes, 2 * pad256(blk * sizeof(T))));
-        T *TinvL = (T *)h->ws2;
-        T *TinvU = (T *)((char *)h->ws2 + pad256(blk * sizeof(T)));
+        LSX_TRY(carve_inv64(h, n, &TinvL, &TinvU));
         LSX_TRY(launch_trtri<T>(h, 1, n, LU, lda, TinvL));
         LSX_TRY(launch_trtri<T>(h, 0, n, LU, lda, TinvU));
         const bool pairs = sweep_pairs(h, n, n);
@@ -780,11 +768,8 @@ static int getrf_host(lsx_handle_t h, int n, T *A, int lda, int32_t *ipiv, int *
     if (info) *info = 0;
     if (n == 0) return LSX_OK;
     const int ld = ld_for(n);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(int32_t) * n) + 512));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    int32_t *dp = c.take<int32_t>(n);
-    int *dinfo = c.take<int>(1);
+    T *dA = nullptr; int32_t *dp = nullptr; int *dinfo = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dA = c.take<T>((size_t)n * ld); dp = c.take<int32_t>(n); dinfo = c.take<int>(1); }));
     int hinfo = 0;
     LSX_TRY(factor_from_host<T>(h, n, A, lda, dA, ld, dp, dinfo, &hinfo));
     LSX_TRY(d2h<T>(h, n, n, dA, ld, A, lda));
@@ -801,12 +786,12 @@ static int getrs_host(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, con
     if (n == 0 || nrhs == 0) return LSX_OK;
     LSX_ARG(LU && ipiv && B);
     const int ld = ld_for(n), ldx = ld_for(nrhs);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(T) * (size_t)n * ldx) +
-                             pad256(sizeof(int32_t) * n) + 512));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldx);
-    int32_t *dp = c.take<int32_t>(n);
+    T *dA = nullptr, *dB = nullptr; int32_t *dp = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld);
+        dB = c.take<T>((size_t)n * ldx);
+        dp = c.take<int32_t>(n);
+    }));
     LSX_TRY(h2d<T>(h, n, n, LU, lda, dA, ld));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
     LSX_HIP(hipMemcpyAsync(dp, ipiv, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
@@ -826,14 +811,14 @@ static int gesv_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, T *B,
     if (n == 0) return LSX_OK;
     LSX_ARG(A && (nrhs == 0 || B));
     const int ld = ld_for(n), ldx = ld_for(nrhs > 0 ? nrhs : 1);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(T) * (size_t)n * ldx) +
-                             pad256(sizeof(int32_t) * n) + 1024));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldx);
-    int32_t *dp = c.take<int32_t>(n);
-    int *dinfo = c.take<int>(1);
-    double *dprobe = c.take<double>(2);
+    T *dA = nullptr, *dB = nullptr; int32_t *dp = nullptr; int *dinfo = nullptr; double *dprobe = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld);
+        dB = c.take<T>((size_t)n * ldx);
+        dp = c.take<int32_t>(n);
+        dinfo = c.take<int>(1);
+        dprobe = c.take<double>(2);
+    }));
     if (nrhs > 0) LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
     LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
     LSX_TRY(launch_amax<T>(h, n, n, dA, ld, dprobe));
@@ -911,11 +896,9 @@ static int potrf_dev(lsx_handle_t h, int n, T *A, int lda, int *d_info) {
     if (n == 0) return LSX_OK;
     LSX_ARG(A);
     const int sb = 128, ldw = ld_for(n);
-    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, 256 + pad256(sizeof(T) * sb * sb)));
-    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(T) * (size_t)sb * ldw)));
-    int *winfo = (int *)h->ws2;
-    T *Vinv = (T *)((char *)h->ws2 + 256);
-    T *W = (T *)h->ws3;
+    int *winfo = nullptr; T *Vinv = nullptr, *W = nullptr;
+    LSX_TRY(carve(h, h->tinv, [&](Carver &c) { winfo = c.take<int>(1); Vinv = c.take<T>((size_t)sb * sb); }));
+    LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) { W = c.take<T>((size_t)sb * ldw); }));
     LSX_HIP(hipMemsetAsync(winfo, 0, sizeof(int), h->stream));
     for (int kb = 0; kb < n; kb += sb) {
         const int jb = (n - kb < sb) ? n - kb : sb, rest = n - kb - jb;
@@ -935,7 +918,7 @@ static int potrf_dev(lsx_handle_t h, int n, T *A, int lda, int *d_info) {
 
 // Few right-hand sides (kernels_posx.hip): one launch per 128-row block step and direction on a dense n x nr copy of
 // the columns, nothing cooperative.  prepare forms the block inverses once (pocon and porfs solve many times with one
-// factor); nothing else may grow ws2 or ws3 between prepare and the last apply.
+// factor); nothing else may grow tinv or rhs_work between prepare and the last apply.
 template <typename T>
 struct PotrsFew {
     const T *inv128 = nullptr;
@@ -943,13 +926,11 @@ struct PotrsFew {
 };
 template <typename T>
 static int potrs_few_prepare(lsx_handle_t h, int n, const T *U, int lda, PotrsFew<T> *pf) {
-    const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
-    const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
-    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, b64 + b128));
-    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(T) * (size_t)n * 8)));
-    pf->inv128 = (const T *)((char *)h->ws2 + b64);
-    pf->W = (T *)h->ws3;
-    return launch_chol_inv<T>(h, n, U, lda, (T *)h->ws2, (T *)((char *)h->ws2 + b64));
+    T *inv64 = nullptr, *inv128 = nullptr;
+    LSX_TRY(carve(h, h->tinv, [&](Carver &c) { inv64 = c.take<T>(inv64_elems(n)); inv128 = c.take<T>(inv128_elems(n)); }));
+    LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) { pf->W = c.take<T>((size_t)n * 8); }));
+    pf->inv128 = inv128;
+    return launch_chol_inv<T>(h, n, U, lda, inv64, inv128);
 }
 // B (n x nrhs, 1 <= nrhs <= 8) <- inv(U) inv(U^T) B
 template <typename T>
@@ -976,13 +957,9 @@ static int potrs_dev(lsx_handle_t h, int n, int nrhs, const T *U, int lda, T *B,
         return potrs_few_apply<T>(h, n, nrhs, U, lda, pf, B, ldb);
     }
     const int sb = 128, ldw = ld_for(nrhs);
-    const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
-    const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
-    const size_t arr = pad256(sizeof(T) * (size_t)n * ldw);
-    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, b64 + b128));
-    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, 2 * arr));
-    T *inv64 = (T *)h->ws2, *inv128 = (T *)((char *)h->ws2 + b64);
-    T *W = (T *)h->ws3, *Y = (T *)((char *)h->ws3 + arr);
+    T *inv64 = nullptr, *inv128 = nullptr, *W = nullptr, *Y = nullptr;
+    LSX_TRY(carve(h, h->tinv, [&](Carver &c) { inv64 = c.take<T>(inv64_elems(n)); inv128 = c.take<T>(inv128_elems(n)); }));
+    LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) { W = c.take<T>((size_t)n * ldw); Y = c.take<T>((size_t)n * ldw); }));
     auto Up = [&](int r, int c) { return U + (size_t)r * lda + c; };
     auto Wp = [&](int r) { return W + (size_t)r * ldw; };
     auto Yp = [&](int r) { return Y + (size_t)r * ldw; };
@@ -1020,10 +997,8 @@ static int potrf_host(lsx_handle_t h, int n, T *A, int lda, int *info) {
     LSX_ARG(A);
     if (info) *info = 0;
     const int ld = ld_for(n);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + 512));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    int *dinfo = c.take<int>(1);
+    T *dA = nullptr; int *dinfo = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dA = c.take<T>((size_t)n * ld); dinfo = c.take<int>(1); }));
     int hinfo = 0;
     LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
     LSX_TRY(potrf_dev<T>(h, n, dA, ld, dinfo));
@@ -1040,10 +1015,8 @@ static int potrs_host(lsx_handle_t h, int n, int nrhs, const T *U, int lda, T *B
     if (n == 0 || nrhs == 0) return LSX_OK;
     LSX_ARG(U && B);
     const int ld = ld_for(n), ldx = ld_for(nrhs);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(T) * (size_t)n * ldx) + 512));
-    Carver c(h->ws);
-    T *dU = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldx);
+    T *dU = nullptr, *dB = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dU = c.take<T>((size_t)n * ld); dB = c.take<T>((size_t)n * ldx); }));
     LSX_TRY(upper_h2d<T>(h, n, U, lda, dU, ld));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
     LSX_TRY(potrs_dev<T>(h, n, nrhs, dU, ld, dB, ldx));
@@ -1059,11 +1032,12 @@ static int posv_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, T *B,
     LSX_ARG(A && B);
     if (info) *info = 0;
     const int ld = ld_for(n), ldx = ld_for(nrhs);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(T) * (size_t)n * ldx) + 512));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldx);
-    int *dinfo = c.take<int>(1);
+    T *dA = nullptr, *dB = nullptr; int *dinfo = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld);
+        dB = c.take<T>((size_t)n * ldx);
+        dinfo = c.take<int>(1);
+    }));
     int hinfo = 0;
     LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
@@ -1097,29 +1071,32 @@ static int getrs_t_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, co
     if (n <= 128)   // one workgroup, interchanges included: no work space
         return lu_solve_transposed<T>(h, n, nrhs, LU, lda, d_ipiv, nullptr, B, ldb, (T *)nullptr, (T *)nullptr,
                                       (T *)nullptr, (T *)nullptr, (T *)nullptr);
-    const size_t b64 = pad256((size_t)((n + 63) / 64) * 64 * 64 * sizeof(T));
-    const size_t b128 = pad256((size_t)((n + 127) / 128) * 128 * 128 * sizeof(T));
-    const size_t vec = pad256(sizeof(T) * (size_t)n * 8);
     // blocked path: two n x nrhs work arrays (ld = ldw) in place of the n x 8 work vector
     const bool blocked = may_block && h->getrs_t_blocked_min > 0 && nrhs >= h->getrs_t_blocked_min;
     const int ldw = ld_for(nrhs);
-    const size_t arr = pad256(sizeof(T) * (size_t)n * ldw);
-    LSX_TRY(grow(&h->ws3, &h->ws3_bytes, pad256(sizeof(int32_t) * n) + (blocked ? 2 * arr : 3 * vec)));
-    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, 2 * b64 + 2 * b128));
-    LSX_TRY(ensure_scratch(h, 8 * (size_t)n + 256));   // index arrays of the permutation conversion
-    int32_t *perm = (int32_t *)h->ws3;
-    T *W = (T *)((char *)h->ws3 + pad256(sizeof(int32_t) * n));
-    char *w2 = (char *)h->ws2;
-    if (blocked) {
-        LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
-        LSX_TRY(launch_inv128_natural<T>(h, n, LU, lda, (T *)w2, (T *)(w2 + b64), (T *)(w2 + 2 * b64), (T *)(w2 + 2 * b64 + b128)));
-        h->getrs_t_path = 1;
-        return lu_solve_transposed_blocked<T>(h, n, nrhs, LU, lda, perm, B, ldb, (const T *)(w2 + 2 * b64),
-                                              (const T *)(w2 + 2 * b64 + b128), W, (T *)((char *)W + arr), ldw);
-    }
+    int32_t *perm = nullptr; T *W = nullptr, *Y = nullptr;
+    LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) {
+        perm = c.take<int32_t>(n);
+        if (blocked) {
+            W = c.take<T>((size_t)n * ldw);
+            Y = c.take<T>((size_t)n * ldw);
+        } else {   // all three n x 8 pieces of getrs_dev's few-column layout: the two solves grow rhs_work alike
+            W = c.take<T>((size_t)n * 8);
+            c.take<T>((size_t)n * 8);
+            c.take<T>((size_t)n * 8);
+        }
+    }));
+    BlockInv<T> bi;
+    LSX_TRY(carve_block_inv<T>(h, n, &bi));
+    LSX_TRY(reserve(h, h->scratch, ipiv_to_perm_scratch_bytes(n)));
     LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
-    return lu_solve_transposed<T>(h, n, nrhs, LU, lda, d_ipiv, perm, B, ldb, (T *)w2, (T *)(w2 + b64), (T *)(w2 + 2 * b64),
-                                  (T *)(w2 + 2 * b64 + b128), W);
+    if (blocked) {
+        LSX_TRY(launch_inv128_natural<T>(h, n, LU, lda, bi.inv64L, bi.inv64U, bi.inv128L, bi.inv128U));
+        h->getrs_t_path = 1;
+        return lu_solve_transposed_blocked<T>(h, n, nrhs, LU, lda, perm, B, ldb, (const T *)bi.inv128L,
+                                              (const T *)bi.inv128U, W, Y, ldw);
+    }
+    return lu_solve_transposed<T>(h, n, nrhs, LU, lda, d_ipiv, perm, B, ldb, bi.inv64L, bi.inv64U, bi.inv128L, bi.inv128U, W);
 }
 
 template <typename T>
@@ -1128,12 +1105,12 @@ static int getrs_t_host(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, c
     if (n == 0 || nrhs == 0) return LSX_OK;
     LSX_ARG(LU && ipiv && B);
     const int ld = ld_for(n), ldx = ld_for(nrhs);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(T) * (size_t)n * ldx) +
-                             pad256(sizeof(int32_t) * n) + 512));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldx);
-    int32_t *dp = c.take<int32_t>(n);
+    T *dA = nullptr, *dB = nullptr; int32_t *dp = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld);
+        dB = c.take<T>((size_t)n * ldx);
+        dp = c.take<int32_t>(n);
+    }));
     LSX_TRY(h2d<T>(h, n, n, LU, lda, dA, ld));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldx));
     LSX_HIP(hipMemcpyAsync(dp, ipiv, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
@@ -1147,8 +1124,8 @@ template <typename T>
 static int lange_dev(lsx_handle_t h, int norm, int m, int n, const T *dA, int lda, double *d_out) {
     LSX_ARG((norm == LSX_NORM_ONE || norm == LSX_NORM_INF) && m >= 0 && n >= 0 && lda >= n && d_out);
     LSX_ARG(m == 0 || n == 0 || dA);
-    LSX_TRY(ensure_scratch(h, lange_work_bytes(norm, m, n) + 256));
-    return launch_lange<T>(h, norm, m, n, dA, lda, (double *)h->scratch, d_out);
+    LSX_TRY(reserve(h, h->scratch, lange_work_bytes(norm, m, n) + 256));
+    return launch_lange<T>(h, norm, m, n, dA, lda, (double *)h->scratch.p, d_out);
 }
 
 // lacn2's iteration (dlacn2.f, the states JUMP = 1..5) for the 1-norm of an operator M that is only available as
@@ -1213,12 +1190,13 @@ static int gecon_dev(lsx_handle_t h, int norm, int n, const T *LU, int lda, cons
     }
     *rcond = 0.0;
     if (anorm == 0) return LSX_OK;
-    const size_t xb = pad256(sizeof(T) * (size_t)n), ib = pad256(sizeof(int32_t) * (size_t)n), sb = pad256((size_t)n);
-    LSX_TRY(grow(&h->ws7, &h->ws7_bytes, xb + ib + sb + 256));
-    T *x = (T *)h->ws7;
-    int32_t *ident = (int32_t *)((char *)h->ws7 + xb);            // no interchange: the solves work on L U alone
-    signed char *isgn = (signed char *)((char *)h->ws7 + xb + ib);
-    double *rec = (double *)((char *)h->ws7 + xb + ib + sb);     // 8 doubles; rec[5] = min |U_ii|
+    T *x = nullptr; int32_t *ident = nullptr; signed char *isgn = nullptr; double *rec = nullptr;
+    LSX_TRY(carve(h, h->cond, [&](Carver &c) {
+        x = c.take<T>(n);
+        ident = c.take<int32_t>(n);   // no interchange: the solves work on L U alone
+        isgn = c.take<signed char>(n);
+        rec = c.take<double>(8);      // rec[5] = min |U_ii|
+    }));
     double r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // kase 1: x <- inv(A) x, kase 2: x <- inv(A^T) x; the infinity-norm of A is the 1-norm of A^T
     auto solve = [&](const int kase) -> int {
@@ -1248,7 +1226,7 @@ template <> struct Lamch<float> { static constexpr double u = 0x1p-24, safmin = 
 //   resid(g, B, X, Rg, Wg, ldr, work)  residual and componentwise bound of g <= 8 columns in one pass over the matrix
 //   solve(transposed, v)               v <- inv(op A) v, or inv(op A)^T v, one vector
 // F (ldf) holds the factors: an exactly zero or NaN diagonal entry means there is no solution to refine.  work_bytes:
-// what resid wants behind the loop's own arrays in ws8.  *steps / *solves: the read-back counters of the caller.
+// what resid wants behind the loop's own arrays in the refine buffer.  *steps / *solves: the read-back counters of the caller.
 // Refine X until the componentwise backward error stops improving, then bound the forward error of every column with
 // lacn2 on inv(op A) diag(W).  A correction is a single right-hand-side solve of the column that asked for it, so a
 // column gets the same bits whatever rides along.  The host reads one record per step.  Synchronises the stream.
@@ -1258,17 +1236,17 @@ static int refine_loop(lsx_handle_t h, int n, int nrhs, const T *F, int ldf, con
                        Resid resid, Solve solve) {
     constexpr int G = 8, ITMAX = 5;
     const double u = Lamch<T>::u, safe1 = (n + 1.0) * Lamch<T>::safmin, safe2 = safe1 / u, nu = (n + 1.0) * u;
-    const size_t gb = pad256(sizeof(T) * (size_t)n * G), vb = pad256(sizeof(T) * (size_t)n), sb = pad256((size_t)n);
-    LSX_TRY(grow(&h->ws8, &h->ws8_bytes, 2 * gb + 2 * vb + sb + 512 + work_bytes));
-    char *w8 = (char *)h->ws8;
-    T *Rg = (T *)w8;                                    // residuals of the group, n x 8
-    T *Wg = (T *)(w8 + gb);                             // bounds of the group
-    T *v = (T *)(w8 + 2 * gb);                          // correction of one column / the estimator's vector
-    T *wt = (T *)(w8 + 2 * gb + vb);                    // the weights W of one column
-    signed char *isgn = (signed char *)(w8 + 2 * gb + 2 * vb);
-    double *rec = (double *)(w8 + 2 * gb + 2 * vb + sb);   // 16 doubles: berr[8], max|x|[8]
-    double *erec = rec + 16;                               // the estimator's record (8 doubles)
-    double *part = rec + 64;                               // the residual pass's partial sums
+    T *Rg = nullptr, *Wg = nullptr, *v = nullptr, *wt = nullptr; signed char *isgn = nullptr; double *rec = nullptr, *part = nullptr;
+    LSX_TRY(carve(h, h->refine, [&](Carver &c) {
+        Rg = c.take<T>((size_t)n * G);   // residuals of the group, n x 8
+        Wg = c.take<T>((size_t)n * G);   // bounds of the group
+        v = c.take<T>(n);                // correction of one column / the estimator's vector
+        wt = c.take<T>(n);               // the weights W of one column
+        isgn = c.take<signed char>(n);
+        rec = c.take<double>(64);        // [0, 16): berr[8], max|x|[8]; [16, 24): the estimator's record
+        part = c.take<double>((work_bytes + 7) / 8);   // the residual pass's partial sums
+    }));
+    double *erec = rec + 16;
     double r[16];
     LSX_TRY(launch_diag_minabs<T>(h, n, F, ldf, rec));     // writes its second slot: rec[1]
     LSX_HIP(hipMemcpyAsync(r, rec, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1371,14 +1349,12 @@ static int gerfs_host(lsx_handle_t h, int trans, int n, int nrhs, const T *A, in
     if (n == 0 || nrhs == 0) return gerfs_dev<T>(h, trans, n, nrhs, A, lda, LU, ldlu, ipiv, B, ldb, X, ldx, ferr, berr);
     LSX_ARG(A && LU && ipiv && B && X);
     const int ld = ld_for(n), ldr = ld_for(nrhs);
-    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) +
-                             pad256(sizeof(int32_t) * n) + 512));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dLU = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldr);
-    T *dX = c.take<T>((size_t)n * ldr);
-    int32_t *dp = c.take<int32_t>(n);
+    T *dA = nullptr, *dLU = nullptr, *dB = nullptr, *dX = nullptr; int32_t *dp = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld); dLU = c.take<T>((size_t)n * ld);
+        dB = c.take<T>((size_t)n * ldr); dX = c.take<T>((size_t)n * ldr);
+        dp = c.take<int32_t>(n);
+    }));
     LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
     LSX_TRY(h2d<T>(h, n, n, LU, ldlu, dLU, ld));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
@@ -1405,15 +1381,13 @@ static int gesvr_host(lsx_handle_t h, int trans, int n, int nrhs, const T *A, in
     if (n == 0) return LSX_OK;
     LSX_ARG(A && (nrhs == 0 || (B && X)));
     const int ld = ld_for(n), ldr = ld_for(nrhs > 0 ? nrhs : 1);
-    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) +
-                             pad256(sizeof(int32_t) * n) + 1024));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dLU = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldr);
-    T *dX = c.take<T>((size_t)n * ldr);
-    int32_t *dp = c.take<int32_t>(n);
-    int *dinfo = c.take<int>(1);
+    T *dA = nullptr, *dLU = nullptr, *dB = nullptr, *dX = nullptr; int32_t *dp = nullptr; int *dinfo = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld); dLU = c.take<T>((size_t)n * ld);
+        dB = c.take<T>((size_t)n * ldr); dX = c.take<T>((size_t)n * ldr);
+        dp = c.take<int32_t>(n);
+        dinfo = c.take<int>(1);
+    }));
     int hinfo = 0;
     LSX_TRY(factor_from_host<T>(h, n, A, lda, dLU, ld, dp, dinfo, &hinfo));
     if (info) *info = hinfo;
@@ -1440,10 +1414,8 @@ static int gecon_host(lsx_handle_t h, int norm, int n, const T *LU, int lda, con
     if (n == 0) { *rcond = 1.0; return LSX_OK; }
     LSX_ARG(LU && ipiv);
     const int ld = ld_for(n);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(int32_t) * n) + 512));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    int32_t *dp = c.take<int32_t>(n);
+    T *dA = nullptr; int32_t *dp = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dA = c.take<T>((size_t)n * ld); dp = c.take<int32_t>(n); }));
     LSX_TRY(h2d<T>(h, n, n, LU, lda, dA, ld));
     LSX_HIP(hipMemcpyAsync(dp, ipiv, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
     return gecon_dev<T>(h, norm, n, dA, ld, dp, anorm, rcond);
@@ -1457,12 +1429,13 @@ static int rcond_host(lsx_handle_t h, int norm, int n, const T *A, int lda, doub
     if (n == 0) return LSX_OK;
     LSX_ARG(A);
     const int ld = ld_for(n);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(int32_t) * n) + 1024));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    int32_t *dp = c.take<int32_t>(n);
-    int *dinfo = c.take<int>(1);
-    double *dnorm = c.take<double>(1);
+    T *dA = nullptr; int32_t *dp = nullptr; int *dinfo = nullptr; double *dnorm = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld);
+        dp = c.take<int32_t>(n);
+        dinfo = c.take<int>(1);
+        dnorm = c.take<double>(1);
+    }));
     LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
     LSX_TRY(lange_dev<T>(h, norm, n, n, dA, ld, dnorm));
     double anorm = 0;
@@ -1481,8 +1454,8 @@ template <typename T>
 static int lansy_dev(lsx_handle_t h, int n, const T *dA, int lda, double *d_out) {
     LSX_ARG(n >= 0 && lda >= n && d_out);
     LSX_ARG(n == 0 || dA);
-    LSX_TRY(ensure_scratch(h, resid_bound_sym_work_bytes(n, 1) + 256));
-    return launch_lansy<T>(h, n, dA, lda, (double *)h->scratch, d_out);
+    LSX_TRY(reserve(h, h->scratch, resid_bound_sym_work_bytes(n, 1) + 256));
+    return launch_lansy<T>(h, n, dA, lda, (double *)h->scratch.p, d_out);
 }
 
 // LAPACK's pocon: lacn2's iteration around x <- inv(U) inv(U^T) x.  The operator is symmetric, so both kase values
@@ -1500,11 +1473,12 @@ static int pocon_dev(lsx_handle_t h, int n, const T *U, int lda, double anorm, d
     }
     *rcond = 0.0;
     if (anorm == 0) return LSX_OK;
-    const size_t xb = pad256(sizeof(T) * (size_t)n), sb = pad256((size_t)n);
-    LSX_TRY(grow(&h->ws7, &h->ws7_bytes, xb + sb + 256));
-    T *x = (T *)h->ws7;
-    signed char *isgn = (signed char *)((char *)h->ws7 + xb);
-    double *rec = (double *)((char *)h->ws7 + xb + sb);          // 8 doubles; rec[5] = min |u_ii|
+    T *x = nullptr; signed char *isgn = nullptr; double *rec = nullptr;
+    LSX_TRY(carve(h, h->cond, [&](Carver &c) {
+        x = c.take<T>(n);
+        isgn = c.take<signed char>(n);
+        rec = c.take<double>(8);      // rec[5] = min |u_ii|
+    }));
     double r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     LSX_HIP(hipMemsetAsync(isgn, 0, (size_t)n, h->stream));
     LSX_TRY(launch_diag_minabs<T>(h, n, U, lda, rec + 4));       // writes its second slot: rec[5]
@@ -1553,9 +1527,8 @@ static int pocon_host(lsx_handle_t h, int n, const T *U, int lda, double anorm, 
     if (n == 0) { *rcond = 1.0; h->pocon_solves = 0; return LSX_OK; }
     LSX_ARG(U);
     const int ld = ld_for(n);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + 512));
-    Carver c(h->ws);
-    T *dU = c.take<T>((size_t)n * ld);
+    T *dU = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dU = c.take<T>((size_t)n * ld); }));
     LSX_TRY(upper_h2d<T>(h, n, U, lda, dU, ld));
     return pocon_dev<T>(h, n, dU, ld, anorm, rcond);
 }
@@ -1570,11 +1543,8 @@ static int porcond_host(lsx_handle_t h, int n, const T *A, int lda, double *rcon
     if (n == 0) return LSX_OK;
     LSX_ARG(A);
     const int ld = ld_for(n);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + 1024));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    int *dinfo = c.take<int>(1);
-    double *dnorm = c.take<double>(1);
+    T *dA = nullptr; int *dinfo = nullptr; double *dnorm = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dA = c.take<T>((size_t)n * ld); dinfo = c.take<int>(1); dnorm = c.take<double>(1); }));
     LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
     LSX_TRY(lansy_dev<T>(h, n, dA, ld, dnorm));
     double anorm = 0;
@@ -1597,12 +1567,11 @@ static int porfs_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, cons
     if (n == 0 || nrhs == 0) return porfs_dev<T>(h, n, nrhs, A, lda, U, ldu, B, ldb, X, ldx, ferr, berr);
     LSX_ARG(A && U && B && X);
     const int ld = ld_for(n), ldr = ld_for(nrhs);
-    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) + 512));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dU = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldr);
-    T *dX = c.take<T>((size_t)n * ldr);
+    T *dA = nullptr, *dU = nullptr, *dB = nullptr, *dX = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld); dU = c.take<T>((size_t)n * ld);
+        dB = c.take<T>((size_t)n * ldr); dX = c.take<T>((size_t)n * ldr);
+    }));
     LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
     LSX_TRY(upper_h2d<T>(h, n, U, ldu, dU, ld));
     LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
@@ -1628,13 +1597,12 @@ static int posvr_host(lsx_handle_t h, int n, int nrhs, const T *A, int lda, cons
     if (n == 0) return LSX_OK;
     LSX_ARG(A && (nrhs == 0 || (B && X)));
     const int ld = ld_for(n), ldr = ld_for(nrhs > 0 ? nrhs : 1);
-    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) + 1024));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dU = c.take<T>((size_t)n * ld);
-    T *dB = c.take<T>((size_t)n * ldr);
-    T *dX = c.take<T>((size_t)n * ldr);
-    int *dinfo = c.take<int>(1);
+    T *dA = nullptr, *dU = nullptr, *dB = nullptr, *dX = nullptr; int *dinfo = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld); dU = c.take<T>((size_t)n * ld);
+        dB = c.take<T>((size_t)n * ldr); dX = c.take<T>((size_t)n * ldr);
+        dinfo = c.take<int>(1);
+    }));
     int hinfo = 0;
     LSX_TRY(upper_h2d<T>(h, n, A, lda, dU, ld));
     LSX_TRY(potrf_dev<T>(h, n, dU, ld, dinfo));
@@ -1668,10 +1636,9 @@ static int d2d(lsx_handle_t h, int m, int n, const T *src, int lds, T *dst, int 
     return LSX_OK;
 }
 
-// ws9: 256 bytes of records in front (the drivers'), then the work area of one reduction
-static int ensure_equil_ws(lsx_handle_t h, size_t work) {
-    if (256 + work > h->ws9_bytes) LSX_HIP(hipStreamSynchronize(h->stream));   // growing frees the old block
-    return grow(&h->ws9, &h->ws9_bytes, 256 + work);
+// the equil buffer: 32 doubles of records in front (the drivers'), then the work area of one reduction
+static int carve_equil(lsx_handle_t h, size_t work_bytes, double **rec, double **work) {
+    return carve(h, h->equil, [&](Carver &c) { *rec = c.take<double>(32); *work = c.take<double>((work_bytes + 7) / 8); });
 }
 
 // LAPACK's geequ on device data; asynchronous
@@ -1679,8 +1646,9 @@ template <typename T>
 static int geequ_dev(lsx_handle_t h, int m, int n, const T *dA, int lda, T *d_r, T *d_c, double *d_stats, int passes = 3) {
     LSX_ARG(m >= 0 && n >= 0 && lda >= n && d_stats && passes >= 1 && passes <= 3);
     LSX_ARG(m == 0 || n == 0 || (dA && d_r && d_c));
-    LSX_TRY(ensure_equil_ws(h, geequ_work_bytes(m, n, sizeof(T))));
-    return launch_geequ<T>(h, m, n, dA, lda, d_r, d_c, d_stats, (char *)h->ws9 + 256, passes);
+    double *rec = nullptr, *work = nullptr;
+    LSX_TRY(carve_equil(h, geequ_work_bytes(m, n, sizeof(T)), &rec, &work));
+    return launch_geequ<T>(h, m, n, dA, lda, d_r, d_c, d_stats, work, passes);
 }
 
 // dlaqge's decision from the three scalars of geequ (values of the working precision held in doubles)
@@ -1738,9 +1706,9 @@ static int gesvx_dev(lsx_handle_t h, int equil, int trans, int n, int nrhs, T *d
     if (n == 0) return LSX_OK;
     LSX_ARG(dA && dLU && d_ipiv && (nrhs == 0 || (dB && dX)) && (equil == 0 || (d_r && d_c)));
     const int norm = trans ? LSX_NORM_INF : LSX_NORM_ONE;
-    LSX_TRY(ensure_equil_ws(h, std::max(geequ_work_bytes(n, n, sizeof(T)), maxabs_work_bytes(n))));
     // records: [0..4) geequ's stats, [4] anorm, [5] max |A|, [6] max |U|, then the factorisation's info word
-    double *rec = (double *)h->ws9, *work = (double *)((char *)h->ws9 + 256);
+    double *rec = nullptr, *work = nullptr;
+    LSX_TRY(carve_equil(h, std::max(geequ_work_bytes(n, n, sizeof(T)), maxabs_work_bytes(n)), &rec, &work));
     int *dinfo = (int *)(rec + 8);
     double hrec[8] = {1, 1, 0, 0, 0, 0, 0, 0};
     double rowcnd = 1.0, colcnd = 1.0;
@@ -1840,16 +1808,13 @@ static int gesvx_host(lsx_handle_t h, int equil, int trans, int n, int nrhs, con
                             nullptr, nullptr, equed, nullptr, nullptr, rcond, ferr, berr, rpvgrw, info);
     LSX_ARG(A && (nrhs == 0 || (B && X)) && (equil == 0 || (r && c)));
     const int ld = ld_for(n), ldr = ld_for(nrhs > 0 ? nrhs : 1);
-    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + 2 * pad256(sizeof(T) * (size_t)n * ldr) +
-                             pad256(sizeof(int32_t) * n) + 2 * pad256(sizeof(T) * (size_t)n) + 1024));
-    Carver cv(h->ws);
-    T *dA = cv.take<T>((size_t)n * ld);
-    T *dLU = cv.take<T>((size_t)n * ld);
-    T *dB = cv.take<T>((size_t)n * ldr);
-    T *dX = cv.take<T>((size_t)n * ldr);
-    int32_t *dp = cv.take<int32_t>(n);
-    T *dr = cv.take<T>(n);
-    T *dc = cv.take<T>(n);
+    T *dA = nullptr, *dLU = nullptr, *dB = nullptr, *dX = nullptr, *dr = nullptr, *dc = nullptr; int32_t *dp = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &cv) {
+        dA = cv.take<T>((size_t)n * ld); dLU = cv.take<T>((size_t)n * ld);
+        dB = cv.take<T>((size_t)n * ldr); dX = cv.take<T>((size_t)n * ldr);
+        dp = cv.take<int32_t>(n);
+        dr = cv.take<T>(n); dc = cv.take<T>(n);
+    }));
     LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
     if (nrhs > 0) LSX_TRY(h2d<T>(h, n, nrhs, B, ldb, dB, ldr));
     GesvxDone done;
@@ -1924,19 +1889,16 @@ int lsx_create(lsx_handle_t *out, int device) {
             return LSX_ERR_HIP;
         }
     }
-    int r = grow(&h->scratch, &h->scratch_bytes, 1 << 20);
+    int r = reserve(h, h->scratch, 1 << 20);
+    DevBuf status, moves;   // fixed size: the handle keeps plain pointers
+    if (r == LSX_OK) r = reserve(h, status, 256);
+    h->dev_status = (int *)status.p;
+    if (r == LSX_OK && hipMemset(status.p, 0, 256) != hipSuccess) r = LSX_ERR_HIP;
+    if (r == LSX_OK) r = reserve(h, moves, 8192);
     if (r == LSX_OK) {
-        size_t ds = 0;
-        void *p = nullptr;
-        r = grow(&p, &ds, 256);
-        h->dev_status = (int *)p;
-        if (r == LSX_OK && hipMemset(p, 0, 256) != hipSuccess) r = LSX_ERR_HIP;
-    }
-    if (r == LSX_OK) {
-        size_t mv = 0;
-        r = grow(&h->moves_buf[0], &mv, 8192);
-        h->moves_api = (char *)h->moves_buf[0] + 2048;
-        h->moves_buf[1] = (char *)h->moves_buf[0] + 4096;
+        h->moves_buf[0] = moves.p;
+        h->moves_api = (char *)moves.p + 2048;
+        h->moves_buf[1] = (char *)moves.p + 4096;
     }
     if (r != LSX_OK) { (void)hipStreamDestroy(h->own_stream); delete h; return r; }
     *out = h;
@@ -1949,19 +1911,10 @@ int lsx_destroy(lsx_handle_t h) {
     (void)hipStreamSynchronize(h->stream);
     for (auto &ev : h->prof.pending) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &e : h->prof.pool) (void)hipEventDestroy(e);
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->ws2) (void)hipFree(h->ws2);
-    if (h->ws3) (void)hipFree(h->ws3);
-    if (h->ws4) (void)hipFree(h->ws4);
-    if (h->ws6) (void)hipFree(h->ws6);
-    if (h->ws7) (void)hipFree(h->ws7);
-    if (h->ws8) (void)hipFree(h->ws8);
-    if (h->ws9) (void)hipFree(h->ws9);
-    if (h->xchg) (void)hipFree(h->xchg);
-    if (h->ws5) (void)hipFree(h->ws5);
-    if (h->scratch) (void)hipFree(h->scratch);
+    for (DevBuf *b : {&h->staging, &h->tinv, &h->rhs_work, &h->mixed_resid, &h->getri_work, &h->rref_first, &h->cond,
+                      &h->refine, &h->equil, &h->xchg, &h->moves_all, &h->scratch})
+        if (b->p) (void)hipFree(b->p);
     if (h->moves_buf[0]) (void)hipFree(h->moves_buf[0]);
-    if (h->moves_all) (void)hipFree(h->moves_all);
     if (h->dev_status) (void)hipFree(h->dev_status);
     if (h->ev_panel) (void)hipEventDestroy(h->ev_panel);
     if (h->ev_next) (void)hipEventDestroy(h->ev_next);
@@ -2176,13 +2129,13 @@ static int getri_host(lsx_handle_t h, int n, const T *A, int lda, T *Ainv, int l
     if (n == 0) return LSX_OK;
     LSX_ARG(A && Ainv);
     const int ld = ld_for(n);
-    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(int32_t) * n) + 1024));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    T *dI = c.take<T>((size_t)n * ld);
-    int32_t *dp = c.take<int32_t>(n);
-    int *dinfo = c.take<int>(1);
-    double *dprobe = c.take<double>(2);
+    T *dA = nullptr, *dI = nullptr; int32_t *dp = nullptr; int *dinfo = nullptr; double *dprobe = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld); dI = c.take<T>((size_t)n * ld);
+        dp = c.take<int32_t>(n);
+        dinfo = c.take<int>(1);
+        dprobe = c.take<double>(2);
+    }));
     LSX_TRY(h2d<T>(h, n, n, A, lda, dA, ld));
     LSX_TRY(launch_amax<T>(h, n, n, dA, ld, dprobe));
     int hinfo = 0;
@@ -2206,12 +2159,13 @@ static int det_host(lsx_handle_t h, int n, const T *A, int lda, double *sign, do
     if (n == 0) { *sign = 1; *mant = 0.5; *exp2 = 1; return LSX_OK; }  // det([]) = 1 (linalg.py:197-199)
     LSX_ARG(A);
     const int ld = ld_for(n);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)n * ld) + pad256(sizeof(int32_t) * n) + 1024));
-    Carver c(h->ws);
-    T *dA = c.take<T>((size_t)n * ld);
-    int32_t *dp = c.take<int32_t>(n);
-    int *dinfo = c.take<int>(1);
-    double *dout = c.take<double>(3);
+    T *dA = nullptr; int32_t *dp = nullptr; int *dinfo = nullptr; double *dout = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld);
+        dp = c.take<int32_t>(n);
+        dinfo = c.take<int>(1);
+        dout = c.take<double>(3);
+    }));
     int hinfo = 0;   // a determinant of garbage factors must not be returned as a value: the status is read first
     LSX_TRY(factor_from_host<T>(h, n, A, lda, dA, ld, dp, dinfo, &hinfo));
     LSX_TRY(launch_det<T>(h, n, dA, ld, dp, dout));
@@ -2251,15 +2205,14 @@ static int rref_first_fast(lsx_handle_t h, int m, int n, int bar, double *R, int
     const int nb = h->nb;
     const int rmax = m < bar ? m : bar;
     const int ldw = ld_for(n), ldg = ld_for(rmax);
-    const size_t wbytes = pad256(sizeof(T) * (size_t)m * ldw), gbytes = pad256(sizeof(T) * (size_t)m * ldg);
-    LSX_TRY(grow(&h->ws6, &h->ws6_bytes, wbytes + gbytes + 2 * pad256(sizeof(int32_t) * (size_t)m) + 1024));
-    Carver c(h->ws6);
-    T *W = c.take<T>((size_t)m * ldw);
-    T *Gm = c.take<T>((size_t)m * ldg);
-    int32_t *ipiv = c.take<int32_t>(m);
-    int32_t *ipiv2 = c.take<int32_t>(m);
-    int *ginfo = c.take<int>(2);
-    double *amax = c.take<double>(1);
+    T *W = nullptr, *Gm = nullptr; int32_t *ipiv = nullptr, *ipiv2 = nullptr; int *ginfo = nullptr; double *amax = nullptr;
+    LSX_TRY(carve(h, h->rref_first, [&](Carver &c) {
+        W = c.take<T>((size_t)m * ldw);
+        Gm = c.take<T>((size_t)m * ldg);
+        ipiv = c.take<int32_t>(m); ipiv2 = c.take<int32_t>(m);
+        ginfo = c.take<int>(2);
+        amax = c.take<double>(1);
+    }));
     // 1. rank and pivot columns
     LSX_TRY(launch_copy2d<T>(h, m, n, R, ldr, W, ldw));
     const int rb = rref_blocked<T>(h, m, n, bar, W, ldw, d_pivots, d_rank, tol, LSX_PIVOT_MAX);
@@ -2284,7 +2237,7 @@ static int rref_first_fast(lsx_handle_t h, int m, int n, int bar, double *R, int
     // 2. P G = L U under the first-non-zero rule
     LSX_TRY(launch_gather_pivot_cols<T>(h, m, r, 0, R, ldr, d_pivots, Gm, ldg));
     LSX_TRY(ensure_getrf_workspace(h, m, sizeof(T)));
-    T *Tinv = (T *)h->ws2;
+    T *Tinv = (T *)h->tinv.p;   // done with before getrf_dev / getrs_dev below carve tinv for themselves
     LSX_HIP(hipMemsetAsync(ginfo, 0, sizeof(int), h->stream));
     GemmPlan mfma;   // as in the LU drivers (the solve and the update of step 3 are no LU updates: plain)
     mfma.mfma_only = true;
@@ -2349,12 +2302,13 @@ static int rref_host(lsx_handle_t h, int m, int n, int bar_col, const T *A, int 
     LSX_ARG(bar <= n);
     const int ld = ld_for(n);
     const int np = m < n ? m : n;
-    LSX_TRY(ensure_ws(h, pad256(sizeof(T) * (size_t)m * ld) + pad256(sizeof(int32_t) * 2 * np) + 512));
-    LSX_TRY(ensure_scratch(h, 256 + 2 * sizeof(double) * (size_t)n + 4096 + 2 * (size_t)m));   // + the blocked form's row-group candidates
-    Carver c(h->ws);
-    T *dR = c.take<T>((size_t)m * ld);
-    int32_t *dp = c.take<int32_t>(2 * (size_t)np);
-    int *drank = c.take<int>(1);
+    T *dR = nullptr; int32_t *dp = nullptr; int *drank = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dR = c.take<T>((size_t)m * ld);
+        dp = c.take<int32_t>(2 * (size_t)np);
+        drank = c.take<int>(1);
+    }));
+    LSX_TRY(reserve(h, h->scratch, rref_scratch_bytes(m, n)));
     LSX_TRY(h2d<T>(h, m, n, A, lda, dR, ld));
     LSX_TRY(rref_any<T>(h, m, n, bar, dR, ld, dp, drank, tol, pivot_rule));
     LSX_TRY(d2h<T>(h, m, n, dR, ld, R, ldr));
@@ -2376,10 +2330,10 @@ static int gesv_refined_dev(lsx_handle_t h, int n, int nrhs, const float *dA, in
     LSX_ARG(n >= 1 && nrhs >= 1 && dA && dLU && d_ipiv && d_info && dB && dX64 && sweeps >= 0 && sweeps <= 16);
     LSX_TRY(launch_copy2d<float>(h, n, n, dA, lda, dLU, ldl));
     LSX_TRY(getrf_dev<float>(h, n, dLU, ldl, d_ipiv, d_info));
-    // correction / right-hand-side buffer: n x nrhs fp32 (ws3 belongs to getrs)
+    // correction / right-hand-side buffer: n x nrhs fp32 (rhs_work belongs to getrs)
     const int ldr = nrhs;
-    LSX_TRY(grow(&h->ws4, &h->ws4_bytes, sizeof(float) * (size_t)n * ldr));
-    float *dR = (float *)h->ws4;
+    float *dR = nullptr;
+    LSX_TRY(carve(h, h->mixed_resid, [&](Carver &c) { dR = c.take<float>((size_t)n * ldr); }));
     int rc = launch_copy2d<float>(h, n, nrhs, dB, ldb, dR, ldr);
     if (rc == LSX_OK) rc = getrs_dev<float>(h, n, nrhs, dLU, ldl, d_ipiv, dR, ldr);
     if (rc == LSX_OK) rc = launch_refine_apply(h, n, nrhs, 1, dR, ldr, dX64, ldx, dX32, ldf, d_stats ? d_stats + 2 : nullptr);
@@ -2426,17 +2380,16 @@ int lsx_gesv_f32_refined(lsx_handle_t h, int n, int nrhs, const float *A, int ld
     if (n == 0 || nrhs == 0) return LSX_OK;
     LSX_ARG(A && B && (X || X64) && (!X || ldx >= nrhs) && (!X64 || ldx64 >= nrhs));
     const int ld = ld_for(n), lr = ld_for(nrhs);
-    LSX_TRY(ensure_ws(h, 2 * pad256(sizeof(float) * (size_t)n * ld) + pad256(sizeof(float) * (size_t)n * lr) * 2 +
-                             pad256(sizeof(double) * (size_t)n * lr) + pad256(sizeof(int32_t) * n) + 1024));
-    Carver c(h->ws);
-    float *dA = c.take<float>((size_t)n * ld);
-    float *dLU = c.take<float>((size_t)n * ld);
-    float *dB = c.take<float>((size_t)n * lr);
-    float *dXf = c.take<float>((size_t)n * lr);
-    double *dX = c.take<double>((size_t)n * lr);
-    int32_t *dp = c.take<int32_t>(n);
-    int *dinfo = c.take<int>(1);
-    double *dstats = c.take<double>(6);
+    float *dA = nullptr, *dLU = nullptr, *dB = nullptr, *dXf = nullptr; double *dX = nullptr, *dstats = nullptr;
+    int32_t *dp = nullptr; int *dinfo = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<float>((size_t)n * ld); dLU = c.take<float>((size_t)n * ld);
+        dB = c.take<float>((size_t)n * lr); dXf = c.take<float>((size_t)n * lr);
+        dX = c.take<double>((size_t)n * lr);
+        dp = c.take<int32_t>(n);
+        dinfo = c.take<int>(1);
+        dstats = c.take<double>(6);
+    }));
     LSX_TRY(h2d<float>(h, n, n, A, lda, dA, ld));
     LSX_TRY(h2d<float>(h, n, nrhs, B, ldb, dB, lr));
     LSX_TRY(launch_amax<float>(h, n, n, dA, ld, dstats + 4));
@@ -2476,12 +2429,12 @@ int lsx_matmul_f64(lsx_handle_t h, int m, int n, int k, const double *A, int lda
     if (m == 0 || n == 0) return LSX_OK;
     LSX_ARG(C && (k == 0 || (A && B)));
     const int la = ld_for(k > 0 ? k : 1), lb = ld_for(n), lc = ld_for(n);
-    LSX_TRY(ensure_ws(h, pad256(sizeof(double) * (size_t)m * la) + pad256(sizeof(double) * (size_t)(k > 0 ? k : 1) * lb) +
-                             pad256(sizeof(double) * (size_t)m * lc) + 512));
-    Carver c(h->ws);
-    double *dA = c.take<double>((size_t)m * la);
-    double *dB = c.take<double>((size_t)(k > 0 ? k : 1) * lb);
-    double *dC = c.take<double>((size_t)m * lc);
+    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<double>((size_t)m * la);
+        dB = c.take<double>((size_t)(k > 0 ? k : 1) * lb);
+        dC = c.take<double>((size_t)m * lc);
+    }));
     LSX_HIP(hipMemsetAsync(dC, 0, sizeof(double) * (size_t)m * lc, h->stream));
     if (k > 0) {
         LSX_TRY(h2d<double>(h, m, k, A, lda, dA, la));
@@ -2582,8 +2535,8 @@ int lsx_gecon_f32_dev(lsx_handle_t h, int norm, int n, const float *dLU, int lda
                 ldx >= nrhs && ldr >= nrhs);                                                                               \
         if (n == 0 || nrhs == 0) return LSX_OK;                                                                            \
         LSX_ARG(dA && dB && dX && dR && dW);                                                                               \
-        LSX_TRY(ensure_scratch(h, resid_bound_work_bytes(trans, n) + 256));                                                \
-        return launch_resid_bound<T>(h, trans, n, nrhs, dA, lda, dB, ldb, dX, ldx, dR, dW, ldr, (double *)h->scratch);     \
+        LSX_TRY(reserve(h, h->scratch, resid_bound_work_bytes(trans, n) + 256));                                           \
+        return launch_resid_bound<T>(h, trans, n, nrhs, dA, lda, dB, ldb, dX, ldx, dR, dW, ldr, (double *)h->scratch.p);   \
     }
 LSX_GERFS_ABI(f64, double)
 LSX_GERFS_ABI(f32, float)
@@ -2702,18 +2655,18 @@ int lsx_rref_trace_f64(lsx_handle_t h, int m, int n, int bar_col, const double *
     const int ld = ld_for(n);
     const int np = m < n ? m : n;
     const size_t snap_elems = (size_t)max_snaps * m * n;
-    LSX_TRY(ensure_ws(h, pad256(sizeof(double) * (size_t)m * ld) + pad256(sizeof(int32_t) * 2 * np) +
-                             pad256(sizeof(int32_t) * 4 * (size_t)max_steps) + pad256(sizeof(double) * snap_elems) +
-                             pad256(snap_elems) + pad256((size_t)m * n) + 1024));
-    LSX_TRY(ensure_scratch(h, 4096));
-    Carver c(h->ws);
-    double *dR = c.take<double>((size_t)m * ld);
-    int32_t *dp = c.take<int32_t>(2 * (size_t)np);
-    int32_t *ds = c.take<int32_t>(4 * (size_t)max_steps);
-    double *dsn = snap_elems ? c.take<double>(snap_elems) : nullptr;
-    unsigned char *dst = snap_elems ? c.take<unsigned char>(snap_elems) : nullptr;
-    unsigned char *dT = c.take<unsigned char>((size_t)m * n);
-    int *dout = c.take<int>(4);
+    double *dR = nullptr, *dsn = nullptr; int32_t *dp = nullptr, *ds = nullptr; unsigned char *dst = nullptr, *dT = nullptr;
+    int *dout = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dR = c.take<double>((size_t)m * ld);
+        dp = c.take<int32_t>(2 * (size_t)np);
+        ds = c.take<int32_t>(4 * (size_t)max_steps);
+        dsn = snap_elems ? c.take<double>(snap_elems) : nullptr;
+        dst = snap_elems ? c.take<unsigned char>(snap_elems) : nullptr;
+        dT = c.take<unsigned char>((size_t)m * n);
+        dout = c.take<int>(4);
+    }));
+    LSX_TRY(reserve(h, h->scratch, rref_trace_scratch_bytes()));
     LSX_TRY(h2d<double>(h, m, n, A, lda, dR, ld));
     if (int_mask) LSX_HIP(hipMemcpyAsync(dT, int_mask, (size_t)m * n, hipMemcpyHostToDevice, h->stream));
     else LSX_HIP(hipMemsetAsync(dT, 0, (size_t)m * n, h->stream));
@@ -2740,7 +2693,7 @@ int lsx_rref_f64_dev(lsx_handle_t h, int m, int n, int bar_col, double *dR, int 
     LSX_ARG(pivot_rule == LSX_PIVOT_FIRST || pivot_rule == LSX_PIVOT_MAX);
     const int bar = bar_col > 0 ? bar_col : n - 1;
     LSX_ARG(bar <= n);
-    LSX_TRY(ensure_scratch(h, 256 + 2 * sizeof(double) * (size_t)n + 4096 + 2 * (size_t)m));   // + the blocked form's row-group candidates
+    LSX_TRY(reserve(h, h->scratch, rref_scratch_bytes(m, n)));
     return rref_any<double>(h, m, n, bar, dR, ldr, d_pivots, d_rank, tol, pivot_rule);
 }
 
@@ -2748,7 +2701,7 @@ int lsx_panel_f64_dev(lsx_handle_t h, int m, int jb, double *dP, int ldp, int ro
                       int *d_info) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && m >= 1 && jb >= 1 && jb <= 256 && dP && d_ipiv && ldp >= jb);
-    LSX_TRY(ensure_scratch(h, std::max(pad256(16 * ((size_t)m / 32 + 2)) + ((size_t)m / 32 + 2) * 5248 + 8192, panel_x_area_bytes(h, h->panel_mode, m, 8) + 4096)));
+    LSX_TRY(reserve(h, h->scratch, std::max(panel_scratch_bytes(m), panel_x_area_bytes(h, h->panel_mode, m, 8) + 4096)));
     PanelArgs pa(h, h->moves_api);
     const int r = launch_panel<double>(h, m, jb, dP, ldp, row0, d_ipiv, d_info, pa);
     h->moves_api_valid = pa.listed;
@@ -2777,18 +2730,18 @@ int lsx_trsm_lu_f64_dev(lsx_handle_t h, int jb, int ncols, const double *dL, int
                         int ldb) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && dL && dB && jb >= 1 && jb <= 256);
-    const size_t tinv = (size_t)((jb + 63) / 64) * 4096 * sizeof(double);
-    LSX_TRY(grow(&h->ws2, &h->ws2_bytes, pad256(tinv)));
-    LSX_TRY(launch_trtri<double>(h, 1, jb, dL, ldl, (double *)h->ws2));
-    return launch_trsm_block<double>(h, 1, jb, ncols, dL, ldl, (const double *)h->ws2, dB, ldb);
+    double *Tinv = nullptr;
+    LSX_TRY(carve(h, h->tinv, [&](Carver &c) { Tinv = c.take<double>(inv64_elems(jb)); }));
+    LSX_TRY(launch_trtri<double>(h, 1, jb, dL, ldl, Tinv));
+    return launch_trsm_block<double>(h, 1, jb, ncols, dL, ldl, Tinv, dB, ldb);
 }
 int lsx_gemm_sub_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dA, int lda,
                          const double *dB, int ldb, double *dC, int ldc) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && dA && dB && dC && lda >= k && ldb >= n && ldc >= n);
     if (h->gemm_queue_test) {   // measurements: the work-queue form alone (1: all XCDs, 2: XCD 0 left out as beside a panel)
-        LSX_TRY(ensure_scratch(h, 4096));
-        int *w = (int *)h->scratch;
+        LSX_TRY(reserve(h, h->scratch, 4096));
+        int *w = (int *)h->scratch.p;
         LSX_HIP(hipMemsetAsync(w, 0, 1024, h->stream));
         if (h->gemm_queue_test >= 2) LSX_HIP(hipMemsetD32Async((hipDeviceptr_t)w, 1, 1, h->stream));
         GemmPlan plan;
@@ -2895,8 +2848,8 @@ int lsx_gemm_tn_sub_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dA
         LSX_ARG(h && n >= 0 && nrhs >= 0 && nrhs <= 8 && lda >= n && ldb >= nrhs && ldx >= nrhs && ldr >= nrhs);          \
         if (n == 0 || nrhs == 0) return LSX_OK;                                                                           \
         LSX_ARG(dA && dB && dX && dR && dW);                                                                              \
-        LSX_TRY(ensure_scratch(h, resid_bound_sym_work_bytes(n, nrhs) + 256));                                            \
-        return launch_resid_bound_sym<T>(h, n, nrhs, dA, lda, dB, ldb, dX, ldx, dR, dW, ldr, (double *)h->scratch);       \
+        LSX_TRY(reserve(h, h->scratch, resid_bound_sym_work_bytes(n, nrhs) + 256));                                       \
+        return launch_resid_bound_sym<T>(h, n, nrhs, dA, lda, dB, ldb, dX, ldx, dR, dW, ldr, (double *)h->scratch.p);     \
     }
 LSX_POSX_ENTRIES(f64, double)
 LSX_POSX_ENTRIES(f32, float)
@@ -2920,9 +2873,9 @@ int lsx_fill_f32_dev(lsx_handle_t h, int kind, uint64_t seed, int m, int n, floa
 
 int lsx_diag_read_scratch(lsx_handle_t h, size_t offset, void *dst, size_t bytes) {
     LSX_DEVICE_GUARD(h);
-    LSX_ARG(h && dst && offset + bytes <= h->scratch_bytes);
+    LSX_ARG(h && dst && offset + bytes <= h->scratch.bytes);
     LSX_HIP(hipStreamSynchronize(h->stream));
-    LSX_HIP(hipMemcpy(dst, (char *)h->scratch + offset, bytes, hipMemcpyDeviceToHost));
+    LSX_HIP(hipMemcpy(dst, (char *)h->scratch.p + offset, bytes, hipMemcpyDeviceToHost));
     return LSX_OK;
 }
 

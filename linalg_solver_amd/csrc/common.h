@@ -76,13 +76,19 @@ struct Prof {
 
 }  // namespace lsx
 
+// One device allocation owned by the handle: grown on demand by lsx::reserve (api.hip), never shrunk, freed by lsx_destroy.
+struct DevBuf { void *p = nullptr; size_t bytes = 0; };
+
 struct lsx_handle_s {
+    // ---- resources
     int device = 0;
+    int num_cu = 256;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;  // stream in use (own or borrowed)
     hipStream_t side_stream = nullptr;  // high-priority stream for the look-ahead panel
     hipEvent_t ev_panel = nullptr, ev_next = nullptr, ev_start = nullptr, ev_done = nullptr;
-    // tunables
+    lsx::Prof prof;
+    // ---- options (lsx_set_option)
     int nb = 128;        // panel width (<= 128)
     int kblock = 1;      // panels per trailing update: update depth K = kblock * nb
     int panel_mode = 4;  // 0 = per-column launches, 3 = pipelined (device-scope exchange), 4 = XCD-scope exchange on one XCD (taller panels than an XCD holds: 3)
@@ -98,64 +104,70 @@ struct lsx_handle_s {
     int chain_fused = 1;             // 1: chain head and the next panel's block solve in one launch (option chain_fused)
     int chain_wait_limit = 1 << 21;  // polls of those waits before they give up (option chain_wait_limit: tests inject a time-out with 0)
     int x_events = 0;                // option x_events (measurements, tests): no column-0 ordering in the XCD-scope schedule
-    void *moves_all = nullptr;       // look-ahead driver with the XCD-scope panel: one gather list per panel
-    size_t moves_all_bytes = 0;
     int panel_debug = 0;  // 1: stamped diagnostic panel kernel (tools/kbench.py)
-    int num_cu = 256;
-    // persistent device workspace (grown on demand, never shrunk)
-    void *ws = nullptr;      // staging of caller matrices (host-buffer entry points)
-    size_t ws_bytes = 0;
-    void *ws2 = nullptr;     // triangular block inverses
-    size_t ws2_bytes = 0;
-    void *ws3 = nullptr;     // permutation vector + right-hand-side copy
-    size_t ws3_bytes = 0;
-    void *ws5 = nullptr;     // work matrix of the structured inverse (getri)
-    size_t ws5_bytes = 0;
     int getri_plain = 0;     // option getri_structured=0: the inverse as a plain n-right-hand-side solve of P*I
-    void *xchg = nullptr;    // few-RHS solve (kernels_trsv.hip, third form): exchange granules validated by an epoch, never cleared
-    size_t xchg_bytes = 0;
-    unsigned xchg_epoch = 0;
-    void *ws6 = nullptr;     // first-rule row reduction: a copy of the matrix, its pivot columns, interchanges
-    size_t ws6_bytes = 0;
     int rref_first_fast = 1; // 1: large fp64 inputs under LSX_PIVOT_FIRST take the blocked form (option rref_first_fast)
-    int rref_first_used = 0; // read-only option: 1 if the last LSX_PIVOT_FIRST reduction took the blocked form
-    void *ws4 = nullptr;     // residual / correction of the mixed-precision solve
-    size_t ws4_bytes = 0;
-    void *ws7 = nullptr;     // condition estimate: the iteration vector, its sign vector, the record, an identity interchange list
-    size_t ws7_bytes = 0;
-    int gecon_solves = 0;    // read-only option: single-right-hand-side solves of the last condition estimate
-    void *ws8 = nullptr;     // refined solve (gerfs): residual and bound of a group, correction / estimator vectors, records, partial sums
-    size_t ws8_bytes = 0;
-    int gerfs_steps = 0;     // read-only option: most refinement steps any column of the last gerfs took
-    int gerfs_solves = 0;    // read-only option: single-right-hand-side estimator solves of the last gerfs
-    void *ws9 = nullptr;     // equilibration (geequ, gesvx): row maxima, partial column maxima, the drivers' records
-    size_t ws9_bytes = 0;
-    int getrs_t_blocked_min = 64;   // transposed solve: smallest nrhs that takes the blocked (MFMA) sweeps when n > 128; 0 = never
-    int getrs_t_path = 0;    // read-only option: 1 if the last lsx_getrs_t_* call took the blocked sweeps
-    int potrs_few_max = 0;   // Cholesky solve: largest nrhs (<= 8) that takes the few-column step kernels; 0 = never
-    int potrs_path = 0;      // read-only option: 1 if the last lsx_potrs_* call took the few-column step kernels
-    int pocon_solves = 0;    // read-only option: single-right-hand-side solves of the last lsx_pocon_* / lsx_porcond_*
-    int porfs_steps = 0;     // read-only option: most refinement steps any column of the last porfs took
-    int porfs_solves = 0;    // read-only option: single-right-hand-side estimator solves of the last porfs
-    // gather lists (int2[256] each) emitted by the cooperative panel kernels: storage only, a launch is told which one
-    void *moves_buf[2] = {nullptr, nullptr};  // the drivers' lists (the shared-CU look-ahead driver alternates)
-    void *moves_api = nullptr;       // list of the last lsx_panel_f64_dev call, handed out by lsx_panel_moves_dev
-    bool moves_api_valid = false;    // that call emitted one (touched by those two entry points only)
-    // small fixed device scratch: pivot search partials, flags, info words
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
-    // device status words (never cleared by kernels): [0] panel exchange time-outs when the caller gave no info
-    // word, [1] few-RHS solve time-outs, [2] the internal info word of a factorisation called without one
-    int *dev_status = nullptr;
     int rref_blocked = 1;       // 1: large inputs with LSX_PIVOT_MAX take the blocked row reduction (option rref_blocked)
+    int getrs_t_blocked_min = 64;   // transposed solve: smallest nrhs that takes the blocked (MFMA) sweeps when n > 128; 0 = never
+    int potrs_few_max = 0;   // Cholesky solve: largest nrhs (<= 8) that takes the few-column step kernels; 0 = never
     int gemm_no_tiles32 = 0;    // option gemm_tiles32=0 (measurements)
     int gemm_queue_test = 0;    // option gemm_queue_test (measurements)
     int xrows_limit = 0;        // option xrows_limit (tests)
     int hybrid_off = 0;         // option hybrid=0 (measurements): no hand-over to the XCD-scope driver above its row limit
-    int panel_fallbacks = 0;    // host-buffer factorisations redone with panel mode 0 after an exchange time-out
     int panel_spin_limit = 1 << 20;   // polls before the XCD-scope panel gives up on a neighbour (option: tests)
     int spin_limit = 1 << 20;   // polls before a cooperative solve gives up (option trsv_spin_limit: tests)
-    lsx::Prof prof;
+    // ---- read-only counters (lsx_get_option): what the last call of a family did
+    int rref_first_used = 0; // 1 if the last LSX_PIVOT_FIRST reduction took the blocked form
+    int gecon_solves = 0;    // single-right-hand-side solves of the last condition estimate
+    int gerfs_steps = 0;     // most refinement steps any column of the last gerfs took
+    int gerfs_solves = 0;    // single-right-hand-side estimator solves of the last gerfs
+    int getrs_t_path = 0;    // 1 if the last lsx_getrs_t_* call took the blocked sweeps
+    int potrs_path = 0;      // 1 if the last lsx_potrs_* call took the few-column step kernels
+    int pocon_solves = 0;    // single-right-hand-side solves of the last lsx_pocon_* / lsx_porcond_*
+    int porfs_steps = 0;     // most refinement steps any column of the last porfs took
+    int porfs_solves = 0;    // single-right-hand-side estimator solves of the last porfs
+    int panel_fallbacks = 0;    // host-buffer factorisations redone with panel mode 0 after an exchange time-out
+    // ---- buffers.  A DevBuf is sized where it is used (lsx::carve / lsx::reserve) and only grows.  Growing frees the old
+    // block, so no function keeps a pointer into a buffer across a call that may grow the SAME buffer.  Who holds what
+    // across which calls (a callee is listed with what it grows itself):
+    //   host-buffer entry points  staging, across everything below; no driver touches it
+    //   getrf_dev                 scratch, tinv (ensure_getrf_workspace), moves_all (look-ahead); calls no other driver
+    //   getrs_dev, getrs_t_dev    rhs_work, tinv, scratch: the same pieces, so the two share what they grow; the many-column
+    //                             getrs_dev is done with rhs_work before lu_solve_permuted carves tinv; xchg in the launcher
+    //   getri_dev                 rhs_work (permutation) and getri_work, across tinv (its own or lu_solve_permuted's)
+    //   potrf_dev, potrs_dev      tinv, rhs_work
+    //   potrs_few_prepare         tinv, rhs_work, in a PotrsFew that pocon_dev / porfs_dev keep across all their
+    //                             potrs_few_apply calls: they call nothing else that grows these two
+    //   gecon_dev, pocon_dev      cond, across getrs_dev / getrs_t_dev and potrs_few_*
+    //   refine_loop               refine, across getrs_dev / getrs_t_dev (gerfs_dev) and potrs_few_apply (porfs_dev)
+    //   gesvx_dev                 equil, across geequ_dev (equil again, never more than gesvx_dev carved), lange_dev
+    //                             (scratch), getrf_dev, gecon_dev, getrs_dev / getrs_t_dev and gerfs_dev
+    //   gesv_refined_dev          mixed_resid, across getrs_dev
+    //   rref_blocked              rhs_work (its column block and block inverses), scratch
+    //   rref_first_fast           rref_first, across rref_blocked, getrf_dev and getrs_dev; tinv for its own first-rule
+    //                             factorisation, which is finished before those two are called
+    // scratch belongs to the launchers: each lays it out from offset 0 (or a driver's area offset) at launch time and
+    // says how much it needs (*_scratch_bytes, *_work_bytes, *_area_bytes below); no launch relies on what an earlier call left there.
+    DevBuf staging;      // staging of caller matrices (host-buffer entry points)
+    DevBuf tinv;         // triangular block inverses of every driver and solve
+    DevBuf rhs_work;     // permutation + right-hand-side / panel work copies
+    DevBuf mixed_resid;  // residual / correction of the mixed-precision solve
+    DevBuf getri_work;   // work matrix of the structured inverse
+    DevBuf rref_first;   // first-rule row reduction: a copy of the matrix, its pivot columns, interchanges
+    DevBuf cond;         // condition estimators (gecon, pocon): iteration vector, sign vector, record, identity interchanges
+    DevBuf refine;       // refinement loop (gerfs, porfs): residual and bound of a group, two vectors, records, partial sums
+    DevBuf equil;        // equilibration (geequ, gesvx): the drivers' records, then row maxima and partial column maxima
+    DevBuf xchg;         // few-RHS solve (kernels_trsv.hip, third form): exchange granules validated by an epoch, never cleared
+    unsigned xchg_epoch = 0;
+    DevBuf moves_all;    // look-ahead driver with the XCD-scope panel: one gather list per panel
+    DevBuf scratch;      // pivot search partials, exchange areas, flags, index arrays
+    // gather lists (int2[256] each) emitted by the cooperative panel kernels: storage only, a launch is told which one
+    void *moves_buf[2] = {nullptr, nullptr};  // the drivers' lists (the shared-CU look-ahead driver alternates); [0] owns the block
+    void *moves_api = nullptr;       // list of the last lsx_panel_f64_dev call, handed out by lsx_panel_moves_dev
+    bool moves_api_valid = false;    // that call emitted one (touched by those two entry points only)
+    // device status words (never cleared by kernels): [0] panel exchange time-outs when the caller gave no info
+    // word, [1] few-RHS solve time-outs, [2] the internal info word of a factorisation called without one
+    int *dev_status = nullptr;
 };
 
 namespace lsx {
@@ -198,7 +210,32 @@ struct PanelArgs {
     PanelArgs(lsx_handle_t h, void *list_) : mode(h->panel_mode), nt(h->panel_nt), rt(h->panel_rt), list(list_) {}
 };
 
-int ensure_ws(lsx_handle_t h, size_t bytes);
+// b holds at least `need` bytes afterwards: no HIP call when it already does (a warmed-up call stays graph-capturable),
+// else the stream is synchronised, the old block freed and a new one of 1 MiB steps allocated (*fresh, if given, is set).
+int reserve(lsx_handle_t h, DevBuf &b, size_t need, bool *fresh = nullptr);
+// Bump carving of a device block, every piece on a 256-byte boundary.  With a null base it only counts: take returns
+// null and off ends as the bytes the same calls need.
+struct Carver {
+    char *base;
+    size_t off = 0;
+    explicit Carver(void *b) : base((char *)b) {}
+    template <typename U> U *take(size_t count) {
+        off = (off + 255) & ~(size_t)255;
+        U *p = base ? (U *)(base + off) : nullptr;
+        off += count * sizeof(U);
+        return p;
+    }
+};
+// Size b from its own layout and lay it out: `layout` (take calls only, pointers derived from a taken one are formed
+// after carve returns) runs once to count and once on the block.
+template <class F> int carve(lsx_handle_t h, DevBuf &b, F &&layout) {
+    Carver count(nullptr);
+    layout(count);
+    LSX_TRY(reserve(h, b, count.off));
+    Carver c(b.p);
+    layout(c);
+    return LSX_OK;
+}
 int ensure_getrf_workspace(lsx_handle_t h, int n, size_t elem);
 // XCD-scope panel under the reference's first-non-zero pivot rule (kernels_panel_x.hip); 1 = shape not served
 int panel_xcd_first(lsx_handle_t h, int m, int jb, double *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, double tol,
@@ -291,6 +328,8 @@ int launch_rref_trace(lsx_handle_t h, int m, int n, int bar, double *R, int ldr,
 template <typename T>
 int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t *d_ipiv,
                  int *d_info, PanelArgs &pa);
+// scratch of a panel launch (<= m rows) that clears its own area: per-column candidates or the pipelined exchange area
+size_t panel_scratch_bytes(int m);
 // bytes of one exchange area of the pipelined panel for panels of up to m rows; 0 = these panel
 // settings are not ones the pipelined kernel serves for every height <= m
 size_t panel_pipe_area_bytes(lsx_handle_t h, int mode, int nt, int rt, int m);
@@ -333,6 +372,7 @@ int launch_trtri_both(lsx_handle_t h, int n, const T *LU, int lda, T *invL, T *i
 template <typename T>
 int launch_trsm_block(lsx_handle_t h, int lower, int jb, int ncols, const T *Tm, int ldt,
                       const T *Tinv, T *B, int ldb);
+size_t ipiv_to_perm_scratch_bytes(int n);   // two index arrays; with less scratch the launch takes its slow form
 int launch_ipiv_to_perm(lsx_handle_t h, int n, const int32_t *d_ipiv, int32_t *d_perm);
 template <typename T>
 int launch_gather_rows(lsx_handle_t h, int n, int ncols, const int32_t *d_perm, const T *S, int lds,
@@ -343,6 +383,9 @@ template <typename T>
 int launch_scatter_cols(lsx_handle_t h, int n, const int32_t *d_perm, const T *S, int lds, T *D, int ldd);
 template <typename T>
 int launch_det(lsx_handle_t h, int n, const T *LU, int lda, const int32_t *d_ipiv, double *d_out);
+// scratch of an m x n row reduction: state and two rows (per-column form) or row-group candidates (blocked); the trace's state
+size_t rref_scratch_bytes(int m, int n);
+size_t rref_trace_scratch_bytes();
 template <typename T>
 int launch_rref(lsx_handle_t h, int m, int n, int bar, T *R, int ldr, int32_t *d_pivots,
                 int *d_rank, double tol, int pivot_rule);
@@ -358,6 +401,8 @@ int lu_solve_few_rhs2(lsx_handle_t h, int n, int nrhs, int nr, const T *LU, int 
 template <typename T>
 int lu_solve_few_rhs(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, T *B, int ldb, T *X, T *inv64L,
                      T *inv64U, T *inv128L, T *inv128U);
+// scratch of lu_solve_few_rhs for nr (1, 2, 4 or 8) columns: the two exchange areas of its cooperative form
+size_t few_rhs_scratch_bytes(int n, int nr);
 // block inverses of both triangles, 128 x 128, natural orientation (kernels_trsv.hip), and the transposed solve,
 // the norms and the estimator's vector steps built on them (kernels_trsvt.hip)
 template <typename T>

@@ -976,12 +976,14 @@ __global__ __launch_bounds__(256) void perm_chase_kernel(int n, const int32_t *_
     perm[k] = v;
 }
 
+size_t ipiv_to_perm_scratch_bytes(int n) { return 2 * sizeof(int32_t) * (size_t)n + 256; }
+
 int launch_ipiv_to_perm(lsx_handle_t h, int n, const int32_t *d_ipiv, int32_t *d_perm) {
     if (n <= 0) return LSX_OK;
     const size_t need = 2 * sizeof(int32_t) * (size_t)n;
-    if (h->scratch && h->scratch_bytes >= need) {
+    if (h->scratch.p && h->scratch.bytes >= need) {
         // the two index arrays live in the handle's scratch (every later user of it is stream-ordered)
-        int32_t *last_target = (int32_t *)h->scratch, *prev_same = last_target + n;
+        int32_t *last_target = (int32_t *)h->scratch.p, *prev_same = last_target + n;
         hipLaunchKernelGGL(perm_index_kernel, dim3((n + 63) / 64, 2), dim3(256), 0, h->stream, n, d_ipiv, last_target,
                            prev_same);
         hipLaunchKernelGGL(perm_chase_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, d_ipiv, last_target,

@@ -131,9 +131,9 @@ int panel_percolumn(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
                     int32_t *d_ipiv, int *d_info) {
     // scratch layout: cand_val[ngrid] | cand_idx[ngrid]
     const int ngrid_max = (m + PROWS - 1) / PROWS + 1;
-    T *cand_val = (T *)h->scratch;
-    int *cand_idx = (int *)((char *)h->scratch + sizeof(double) * ngrid_max);
-    if (sizeof(double) * ngrid_max + sizeof(int) * ngrid_max > h->scratch_bytes) {
+    T *cand_val = (T *)h->scratch.p;
+    int *cand_idx = (int *)((char *)h->scratch.p + sizeof(double) * ngrid_max);
+    if (sizeof(double) * ngrid_max + sizeof(int) * ngrid_max > h->scratch.bytes) {
         set_error("panel: scratch too small for m=%d", m);
         return LSX_ERR_INTERNAL;
     }
@@ -159,6 +159,11 @@ int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
 
 template <typename T>
 int panel_xcd(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, PanelArgs &pa);
+
+size_t panel_scratch_bytes(int m) {
+    const size_t groups = (size_t)m / 32 + 2;   // 32-row groups: more than either form has workgroups
+    return ((16 * groups + 255) & ~(size_t)255) + groups * 5248 + 8192;
+}
 
 template <typename T>
 int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t *d_ipiv,

@@ -710,11 +710,11 @@ static int panel_xcd_rt(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, 
     const size_t total = dbg_off + (h->panel_debug ? (size_t)G * 128 : 0);
     const bool driver_clears = pa.area_bytes > 0 && !h->panel_debug;
     const size_t base_off = driver_clears ? pa.area_off : 0;
-    if (base_off + total > h->scratch_bytes || (driver_clears && need > pa.area_bytes)) {
-        set_error("panel_xcd: scratch too small (%zu + %zu > %zu)", base_off, total, h->scratch_bytes);
+    if (base_off + total > h->scratch.bytes || (driver_clears && need > pa.area_bytes)) {
+        set_error("panel_xcd: scratch too small (%zu + %zu > %zu)", base_off, total, h->scratch.bytes);
         return LSX_ERR_INTERNAL;
     }
-    char *base = (char *)h->scratch + base_off;
+    char *base = (char *)h->scratch.p + base_off;
     int *status = (int *)base;
     int *xcc = (int *)(base + 64);
     char *rec = base + 256;

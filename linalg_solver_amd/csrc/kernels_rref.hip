@@ -171,6 +171,8 @@ template <typename T>
 int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *d_pivots, int *d_rank, double tol,
                  int pivot_rule);
 
+size_t rref_scratch_bytes(int m, int n) { return 256 + 2 * sizeof(double) * (size_t)n + 4096 + 2 * (size_t)m; }
+
 template <typename T>
 int launch_rref(lsx_handle_t h, int m, int n, int bar, T *R, int ldr, int32_t *d_pivots, int *d_rank,
                 double tol, int pivot_rule) {
@@ -181,12 +183,12 @@ int launch_rref(lsx_handle_t h, int m, int n, int bar, T *R, int ldr, int32_t *d
     ProfScope ps(h, LSX_PROF_OTHER);
     // scratch: state | prow[n] | orow[n]
     const size_t need = 256 + 2 * (size_t)n * sizeof(T);
-    if (need > h->scratch_bytes) {
+    if (need > h->scratch.bytes) {
         set_error("rref: scratch too small (need %zu)", need);
         return LSX_ERR_INTERNAL;
     }
-    RrefState *st = (RrefState *)h->scratch;
-    T *prow = (T *)((char *)h->scratch + 256);
+    RrefState *st = (RrefState *)h->scratch.p;
+    T *prow = (T *)((char *)h->scratch.p + 256);
     T *orow = prow + n;
     LSX_HIP(hipMemsetAsync(st, 0, sizeof(RrefState), h->stream));
     if (tol < 0 && bar > 0)

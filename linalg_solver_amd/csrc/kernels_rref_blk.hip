@@ -300,28 +300,22 @@ int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *
     if (pivot_rule != LSX_PIVOT_MAX || (size_t)m * bar < (size_t)256 * 256 || bar < 1) return 1;
     ProfScope ps(h, LSX_PROF_OTHER);
     const int ncand = (m + RRB_ROWS - 1) / RRB_ROWS;
-    // scratch: state | amax | cand_val | cand_idx ; workspace (ws3): L / G buffer m x 128, block inverses
-    const size_t need = 2048 + (size_t)ncand * (sizeof(T) + sizeof(int)) + 256;
-    if (need > h->scratch_bytes) { set_error("rref_blocked: scratch too small"); return LSX_ERR_INTERNAL; }
-    RrbState *st = (RrbState *)h->scratch;
-    double *amax = (double *)((char *)h->scratch + 1536);
-    T *cand_val = (T *)((char *)h->scratch + 2048);
-    int *cand_idx = (int *)((char *)h->scratch + 2048 + (((size_t)ncand * sizeof(T) + 15) & ~(size_t)15));
-    const size_t lbytes = (((size_t)m * RB_W * sizeof(T)) + 255) & ~(size_t)255;
-    const size_t tbytes = 2 * 4096 * sizeof(T);
-    if (h->ws3_bytes < lbytes + tbytes) {
-        LSX_HIP(hipStreamSynchronize(h->stream));
-        if (h->ws3) (void)hipFree(h->ws3);
-        h->ws3 = nullptr; h->ws3_bytes = 0;
-        if (hipMalloc(&h->ws3, lbytes + tbytes) != hipSuccess) { set_error("rref_blocked: hipMalloc"); return LSX_ERR_ALLOC; }
-        h->ws3_bytes = lbytes + tbytes;
-    }
-    T *L = (T *)h->ws3;
-    T *Tinv = (T *)((char *)h->ws3 + lbytes);
+    // scratch: state | amax | cand_val | cand_idx (2048 + 12 or 16 bytes per row group: within rref_scratch_bytes)
+    if (rref_scratch_bytes(m, n) > h->scratch.bytes) { set_error("rref_blocked: scratch too small"); return LSX_ERR_INTERNAL; }
+    RrbState *st = (RrbState *)h->scratch.p;
+    double *amax = (double *)((char *)h->scratch.p + 1536);
+    T *cand_val = (T *)((char *)h->scratch.p + 2048);
+    int *cand_idx = (int *)((char *)h->scratch.p + 2048 + (((size_t)ncand * sizeof(T) + 15) & ~(size_t)15));
+    // rhs_work: L / G buffer m x 128, block inverses (two 64 x 64)
+    T *L = nullptr, *Tinv = nullptr;
+    LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) {
+        L = c.take<T>((size_t)m * RB_W);
+        Tinv = c.take<T>(2 * 4096);
+    }));
     GemmPlan mfma;   // as in the LU drivers: narrow updates on the MFMA kernel too
     mfma.mfma_only = true;
     hipStream_t s = h->stream;
-    LSX_HIP(hipMemsetAsync(h->scratch, 0, 2048, s));
+    LSX_HIP(hipMemsetAsync(h->scratch.p, 0, 2048, s));
     if (tol < 0) hipLaunchKernelGGL(rrb_amax_kernel<T>, dim3(256), dim3(256), 0, s, m, bar, W, ldw, amax);
     // 32 eps max(m, n): the residue of a dependent column after k elimination steps is ~k eps times the running
     // maximum with a tail; a factor of 1 put exactly-rank-517 integer products of order 1000 at rank 518

@@ -358,11 +358,11 @@ static int trsv_coop_run(lsx_handle_t h, int n, const T *LU, int lda, T *B, int 
     {
         // one launch per direction; exchange area (zeroed) + status word in the scratch
         const size_t xbytes = (size_t)wgs * CB * NR * sizeof(XGran);
-        if (256 + 2 * xbytes > h->scratch_bytes) { set_error("trsv: scratch too small"); return LSX_ERR_INTERNAL; }
+        if (256 + 2 * xbytes > h->scratch.bytes) { set_error("trsv: scratch too small"); return LSX_ERR_INTERNAL; }
         int *status = h->dev_status + 1;   // persistent word: read (and cleared) by the host entry points / lsx_check_status
         const int spin_limit = h->spin_limit;
-        XGran *xb0 = (XGran *)((char *)h->scratch + 256), *xb1 = (XGran *)((char *)h->scratch + 256 + xbytes);
-        LSX_HIP(hipMemsetAsync(h->scratch, 0, 256 + 2 * xbytes, h->stream));
+        XGran *xb0 = (XGran *)((char *)h->scratch.p + 256), *xb1 = (XGran *)((char *)h->scratch.p + 256 + xbytes);
+        LSX_HIP(hipMemsetAsync(h->scratch.p, 0, 256 + 2 * xbytes, h->stream));
         hipLaunchKernelGGL((trsv_coop_kernel<T, NR, true>), dim3(wgs), dim3(256), 0, h->stream, n, LU, lda, inv64L,
                            (const T *)B, ldb, X, xb0, status, spin_limit);
         LSX_TRY(launch_copy2d<T>(h, n, NR, X, NR, B, ldb));  // y is the right-hand side of U x = y
@@ -899,22 +899,18 @@ int lu_solve_few_rhs2(lsx_handle_t h, int n, int nrhs, int nr, const T *LU, int 
     if (nr >= 8 && H > 4) H = 4;                           // 8 right-hand sides: the helpers' partial sums are 8 x the traffic
     const size_t xbytes = (size_t)NB * SB * nr * sizeof(XGran), pbytes = xbytes * H;
     const size_t need = 2 * (xbytes + pbytes) + 256;
-    if (need > h->xchg_bytes) {
-        // a fresh, zeroed area: tags of another life of the memory must not pass for this handle's epochs
-        LSX_HIP(hipStreamSynchronize(h->stream));
-        if (h->xchg) (void)hipFree(h->xchg);
-        h->xchg = nullptr; h->xchg_bytes = 0;
-        LSX_HIP(hipMalloc(&h->xchg, need));
-        LSX_HIP(hipMemsetAsync(h->xchg, 0, need, h->stream));
-        h->xchg_bytes = need;
+    bool fresh = false;
+    LSX_TRY(reserve(h, h->xchg, need, &fresh));
+    if (fresh) {   // zeroed: tags of another life of the memory must not pass for this handle's epochs
+        LSX_HIP(hipMemsetAsync(h->xchg.p, 0, h->xchg.bytes, h->stream));
         h->xchg_epoch = 0;
     }
     if (++h->xchg_epoch == 0u) {   // wrapped: start over on a cleared area
-        LSX_HIP(hipMemsetAsync(h->xchg, 0, h->xchg_bytes, h->stream));
+        LSX_HIP(hipMemsetAsync(h->xchg.p, 0, h->xchg.bytes, h->stream));
         h->xchg_epoch = 1;
     }
     ProfScope ps(h, LSX_PROF_TRSM, 2.0 * n * (double)n * nrhs, 2.0 * sizeof(T) * n * (double)n);
-    XGran *xgL = (XGran *)((char *)h->xchg + 256), *pgL = (XGran *)((char *)xgL + xbytes);
+    XGran *xgL = (XGran *)((char *)h->xchg.p + 256), *pgL = (XGran *)((char *)xgL + xbytes);
     XGran *xgU = (XGran *)((char *)pgL + pbytes), *pgU = (XGran *)((char *)xgU + xbytes);
     int *status = h->dev_status + 1;
     LSX_TRY(launch_trtri_both<T>(h, n, LU, lda, inv64L, inv64U));
@@ -926,8 +922,8 @@ int lu_solve_few_rhs2(lsx_handle_t h, int n, int nrhs, int nr, const T *LU, int 
                        (const T *)inv64L, (const T *)inv64U, inv128L, inv128U, d_ipiv, (const T *)B, ldb, Bp);
     // development: LSX_S2_DBG=1 -> owner stamps in the handle's scratch (tools/solve_stamps.py reads them back)
     unsigned long long *dbgL = nullptr, *dbgU = nullptr;
-    if (getenv("LSX_S2_DBG") && h->scratch_bytes >= (size_t)NB * 128 + 4096) {
-        dbgL = (unsigned long long *)h->scratch;
+    if (getenv("LSX_S2_DBG") && h->scratch.bytes >= (size_t)NB * 128 + 4096) {
+        dbgL = (unsigned long long *)h->scratch.p;
         dbgU = dbgL + (size_t)NB * 8;
     }
 #define S2_LAUNCH(NRV)                                                                                                    \
@@ -951,6 +947,9 @@ template int lu_solve_few_rhs2<double>(lsx_handle_t, int, int, int, const double
                                        double *, double *, double *, double *, double *, double *);
 template int lu_solve_few_rhs2<float>(lsx_handle_t, int, int, int, const float *, int, const int32_t *, float *, int, float *,
                                       float *, float *, float *, float *, float *);
+
+// (sized for 128-row steps: no less than the 64-row workgroups of trsv_coop_run take)
+size_t few_rhs_scratch_bytes(int n, int nr) { return 512 + 2 * (size_t)((n + 127) / 128) * 128 * nr * sizeof(XGran); }
 
 // X (n x nrhs, dense) <- U^-1 L^-1 B for B already row-permuted; B is used as work space.
 // nrhs must be 1, 2, 4 or 8 (the caller pads).

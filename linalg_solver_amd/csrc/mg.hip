@@ -200,9 +200,9 @@ static int getrf_mg_body(std::vector<Dev> &D, lsx_handle_t *hs, int P, int n, do
         else LSX_TRY(launch_laswp<double>(x.h, c1 - c0, Ac, lda[d], k, jb, (const int32_t *)(buf + 2304)));
         double *U12 = dA[d] + (size_t)k * lda[d] + c0;
         const size_t tinv = (size_t)((jb + 63) / 64) * 4096 * sizeof(double);
-        if (x.h->ws2_bytes < tinv) { set_error("getrf_mg: block-inverse workspace"); return LSX_ERR_INTERNAL; }
-        LSX_TRY(launch_trtri<double>(x.h, 1, jb, panel, jb, (double *)x.h->ws2));
-        LSX_TRY(launch_trsm_block<double>(x.h, 1, jb, c1 - c0, panel, jb, (const double *)x.h->ws2, U12, lda[d]));
+        if (x.h->tinv.bytes < tinv) { set_error("getrf_mg: block-inverse workspace"); return LSX_ERR_INTERNAL; }
+        LSX_TRY(launch_trtri<double>(x.h, 1, jb, panel, jb, (double *)x.h->tinv.p));
+        LSX_TRY(launch_trsm_block<double>(x.h, 1, jb, c1 - c0, panel, jb, (const double *)x.h->tinv.p, U12, lda[d]));
         if (m > jb) {
             if (d == o || !chunked) {
                 if (d != o) LSX_HIP(hipStreamWaitEvent(x.comp, landed(MG_CHUNKS - 1), 0));

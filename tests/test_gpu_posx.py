@@ -712,7 +712,7 @@ def test_matrix_solve_pos_def_array(la, fill):
 # ------------------------------------------------------------------ nothing else moved
 def test_gerfs_and_gecon_keep_their_bits_around_porfs_and_pocon(la):
     """lsx_gerfs_f64 and lsx_gecon_f64 before and after a porfs / pocon call on the same handle: the shared loop and
-    the shared work space (ws7, ws8) leave them their bits."""
+    the shared work space (the cond and refine buffers) leave them their bits."""
     from linalg_solver_amd import dense
 
     n = 300
