@@ -430,6 +430,77 @@ int lsx_posv_f32(lsx_handle_t h, int n, int nrhs, const float *A, int lda, float
 int lsx_syrk_tn_sub_f64_dev(lsx_handle_t h, int n, int k, const double *dA, int lda, double *dC, int ldc);
 int lsx_syrk_tn_sub_f32_dev(lsx_handle_t h, int n, int k, const float *dA, int lda, float *dC, int ldc);
 
+/* ---- Cholesky: inverse and determinant from the factor (LAPACK's potri; trtri and lauum as its two phases) ---- */
+/* Storage as above: row-major, UPPER, A = U^T U.  inv(A) = inv(U) inv(U)^T = V^T V with V = inv(U^T), lower triangular:
+ * n^3/3 flops for V, n^3/3 for the product, against 4/3 n^3 for lsx_getri_* after 2/3 n^3 for lsx_getrf_*; no pivoting.
+ * Nothing here is cooperative: no kernel waits on another workgroup, there is no time-out outcome and lsx_check_status
+ * has nothing to report.  Deterministic: a fixed order of k in every product, no split-K, no atomics on data; two calls
+ * give identical bits; any alignment and leading dimension (16-byte forms where the operands allow, element-wise forms
+ * otherwise, same bits).  As for lsx_potrs_*, every u_ii needs a reciprocal that is a finite number.
+ *
+ * lsx_potri_*_dev: in place.  On return the upper triangle of dU holds the upper triangle of inv(A); the strictly lower
+ * triangle is never read and never written, inside a diagonal 128-block either.  Asynchronous on the handle's stream.
+ * d_info is a device int and may be NULL: 0, or i + 1 (1-based) for the first u_ii that is exactly zero or NaN (dtrtri's
+ * test); the upper triangle is then unspecified and may hold inf or NaN, and no launch faults or waits.  Work space: V,
+ * n x ceil16(n) elements, the block inverses of lsx_potrs_* and one 128-row strip, all on the handle.  Arguments as
+ * lsx_potrf_*_dev: lda >= n; n == 0 is LSX_OK with nothing touched; dU non-NULL otherwise.
+ * lsx_potri_*: the host-buffer form; the upper triangle is staged both ways as in lsx_potrf_* (each 128-row block row from
+ * its first diagonal column on), *info (may be NULL) as d_info.
+ * lsx_poinv_*: factor, invert and mirror a host matrix in one call.  A is not modified (only its upper triangle is read);
+ * Ainv (n x n, ldi >= n) receives the FULL inverse, both triangles, exactly symmetric.  *info as lsx_potrf_* (may be
+ * NULL); with info > 0 Ainv is not written.
+ *
+ * lsx_trtri_upper_t_*_dev: the first phase on its own, dV = inv(dU^T).  Written: row i of dV in the columns
+ * [0, 128 (i / 128 + 1)), cut at n -- the blocks on and below the diagonal 128-blocks; inside a diagonal block the
+ * entries above the diagonal are exact zeros.  The blocks of dV strictly above the diagonal blocks are never written and
+ * never read.  Of dU the upper triangle alone is read.  dU and dV must not overlap.  Forward substitution over 128-row
+ * steps on the TN form of the MFMA tile, block row kb on its columns [0, kb + jb) only.
+ * lsx_lauum_tn_*_dev: the second phase on its own, the upper triangle of dC (n x n) = dV^T * dV for a lower-triangular dV
+ * (n x n, row-major, ldv >= n, ldc >= n).  For col >= row the sum runs over k >= col only, so the tile (I, J) of 128 x 128
+ * takes k from 128 J on: the blocks of dV strictly above its diagonal 128-blocks are never read (they may hold NaN);
+ * inside a diagonal block the entries above the diagonal are read and must be the zeros of a lower-triangular matrix.
+ * The strictly lower triangle of dC is neither read nor written; dC is not read at all.  By default k is taken in
+ * ascending order, so every element of the upper triangle has the bits that lsx_gemm_tn_add_*_dev(n, n, n, V0, ldv, V0, ldv, Z, ldc) gives
+ * it for V0 = dV with zeros above the diagonal and Z = 0: the skipped terms are products with exact zeros added to a
+ * zero accumulator.  One launch when n is a multiple of 128 and the operands are 16-byte aligned with leading dimensions
+ * that are multiples of 16 bytes.  The option "potri_order" (0, default: tiles handed out deepest first, by ascending
+ * tile column; 1: the order of lsx_syrk_tn_sub_*_dev) picks the tile order of this product here and in lsx_potri_* --
+ * same bits either way -- and "potri_tiles" reads back how many tiles the last such product ran: t (t + 1) / 2 with
+ * t = ceil(n / 128).  A zero n leaves dC untouched (pointers may then be NULL); LSX_ERR_ARG for a negative n, ldv < n,
+ * ldc < n or a NULL pointer with n > 0.
+ * Order of summation.  lsx_potri_* runs this product with every tile's k-slabs of 16 taken from the LAST one down to the
+ * first (k ascending inside a slab; a partial last slab comes first); the option "lauum_descending" = 1 (default 0) makes
+ * lsx_lauum_tn_*_dev do the same, so that lsx_potri_*_dev has the bits of lsx_trtri_upper_t_*_dev followed by
+ * lsx_lauum_tn_*_dev under that option.  Why: the term k = col of the sum carries v[col][col], which dominates when V is
+ * diagonally dominant; met first, every later addition is rounded at the size of the whole sum (measured: LAPACK's test
+ * ratio of the inverse 4 to 6 times that of LAPACK's potri on G G^T / n + I); met after the tail, 1.5 to 1.6 times.  The
+ * two orders cost the same time.  The ascending default of the stand-alone entry point keeps its bits comparable with
+ * lsx_gemm_tn_add_*_dev.
+ * lsx_symmetrize_upper_*_dev: a_ji = a_ij for every j > i -- the only entry point of this family that writes below the
+ * diagonal.  A tiled transpose-copy through LDS; the diagonal and the upper triangle are not written.
+ *
+ * lsx_podet_*_dev: det(A) = prod u_ii^2 from the factor: d_out = {sign, mant, (double)exp2} in the format of
+ * lsx_det_*_dev, det = sign * mant * 2^exp2 with mant in [0.5, 1).  sign is 1, or 0 with mant = exp2 = 0 when some u_ii
+ * is exactly zero.  n == 0 gives {1, 0.5, 1}.  Asynchronous.
+ * lsx_podet_*: factors a copy of a host matrix and returns its determinant; *info as lsx_potrf_* (may be NULL); with
+ * info > 0 the three outputs are 0. */
+int lsx_potri_f64_dev(lsx_handle_t h, int n, double *dU, int lda, int *d_info);
+int lsx_potri_f32_dev(lsx_handle_t h, int n, float *dU, int lda, int *d_info);
+int lsx_potri_f64(lsx_handle_t h, int n, double *U, int lda, int *info);
+int lsx_potri_f32(lsx_handle_t h, int n, float *U, int lda, int *info);
+int lsx_poinv_f64(lsx_handle_t h, int n, const double *A, int lda, double *Ainv, int ldi, int *info);
+int lsx_poinv_f32(lsx_handle_t h, int n, const float *A, int lda, float *Ainv, int ldi, int *info);
+int lsx_trtri_upper_t_f64_dev(lsx_handle_t h, int n, const double *dU, int lda, double *dV, int ldv);
+int lsx_trtri_upper_t_f32_dev(lsx_handle_t h, int n, const float *dU, int lda, float *dV, int ldv);
+int lsx_lauum_tn_f64_dev(lsx_handle_t h, int n, const double *dV, int ldv, double *dC, int ldc);
+int lsx_lauum_tn_f32_dev(lsx_handle_t h, int n, const float *dV, int ldv, float *dC, int ldc);
+int lsx_symmetrize_upper_f64_dev(lsx_handle_t h, int n, double *dA, int lda);
+int lsx_symmetrize_upper_f32_dev(lsx_handle_t h, int n, float *dA, int lda);
+int lsx_podet_f64_dev(lsx_handle_t h, int n, const double *dU, int lda, double *d_out);
+int lsx_podet_f32_dev(lsx_handle_t h, int n, const float *dU, int lda, double *d_out);
+int lsx_podet_f64(lsx_handle_t h, int n, const double *A, int lda, double *sign, double *mant, int64_t *exp2, int *info);
+int lsx_podet_f32(lsx_handle_t h, int n, const float *A, int lda, double *sign, double *mant, int64_t *exp2, int *info);
+
 /* ---- Cholesky: condition estimate and error bounds (LAPACK's lansy, pocon, porfs) ---- */
 /* Storage as above: row-major, UPPER, A = U^T U.  The strictly lower triangle of A and of U is never loaded and never
  * written by any of these, inside a diagonal tile or block included: it may hold NaN.  Nothing here is cooperative: no

@@ -140,6 +140,22 @@ _SIGS = {
     "lsx_diag_resid_bound_sym_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i],
     "lsx_syrk_tn_sub_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _i],
     "lsx_syrk_tn_sub_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _i],
+    "lsx_potri_f64_dev": [_vp, _i, _vp, _i, _vp],
+    "lsx_potri_f32_dev": [_vp, _i, _vp, _i, _vp],
+    "lsx_potri_f64": [_vp, _i, _dp, _i, C.POINTER(_i)],
+    "lsx_potri_f32": [_vp, _i, _fp, _i, C.POINTER(_i)],
+    "lsx_poinv_f64": [_vp, _i, _dp, _i, _dp, _i, C.POINTER(_i)],
+    "lsx_poinv_f32": [_vp, _i, _fp, _i, _fp, _i, C.POINTER(_i)],
+    "lsx_trtri_upper_t_f64_dev": [_vp, _i, _vp, _i, _vp, _i],
+    "lsx_trtri_upper_t_f32_dev": [_vp, _i, _vp, _i, _vp, _i],
+    "lsx_lauum_tn_f64_dev": [_vp, _i, _vp, _i, _vp, _i],
+    "lsx_lauum_tn_f32_dev": [_vp, _i, _vp, _i, _vp, _i],
+    "lsx_symmetrize_upper_f64_dev": [_vp, _i, _vp, _i],
+    "lsx_symmetrize_upper_f32_dev": [_vp, _i, _vp, _i],
+    "lsx_podet_f64_dev": [_vp, _i, _vp, _i, _vp],
+    "lsx_podet_f32_dev": [_vp, _i, _vp, _i, _vp],
+    "lsx_podet_f64": [_vp, _i, _dp, _i, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(_i)],
+    "lsx_podet_f32": [_vp, _i, _fp, _i, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(_i)],
     "lsx_matmul_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i],
     "lsx_fill_f64_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],
     "lsx_fill_f32_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],

@@ -1060,6 +1060,155 @@ static int syrk_tn_dev(lsx_handle_t h, int n, int k, const T *dA, int lda, T *dC
     return launch_syrk_tn_sub<T>(h, n, k, dA, lda, dC, ldc);
 }
 
+// ---------------------------------------------------------------- SPD inverse and determinant from the factor
+// inv(A) = inv(U) inv(U)^T = V^T V with V = inv(U^T), lower triangular: n^3/3 flops for V, n^3/3 for the product.
+//
+// trtri_upper_t: V = inv(U^T) on and below the diagonal 128-blocks of V.  The forward loop of potrs_dev (U^T Y = B on
+// the TN tile) applied to the identity with getri_dev's column restriction: block row kb has columns [0, kb + jb) to
+// work on, the rest are exact zeros and stay unwritten.  The diagonal-block product cannot run in place, so the block
+// row goes through one 128-row strip (potrf_dev's device) and back.  U is read through its diagonal blocks
+// (launch_chol_inv: the upper triangle alone) and through the blocks strictly above them.  Inside a diagonal block of V
+// the entries above the diagonal are exact zeros (inv128's zeros times finite numbers); the blocks of V strictly above
+// the diagonal blocks are never written.
+template <typename T>
+static int trtri_upper_t(lsx_handle_t h, int n, const T *U, int lda, T *V, int ldv) {
+    const int sb = 128, ldw = ld_for(n);
+    T *inv64 = nullptr, *inv128 = nullptr, *S = nullptr;
+    LSX_TRY(carve(h, h->tinv, [&](Carver &c) { inv64 = c.take<T>(inv64_elems(n)); inv128 = c.take<T>(inv128_elems(n)); }));
+    LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) { S = c.take<T>((size_t)sb * ldw); }));
+    auto Up = [&](int r, int c) { return U + (size_t)r * lda + c; };
+    auto Vp = [&](int r) { return V + (size_t)r * ldv; };
+    LSX_TRY(launch_chol_inv<T>(h, n, U, lda, inv64, inv128));
+    LSX_TRY(launch_lower_identity<T>(h, n, V, ldv));
+    for (int kb = 0; kb < n; kb += sb) {
+        const int jb = (n - kb < sb) ? n - kb : sb, nc = kb + jb;
+        {
+            ProfScope ps(h, LSX_PROF_TRSM, 0, 2.0 * sizeof(T) * jb * (double)nc);
+            LSX_TRY(launch_copy2d<T>(h, jb, nc, Vp(kb), ldv, S, ldw));
+        }
+        LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nc, jb, inv128 + (size_t)(kb / sb) * sb * sb, sb, S, ldw, Vp(kb), ldv, LSX_PROF_TRSM));
+        LSX_TRY(launch_gemm_tn_sub<T>(h, n - kb - jb, nc, jb, Up(kb, kb + jb), lda, Vp(kb), ldv, Vp(kb + jb), ldv));
+    }
+    return LSX_OK;
+}
+
+template <typename T>
+static int trtri_upper_t_dev(lsx_handle_t h, int n, const T *dU, int lda, T *dV, int ldv) {
+    LSX_ARG(h && n >= 0 && lda >= n && ldv >= n);
+    if (n == 0) return LSX_OK;
+    LSX_ARG(dU && dV);
+    return trtri_upper_t<T>(h, n, dU, lda, dV, ldv);
+}
+
+template <typename T>
+static int lauum_tn_dev(lsx_handle_t h, int n, const T *dV, int ldv, T *dC, int ldc) {
+    LSX_ARG(h && n >= 0 && ldv >= n && ldc >= n);
+    h->potri_tiles = 0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(dV && dC);
+    return launch_lauum_tn<T>(h, n, dV, ldv, dC, ldc, h->potri_order, h->lauum_descending != 0);
+}
+
+// LAPACK's potri, in place: the upper triangle of the factor array receives the upper triangle of inv(A).  V lives in
+// getri_work (n x ld_for(n), aligned whatever lda is); U is dead once V is formed, so the product (always in its
+// descending k-slab form, which adds the dominant terms k = col last: kernels_gemm.hip) goes straight into the
+// caller's array.  A zero or NaN u_ii is reported and otherwise takes its course: the launches are the same, nothing
+// faults or waits, the upper triangle then holds inf / NaN.
+template <typename T>
+static int potri_dev(lsx_handle_t h, int n, T *U, int lda, int *d_info) {
+    LSX_ARG(h && n >= 0 && lda >= n);
+    h->potri_tiles = 0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(U);
+    const int ldw = ld_for(n);
+    T *V = nullptr;
+    LSX_TRY(carve(h, h->getri_work, [&](Carver &c) { V = c.take<T>((size_t)n * ldw); }));
+    if (d_info) LSX_TRY(launch_diag_zero_info<T>(h, n, U, lda, d_info));
+    LSX_TRY(trtri_upper_t<T>(h, n, U, lda, V, ldw));
+    return launch_lauum_tn<T>(h, n, V, ldw, U, lda, h->potri_order, true);
+}
+
+template <typename T>
+static int symmetrize_upper_dev(lsx_handle_t h, int n, T *dA, int lda) {
+    LSX_ARG(h && n >= 0 && lda >= n);
+    if (n == 0) return LSX_OK;
+    LSX_ARG(dA);
+    return launch_symmetrize_upper<T>(h, n, dA, lda);
+}
+
+// det(A) = prod u_ii^2 as {sign, mant, exp2} (lsx_det_*_dev's format): det_kernel's frexp product, the pair squared
+template <typename T>
+static int podet_dev(lsx_handle_t h, int n, const T *dU, int lda, double *d_out) {
+    LSX_ARG(h && n >= 0 && lda >= n && d_out && (n == 0 || dU));
+    return launch_det<T>(h, n, dU, lda, nullptr, d_out, true);
+}
+
+template <typename T>
+static int potri_host(lsx_handle_t h, int n, T *U, int lda, int *info) {
+    LSX_ARG(h && n >= 0 && lda >= n);
+    if (n == 0) return LSX_OK;
+    LSX_ARG(U);
+    if (info) *info = 0;
+    const int ld = ld_for(n);
+    T *dU = nullptr; int *dinfo = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dU = c.take<T>((size_t)n * ld); dinfo = c.take<int>(1); }));
+    int hinfo = 0;
+    LSX_TRY(upper_h2d<T>(h, n, U, lda, dU, ld));
+    LSX_TRY(potri_dev<T>(h, n, dU, ld, dinfo));
+    LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LSX_TRY(upper_d2h<T>(h, n, dU, ld, U, lda));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (info) *info = hinfo;
+    return LSX_OK;
+}
+
+// factor, invert, mirror: A is kept, Ainv receives both triangles
+template <typename T>
+static int poinv_host(lsx_handle_t h, int n, const T *A, int lda, T *Ainv, int ldi, int *info) {
+    LSX_ARG(h && n >= 0 && lda >= n && ldi >= n);
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A && Ainv);
+    if (info) *info = 0;
+    const int ld = ld_for(n);
+    T *dA = nullptr; int *dinfo = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dA = c.take<T>((size_t)n * ld); dinfo = c.take<int>(1); }));
+    int hinfo = 0;
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
+    LSX_TRY(potrf_dev<T>(h, n, dA, ld, dinfo));
+    LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (info) *info = hinfo;
+    if (hinfo != 0) return LSX_OK;   // not positive definite: Ainv is left untouched
+    LSX_TRY(potri_dev<T>(h, n, dA, ld, nullptr));   // u_ii > 0 after a clean factorisation
+    LSX_TRY(launch_symmetrize_upper<T>(h, n, dA, ld));
+    LSX_TRY(d2h<T>(h, n, n, dA, ld, Ainv, ldi));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+template <typename T>
+static int podet_host(lsx_handle_t h, int n, const T *A, int lda, double *sign, double *mant, int64_t *exp2, int *info) {
+    LSX_ARG(h && n >= 0 && lda >= n && sign && mant && exp2);
+    if (info) *info = 0;
+    if (n == 0) { *sign = 1; *mant = 0.5; *exp2 = 1; return LSX_OK; }   // det([]) = 1, as lsx_det_*
+    LSX_ARG(A);
+    const int ld = ld_for(n);
+    T *dA = nullptr; int *dinfo = nullptr; double *dout = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dA = c.take<T>((size_t)n * ld); dinfo = c.take<int>(1); dout = c.take<double>(3); }));
+    int hinfo = 0;
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
+    LSX_TRY(potrf_dev<T>(h, n, dA, ld, dinfo));
+    LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LSX_TRY(launch_det<T>(h, n, dA, ld, nullptr, dout, true));
+    double out[3];
+    LSX_HIP(hipMemcpyAsync(out, dout, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (info) *info = hinfo;
+    if (hinfo != 0) { *sign = 0; *mant = 0; *exp2 = 0; return LSX_OK; }   // not positive definite: no value
+    *sign = out[0]; *mant = out[1]; *exp2 = (int64_t)out[2];
+    return LSX_OK;
+}
+
 // A^T X = B from the factors (kernels_trsvt.hip).  Work space as in getrs_dev, so the two share what they grow.
 // may_block = false: the single-column solves inside the estimators, which keep the grouped path whatever the option says.
 template <typename T>
@@ -2045,6 +2194,12 @@ int lsx_set_option(lsx_handle_t h, const char *key, int value) {
     } else if (!strcmp(key, "potrs_few_max")) {   // Cholesky solve: largest nrhs on the few-column step kernels; 0 = never
         LSX_ARG(value >= 0 && value <= 8);
         h->potrs_few_max = value;
+    } else if (!strcmp(key, "potri_order")) {   // SPD inverse, V^T V tiles: 0 = deepest first, 1 = the symmetric update's order (same bits)
+        LSX_ARG(value == 0 || value == 1);
+        h->potri_order = value;
+    } else if (!strcmp(key, "lauum_descending")) {   // lsx_lauum_tn_*: 1 = the descending k-slabs lsx_potri_* runs, 0 = k ascending
+        LSX_ARG(value == 0 || value == 1);
+        h->lauum_descending = value;
     } else {
         set_error("unknown option '%s'", key);
         return LSX_ERR_ARG;
@@ -2080,6 +2235,9 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value) {
     else if (!strcmp(key, "getrs_t_path")) *value = h->getrs_t_path;
     else if (!strcmp(key, "potrs_few_max")) *value = h->potrs_few_max;
     else if (!strcmp(key, "potrs_path")) *value = h->potrs_path;
+    else if (!strcmp(key, "potri_order")) *value = h->potri_order;
+    else if (!strcmp(key, "lauum_descending")) *value = h->lauum_descending;
+    else if (!strcmp(key, "potri_tiles")) *value = h->potri_tiles;
     else if (!strcmp(key, "pocon_solves")) *value = h->pocon_solves;
     else if (!strcmp(key, "porfs_steps")) *value = h->porfs_steps;
     else if (!strcmp(key, "porfs_solves")) *value = h->porfs_solves;
@@ -2794,6 +2952,38 @@ int lsx_gemm_tn_sub_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dA
     int lsx_syrk_tn_sub_##SFX##_dev(lsx_handle_t h, int n, int k, const T *dA, int lda, T *dC, int ldc) {                 \
         LSX_DEVICE_GUARD(h);                                                                                              \
         return syrk_tn_dev<T>(h, n, k, dA, lda, dC, ldc);                                                                 \
+    }                                                                                                                     \
+    int lsx_potri_##SFX##_dev(lsx_handle_t h, int n, T *dU, int lda, int *d_info) {                                       \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return potri_dev<T>(h, n, dU, lda, d_info);                                                                       \
+    }                                                                                                                     \
+    int lsx_trtri_upper_t_##SFX##_dev(lsx_handle_t h, int n, const T *dU, int lda, T *dV, int ldv) {                      \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return trtri_upper_t_dev<T>(h, n, dU, lda, dV, ldv);                                                              \
+    }                                                                                                                     \
+    int lsx_lauum_tn_##SFX##_dev(lsx_handle_t h, int n, const T *dV, int ldv, T *dC, int ldc) {                           \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return lauum_tn_dev<T>(h, n, dV, ldv, dC, ldc);                                                                   \
+    }                                                                                                                     \
+    int lsx_symmetrize_upper_##SFX##_dev(lsx_handle_t h, int n, T *dA, int lda) {                                         \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return symmetrize_upper_dev<T>(h, n, dA, lda);                                                                    \
+    }                                                                                                                     \
+    int lsx_podet_##SFX##_dev(lsx_handle_t h, int n, const T *dU, int lda, double *d_out) {                               \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return podet_dev<T>(h, n, dU, lda, d_out);                                                                        \
+    }                                                                                                                     \
+    int lsx_potri_##SFX(lsx_handle_t h, int n, T *U, int lda, int *info) {                                                \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return potri_host<T>(h, n, U, lda, info);                                                                         \
+    }                                                                                                                     \
+    int lsx_poinv_##SFX(lsx_handle_t h, int n, const T *A, int lda, T *Ainv, int ldi, int *info) {                        \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return poinv_host<T>(h, n, A, lda, Ainv, ldi, info);                                                              \
+    }                                                                                                                     \
+    int lsx_podet_##SFX(lsx_handle_t h, int n, const T *A, int lda, double *sign, double *mant, int64_t *exp2, int *info) { \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return podet_host<T>(h, n, A, lda, sign, mant, exp2, info);                                                       \
     }                                                                                                                     \
     int lsx_potrf_##SFX(lsx_handle_t h, int n, T *A, int lda, int *info) {                                                \
         LSX_DEVICE_GUARD(h);                                                                                              \

@@ -110,6 +110,8 @@ struct lsx_handle_s {
     int rref_blocked = 1;       // 1: large inputs with LSX_PIVOT_MAX take the blocked row reduction (option rref_blocked)
     int getrs_t_blocked_min = 64;   // transposed solve: smallest nrhs that takes the blocked (MFMA) sweeps when n > 128; 0 = never
     int potrs_few_max = 0;   // Cholesky solve: largest nrhs (<= 8) that takes the few-column step kernels; 0 = never
+    int lauum_descending = 0;   // lsx_lauum_tn_*: 1 = the k-slabs in descending order, the form lsx_potri_* always runs; 0 = k ascending
+    int potri_order = 0;     // SPD inverse, V^T V tiles: 0 = deepest first (ascending tile column), 1 = the symmetric update's order
     int gemm_no_tiles32 = 0;    // option gemm_tiles32=0 (measurements)
     int gemm_queue_test = 0;    // option gemm_queue_test (measurements)
     int xrows_limit = 0;        // option xrows_limit (tests)
@@ -123,6 +125,7 @@ struct lsx_handle_s {
     int gerfs_solves = 0;    // single-right-hand-side estimator solves of the last gerfs
     int getrs_t_path = 0;    // 1 if the last lsx_getrs_t_* call took the blocked sweeps
     int potrs_path = 0;      // 1 if the last lsx_potrs_* call took the few-column step kernels
+    int potri_tiles = 0;     // tiles of the last V^T V product (lsx_potri_*, lsx_lauum_tn_*): t (t + 1) / 2, t = ceil(n / 128)
     int pocon_solves = 0;    // single-right-hand-side solves of the last lsx_pocon_* / lsx_porcond_*
     int porfs_steps = 0;     // most refinement steps any column of the last porfs took
     int porfs_solves = 0;    // single-right-hand-side estimator solves of the last porfs
@@ -136,6 +139,8 @@ struct lsx_handle_s {
     //                             getrs_dev is done with rhs_work before lu_solve_permuted carves tinv; xchg in the launcher
     //   getri_dev                 rhs_work (permutation) and getri_work, across tinv (its own or lu_solve_permuted's)
     //   potrf_dev, potrs_dev      tinv, rhs_work
+    //   potri_dev                 getri_work (V = inv(U^T)), across trtri_upper_t (tinv: block inverses, rhs_work: one
+    //                             128-row strip); getri_dev and potri_dev each lay getri_work out from its start
     //   potrs_few_prepare         tinv, rhs_work, in a PotrsFew that pocon_dev / porfs_dev keep across all their
     //                             potrs_few_apply calls: they call nothing else that grows these two
     //   gecon_dev, pocon_dev      cond, across getrs_dev / getrs_t_dev and potrs_few_*
@@ -321,6 +326,12 @@ template <typename T>
 int launch_syrk_tn_sub(lsx_handle_t h, int n, int k, const T *A, int lda, T *C, int ldc);
 template <typename T>
 int launch_gemm_tn_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C, int ldc);
+// upper triangle of C (n x n) = V^T*V for a lower-triangular V (n x n): tile (I, J) runs over k >= 128 J only, so the
+// blocks of V strictly above its diagonal 128-blocks are never read; nothing below the diagonal of C is read or written.
+// order 0: tiles handed out deepest first, 1: the order of the symmetric update.  descending: every tile takes its
+// k-slabs of 16 from the last one down (k ascending inside a slab) instead of k ascending throughout.  Sets h->potri_tiles.
+template <typename T>
+int launch_lauum_tn(lsx_handle_t h, int n, const T *V, int ldv, T *C, int ldc, int order, bool descending);
 // traced reference-order row reduction (kernels_trace.hip); d_out = {pivots, steps, overflow}
 int launch_rref_trace(lsx_handle_t h, int m, int n, int bar, double *R, int ldr, unsigned char *Tm,
                       int32_t *d_pivots, int32_t *d_steps, int max_steps, double *d_snaps,
@@ -381,8 +392,9 @@ template <typename T>
 int launch_set_identity_perm(lsx_handle_t h, int n, const int32_t *d_perm, T *X, int ldx);
 template <typename T>
 int launch_scatter_cols(lsx_handle_t h, int n, const int32_t *d_perm, const T *S, int lds, T *D, int ldd);
+// d_ipiv == nullptr: no interchanges (a Cholesky factor); square: the (sign, mant, exp2) triple of the product squared
 template <typename T>
-int launch_det(lsx_handle_t h, int n, const T *LU, int lda, const int32_t *d_ipiv, double *d_out);
+int launch_det(lsx_handle_t h, int n, const T *LU, int lda, const int32_t *d_ipiv, double *d_out, bool square = false);
 // scratch of an m x n row reduction: state and two rows (per-column form) or row-group candidates (blocked); the trace's state
 size_t rref_scratch_bytes(int m, int n);
 size_t rref_trace_scratch_bytes();
@@ -471,6 +483,15 @@ template <typename T>
 int launch_chol_diag(lsx_handle_t h, int jb, T *A, int lda, int col0, T *Vinv, int *info);
 template <typename T>
 int launch_chol_inv(lsx_handle_t h, int n, const T *U, int lda, T *inv64, T *inv128);
+// Pieces of the SPD inverse (api.hip, potri_dev).  launch_lower_identity: X[i][j] = (i == j) for j < 128 (i / 128 + 1),
+// the identity on and below the diagonal 128-blocks; the blocks above them are not written.  launch_diag_zero_info:
+// *info = 0, or i + 1 for the first u_ii that is exactly zero or NaN.  launch_symmetrize_upper: a_ji = a_ij for j > i.
+template <typename T>
+int launch_lower_identity(lsx_handle_t h, int n, T *X, int ldx);
+template <typename T>
+int launch_diag_zero_info(lsx_handle_t h, int n, const T *U, int lda, int *info);
+template <typename T>
+int launch_symmetrize_upper(lsx_handle_t h, int n, T *A, int lda);
 // Condition estimate and error bounds of the Cholesky family (kernels_posx.hip); nothing below a diagonal is loaded.
 // launch_resid_bound_sym: launch_resid_bound for a symmetric A given by its upper triangle; launch_lansy: its 1-norm
 // (launch_lange's contract); d_work: resid_bound_sym_work_bytes(n, ncols) bytes, ncols = 1 for the norm.

@@ -228,6 +228,116 @@ int launch_chol_inv(lsx_handle_t h, int n, const T *U, int lda, T *inv64, T *inv
     return LSX_OK;
 }
 
+// ---------------------------------------------------------------- pieces of the SPD inverse (api.hip, potri_dev)
+// The identity on and below the diagonal 128-blocks of X: row i gets columns [0, 128 (i / 128 + 1)), cut at n.  The
+// blocks strictly above the diagonal blocks are not written.
+template <typename T>
+__global__ __launch_bounds__(256) void lower_identity_kernel(int n, T *__restrict__ X, int ldx) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= n || j >= CB * (i / CB + 1)) return;
+    X[(size_t)i * ldx + j] = (i == j) ? T(1) : T(0);
+}
+template <typename T>
+int launch_lower_identity(lsx_handle_t h, int n, T *X, int ldx) {
+    if (n <= 0) return LSX_OK;
+    ProfScope ps(h, LSX_PROF_OTHER);
+    hipLaunchKernelGGL(lower_identity_kernel<T>, dim3((n + 255) / 256, n), dim3(256), 0, h->stream, n, X, ldx);
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
+}
+
+// dtrtri's singularity test on the diagonal of the factor: *info = 0, or i + 1 for the first u_ii that is exactly zero
+// or NaN.  One workgroup.
+template <typename T>
+__global__ __launch_bounds__(256) void diag_zero_info_kernel(int n, const T *__restrict__ U, int lda, int *__restrict__ info) {
+    __shared__ int s_first;
+    if (threadIdx.x == 0) s_first = n;
+    __syncthreads();
+    int first = n;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const T d = U[(size_t)i * lda + i];
+        if (d == T(0) || d != d) { first = i; break; }   // ascending per thread: its first hit is its smallest
+    }
+    if (first < n) atomicMin(&s_first, first);
+    __syncthreads();
+    if (threadIdx.x == 0) *info = s_first < n ? s_first + 1 : 0;
+}
+template <typename T>
+int launch_diag_zero_info(lsx_handle_t h, int n, const T *U, int lda, int *info) {
+    if (n <= 0) return LSX_OK;
+    ProfScope ps(h, LSX_PROF_OTHER);
+    hipLaunchKernelGGL(diag_zero_info_kernel<T>, dim3(1), dim3(256), 0, h->stream, n, U, lda, info);
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
+}
+
+// a_ji = a_ij for j > i: a transpose-copy of 32 x 32 tiles through LDS (padded rows: the transposed reads are
+// conflict-free).  Workgroup (bx, by), bx >= by, reads the tile at rows 32 by, columns 32 bx of the upper triangle and
+// writes its transpose at rows 32 bx, columns 32 by.  VEC: a complete tile off the diagonal of a 16-byte aligned matrix
+// moves in 16-byte pieces on both sides; diagonal tiles (predicate j > i on both sides), edge tiles and unaligned
+// matrices go element by element.  Copies only, so both forms give the same bits.  The diagonal and the upper triangle
+// are not written.
+constexpr int ST = 32;
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void symmetrize_upper_kernel(int n, T *__restrict__ A, int lda) {
+    typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
+    constexpr int W = 16 / (int)sizeof(T);       // elements per 16 bytes
+    constexpr int RP = 256 / (ST / W);           // tile rows per pass of the vector form
+    __shared__ T s[ST][ST + 1];
+    const int bx = blockIdx.x, by = blockIdx.y;
+    if (bx < by) return;
+    const int i0 = by * ST, j0 = bx * ST;
+    const int tid = threadIdx.x;
+    if (VEC && bx > by && j0 + ST <= n) {   // (i0 + ST <= j0: the tile is complete and strictly above the diagonal)
+        const int q = (tid % (ST / W)) * W, r = tid / (ST / W);
+#pragma unroll
+        for (int rr = r; rr < ST; rr += RP) {
+            const vec_t v = *(const vec_t *)(A + (size_t)(i0 + rr) * lda + j0 + q);
+#pragma unroll
+            for (int e = 0; e < W; ++e) s[rr][q + e] = v[e];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int rr = r; rr < ST; rr += RP) {
+            vec_t v;
+#pragma unroll
+            for (int e = 0; e < W; ++e) v[e] = s[q + e][rr];
+            *(vec_t *)(A + (size_t)(j0 + rr) * lda + i0 + q) = v;
+        }
+        return;
+    }
+    const int c = tid & (ST - 1), r = tid >> 5;
+    for (int rr = r; rr < ST; rr += 256 / ST) {
+        const int i = i0 + rr, j = j0 + c;
+        if (i < n && j < n && j > i) s[rr][c] = A[(size_t)i * lda + j];
+    }
+    __syncthreads();
+    for (int rr = r; rr < ST; rr += 256 / ST) {
+        const int j = j0 + rr, i = i0 + c;   // writes a_ji, row j, column i
+        if (i < n && j < n && j > i) A[(size_t)j * lda + i] = s[c][rr];
+    }
+}
+template <typename T>
+int launch_symmetrize_upper(lsx_handle_t h, int n, T *A, int lda) {
+    if (n <= 1) return LSX_OK;
+    ProfScope ps(h, LSX_PROF_OTHER, 0, sizeof(T) * (double)n * n);
+    const int t = (n + ST - 1) / ST;
+    const bool aligned = ((size_t)A % 16 == 0) && (lda % (16 / (int)sizeof(T)) == 0);
+    if (aligned) hipLaunchKernelGGL((symmetrize_upper_kernel<T, true>), dim3(t, t), dim3(256), 0, h->stream, n, A, lda);
+    else hipLaunchKernelGGL((symmetrize_upper_kernel<T, false>), dim3(t, t), dim3(256), 0, h->stream, n, A, lda);
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
+}
+
+#define LSX_POTRI_PIECES(T)                                                  \
+    template int launch_lower_identity<T>(lsx_handle_t, int, T *, int);      \
+    template int launch_diag_zero_info<T>(lsx_handle_t, int, const T *, int, int *); \
+    template int launch_symmetrize_upper<T>(lsx_handle_t, int, T *, int);
+LSX_POTRI_PIECES(double)
+LSX_POTRI_PIECES(float)
+#undef LSX_POTRI_PIECES
+
 template int launch_chol_diag<double>(lsx_handle_t, int, double *, int, int, double *, int *);
 template int launch_chol_diag<float>(lsx_handle_t, int, float *, int, int, float *, int *);
 template int launch_chol_inv<double>(lsx_handle_t, int, const double *, int, double *, double *);

@@ -82,7 +82,10 @@ struct ASlab {
 // are neither loaded nor stored (their accumulators start from zero and are dropped), the others go through exactly the
 // operations of the plain form.  With FULL the k-slabs keep their unpredicated 16-byte loads and only the C traffic
 // goes element by element (a diagonal tile among the complete ones).
-template <typename T, bool FULL, int NWN, int BM_, bool TA = false, bool TRI = false>
+// REV: the k-slabs are taken from the last one down to the first (k ascending inside a slab of BK, a partial last slab
+// comes first): for sums whose dominant terms sit at the smallest k (lauum_tn_kernel below) the small terms are then
+// added up before the large ones.  Every other instantiation keeps the ascending order and its bits.
+template <typename T, bool FULL, int NWN, int BM_, bool TA = false, bool TRI = false, bool REV = false>
 __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__restrict__ A, int lda,
                                               const T *__restrict__ B, int ldb, T *__restrict__ C, int ldc,
                                               int m0, int n0, T (*As)[BK / 2][ASlab<T, BM_>::PAIR], T (*Bs)[BK][BN + LPAD],
@@ -190,7 +193,8 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
 
     // first slab goes out before the C loads so both latencies overlap
     const int nslab = (K + BK - 1) / BK;
-    load_slab(0, ra0, rb0);
+    auto slab_k = [&](int kt) { return (REV ? nslab - 1 - kt : kt) * BK; };
+    load_slab(slab_k(0), ra0, rb0);
 
     // ---- accumulators <- C.  Lane owns columns wn + TN*lc + t (t = N-tile index).
     acc_t acc[SR][TN];
@@ -228,7 +232,7 @@ __device__ __forceinline__ void gemm_sub_tile(int M, int N, int K, const T *__re
     int ticket = 0;
     for (int kt = 0; kt < nslab; ++kt) {
         const int buf = kt & 1;
-        if (kt + 1 < nslab) load_slab((kt + 1) * BK, ra0, rb0);
+        if (kt + 1 < nslab) load_slab(slab_k(kt + 1), ra0, rb0);
         else if (ticket_ctr && tid == 0) ticket = __hip_atomic_fetch_add(ticket_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
         for (int kk = 0; kk < BK; kk += 4) {
@@ -420,6 +424,67 @@ __global__ __launch_bounds__(BM * NWN, (sizeof(T) == 4 && NWN == 4) ? 6 : NWN) v
         tile_n = full;
     }
     gemm_sub_tile<T, false, NWN, BM, true, true>(N, N, K, A, lda, A, lda, C, ldc, tile_m * BM, tile_n * BN, As, Bs, 0);
+}
+
+// Upper triangle of C (N x N) = V^T V for a lower-triangular V stored N x N (LAPACK's lauum for the factor V = inv(U^T) of
+// the SPD inverse: api.hip, potri_dev).  For col >= row, (V^T V)[row][col] = sum over k >= col of v[k][row] v[k][col], so
+// tile (tile_m, tile_n), tile_n >= tile_m, takes k from k0 = 128 tile_n to N - 1 only: both operand pointers are advanced
+// by k0 rows and the tile runs at depth N - k0.  That is a third of the flops of the full depth, and the blocks of V
+// strictly above its diagonal 128-blocks are never read (they may hold anything).  k0 is a multiple of BK, so with
+// N % BK == 0 and aligned operands the interior keeps the unpredicated 16-byte slab loads of the FULL form.  The
+// accumulators start from zero (plus = 3: C = A^T B); the diagonal tiles store under the predicate col >= row, nothing
+// below the diagonal of C is read or written.  k ascending, no split-K, no atomics: an element of the upper triangle
+// has the bits of the full-depth product of the zero-completed V onto zeros, the skipped terms being products with exact
+// zeros added to a zero accumulator.
+// lauum_tile: tile depth falls from N (tile column 0) to at most 128 (the last one), so with order 0 the tiles are handed
+// out deepest first: place p of the sequence is the p-th tile by ascending tile column (column c holds tiles (0..c, c)),
+// and what runs last is shallow.  The XCD-aware placement is kept in chunks: of every 64 consecutive places, the 8
+// workgroups of a chunk that share an XCD (bid % 8) take 8 consecutive ones -- mostly one tile column, whose B operand
+// V[k0:, column block] they then share in that XCD's L2 -- while every XCD still gets every depth (whole-sequence
+// shares per XCD, as upper_tile has them, would give one XCD all the deep tiles).  A last partial chunk is taken as it
+// comes.  order 1: upper_tile's order.
+__device__ __forceinline__ void lauum_tile(int bid, int nwg, int tiles, int order, int &tile_m, int &tile_n) {
+    if (order != 0) {
+        upper_tile(bid, nwg, tiles, tile_m, tile_n);
+        return;
+    }
+    constexpr int CHUNK = 64;
+    int p = bid;
+    if (bid < (nwg / CHUNK) * CHUNK) p = (bid / CHUNK) * CHUNK + (bid & 7) * 8 + ((bid % CHUNK) >> 3);
+    int c = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
+    while (c * (c + 1) / 2 > p) --c;
+    while ((c + 1) * (c + 2) / 2 <= p) ++c;
+    tile_n = c;
+    tile_m = p - c * (c + 1) / 2;
+}
+
+// FULL / not FULL and `tiles` / `full` as gemm_tn_upper_kernel: the interior launch covers the triangle of the complete,
+// aligned tiles, the bounds-checked one everything when full == 0, else the ragged last tile column with its diagonal tile.
+// REV: every tile takes its k-slabs in descending order (gemm_sub_tile): the term k = col, which carries v[col][col] and
+// dominates the sum when V is diagonally dominant, is then added after the tail k > col + 15 instead of before it.
+template <typename T, int NWN, bool FULL, bool REV>
+__global__ __launch_bounds__(BM * NWN, (sizeof(T) == 4 && NWN == 4) ? 6 : NWN) void lauum_tn_kernel(
+    int N, const T *__restrict__ V, int ldv, T *__restrict__ C, int ldc, int tiles, int full, int order) {
+    __shared__ T As[2][BK / 2][ASlab<T, BM>::PAIR];  // AS_AT(buf, k, m) = V[k0 + k][m]
+    __shared__ T Bs[2][BK][BN + LPAD];
+    const int bid = (int)blockIdx.x;
+    int tile_m, tile_n;
+    if (FULL || full == 0) {
+        lauum_tile(bid, (int)gridDim.x, FULL ? full : tiles, order, tile_m, tile_n);
+    } else {   // tiles == full + 1: the last tile column
+        tile_m = bid;
+        tile_n = full;
+    }
+    const int k0 = tile_n * BN;
+    const T *Vk = V + (size_t)k0 * ldv;
+    if (FULL) {
+        if (tile_m == tile_n)
+            gemm_sub_tile<T, true, NWN, BM, true, true, REV>(N, N, N - k0, Vk, ldv, Vk, ldv, C, ldc, tile_m * BM, tile_n * BN, As, Bs, 3);
+        else
+            gemm_sub_tile<T, true, NWN, BM, true, false, REV>(N, N, N - k0, Vk, ldv, Vk, ldv, C, ldc, tile_m * BM, tile_n * BN, As, Bs, 3);
+        return;
+    }
+    gemm_sub_tile<T, false, NWN, BM, true, true, REV>(N, N, N - k0, Vk, ldv, Vk, ldv, C, ldc, tile_m * BM, tile_n * BN, As, Bs, 3);
 }
 
 // The same interior tiles handed out by a work queue instead of one workgroup per tile: the look-ahead driver
@@ -654,6 +719,35 @@ int launch_syrk_tn_sub(lsx_handle_t h, int n, int k, const T *A, int lda, T *C, 
     return LSX_OK;
 }
 
+// upper triangle of C (n x n) = V^T V, V lower triangular n x n: the trapezoid product (lauum_tn_kernel); order as
+// lauum_tile; descending: the k-slabs of every tile from the last down (REV).  One launch when every tile is complete
+// and aligned.
+template <typename T, bool REV>
+static int launch_lauum_tn_rev(lsx_handle_t h, int n, const T *V, int ldv, T *C, int ldc, int order) {
+    h->potri_tiles = 0;
+    if (n <= 0) return LSX_OK;
+    ProfScope ps(h, LSX_PROF_GEMM, (double)n * n * (double)n / 3.0, sizeof(T) * (double)n * n);
+    const int t = (n + BM - 1) / BM;
+    const int elems16 = 16 / (int)sizeof(T);
+    const bool aligned = ((size_t)V % 16 == 0) && ((size_t)C % 16 == 0) && (ldv % elems16 == 0) && (ldc % elems16 == 0) &&
+                         (n % BK == 0);   // every tile's depth n - 128 tile_n is then a multiple of BK
+    const int f = aligned ? n / BM : 0;
+    constexpr int NWN = sizeof(T) == 8 ? 4 : 2;
+    if (f > 0)
+        hipLaunchKernelGGL((lauum_tn_kernel<T, NWN, true, REV>), dim3(f * (f + 1) / 2), dim3(BM * NWN), 0, h->stream, n, V, ldv, C, ldc, t, f, order);
+    const int edge = f == 0 ? t * (t + 1) / 2 : (t > f ? f + 1 : 0);
+    if (edge > 0)
+        hipLaunchKernelGGL((lauum_tn_kernel<T, NWN, false, REV>), dim3(edge), dim3(BM * NWN), 0, h->stream, n, V, ldv, C, ldc, t, f, order);
+    LSX_HIP(hipGetLastError());
+    h->potri_tiles = f * (f + 1) / 2 + edge;
+    return LSX_OK;
+}
+template <typename T>
+int launch_lauum_tn(lsx_handle_t h, int n, const T *V, int ldv, T *C, int ldc, int order, bool descending) {
+    return descending ? launch_lauum_tn_rev<T, true>(h, n, V, ldv, C, ldc, order)
+                      : launch_lauum_tn_rev<T, false>(h, n, V, ldv, C, ldc, order);
+}
+
 template <typename T>
 int launch_gemm_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda, const T *B, int ldb, T *C,
                     int ldc, const GemmPlan &plan, GemmDone *done) {
@@ -668,6 +762,8 @@ template int launch_gemm_tn_acc<double>(lsx_handle_t, int, int, int, int, const 
 template int launch_gemm_tn_acc<float>(lsx_handle_t, int, int, int, int, const float *, int, const float *, int, float *, int, int);
 template int launch_syrk_tn_sub<double>(lsx_handle_t, int, int, const double *, int, double *, int);
 template int launch_syrk_tn_sub<float>(lsx_handle_t, int, int, const float *, int, float *, int);
+template int launch_lauum_tn<double>(lsx_handle_t, int, const double *, int, double *, int, int, bool);
+template int launch_lauum_tn<float>(lsx_handle_t, int, const float *, int, float *, int, int, bool);
 template int launch_gemm_tn_sub<double>(lsx_handle_t, int, int, int, const double *, int, const double *, int, double *, int);
 template int launch_gemm_tn_sub<float>(lsx_handle_t, int, int, int, const float *, int, const float *, int, float *, int);
 template int launch_gemm_sub<double>(lsx_handle_t, int, int, int, const double *, int,

@@ -1053,7 +1053,7 @@ int launch_set_identity_perm(lsx_handle_t h, int n, const int32_t *perm, T *X, i
 // sign also flips once per actual interchange.  One workgroup, tree reduction.
 template <typename T>
 __global__ __launch_bounds__(256) void det_kernel(int n, const T *__restrict__ LU, int lda,
-                                                  const int32_t *__restrict__ ipiv, double *out) {
+                                                  const int32_t *__restrict__ ipiv, double *out, int square) {
     __shared__ double s_m[256];
     __shared__ long long s_e[256];
     __shared__ int s_neg[256];
@@ -1064,7 +1064,7 @@ __global__ __launch_bounds__(256) void det_kernel(int n, const T *__restrict__ L
     int neg = 0, zero = 0;
     for (int k = tid; k < n; k += 256) {
         double d = (double)LU[(size_t)k * lda + k];
-        if (ipiv[k] != k) neg ^= 1;
+        if (ipiv && ipiv[k] != k) neg ^= 1;
         if (d == 0.0) { zero = 1; continue; }
         if (d < 0) { neg ^= 1; d = -d; }
         int ex;
@@ -1090,6 +1090,11 @@ __global__ __launch_bounds__(256) void det_kernel(int n, const T *__restrict__ L
     if (tid == 0) {
         if (s_zero[0]) {
             out[0] = 0.0; out[1] = 0.0; out[2] = 0.0;
+        } else if (square) {   // det(U^T U) = (prod u_ii)^2: the pair squared, renormalised once
+            int ex;
+            out[0] = 1.0;
+            out[1] = frexp(s_m[0] * s_m[0], &ex);
+            out[2] = (double)(2 * s_e[0] + ex);
         } else {
             out[0] = s_neg[0] ? -1.0 : 1.0;
             out[1] = s_m[0];
@@ -1099,9 +1104,9 @@ __global__ __launch_bounds__(256) void det_kernel(int n, const T *__restrict__ L
 }
 
 template <typename T>
-int launch_det(lsx_handle_t h, int n, const T *LU, int lda, const int32_t *d_ipiv, double *d_out) {
+int launch_det(lsx_handle_t h, int n, const T *LU, int lda, const int32_t *d_ipiv, double *d_out, bool square) {
     ProfScope ps(h, LSX_PROF_OTHER);
-    hipLaunchKernelGGL(det_kernel<T>, dim3(1), dim3(256), 0, h->stream, n, LU, lda, d_ipiv, d_out);
+    hipLaunchKernelGGL(det_kernel<T>, dim3(1), dim3(256), 0, h->stream, n, LU, lda, d_ipiv, d_out, square ? 1 : 0);
     LSX_HIP(hipGetLastError());
     return LSX_OK;
 }
@@ -1270,7 +1275,7 @@ int launch_refine_apply(lsx_handle_t h, int n, int nrhs, int init, const float *
                                       int);                                                       \
     template int launch_set_identity_perm<T>(lsx_handle_t, int, const int32_t *, T *, int);       \
     template int launch_scatter_cols<T>(lsx_handle_t, int, const int32_t *, const T *, int, T *, int); \
-    template int launch_det<T>(lsx_handle_t, int, const T *, int, const int32_t *, double *);     \
+    template int launch_det<T>(lsx_handle_t, int, const T *, int, const int32_t *, double *, bool);    \
     template int launch_copy2d<T>(lsx_handle_t, int, int, const T *, int, T *, int);              \
     template int launch_gather_rows<T>(lsx_handle_t, int, int, const int32_t *, const T *, int, T *, int); \
     template int launch_amax<T>(lsx_handle_t, int, int, const T *, int, double *);                \

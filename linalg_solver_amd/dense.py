@@ -86,6 +86,26 @@ def cho_solve(U: np.ndarray, b, handle: Optional[N.Handle] = None) -> np.ndarray
     return X[:, 0].copy() if vec else X
 
 
+def cho_inverse(U: np.ndarray, handle: Optional[N.Handle] = None) -> np.ndarray:
+    """inv(A) from the factor of cho_factor (lsx_potri_*: inv(A) = V^T V with V = inv(U^T), n^3 flops with the
+    factorisation, no pivoting).  Only the upper triangle of U is used.  Returns the full inverse, both triangles,
+    exactly symmetric.  A zero or NaN u_ii raises ValueError (cho_factor's info says so beforehand)."""
+    U = np.asarray(U)
+    if U.ndim != 2 or U.shape[0] != U.shape[1]:
+        raise ValueError("cho_inverse needs the square factor matrix")
+    ct, sfx = _ct(U.dtype)
+    n = U.shape[0]
+    h = _h(handle)
+    X = np.array(U, dtype=U.dtype, order="C", copy=True)
+    info = C.c_int(0)
+    if n:
+        N.check(getattr(h.lib, f"lsx_potri_{sfx}")(h.ptr, n, _ptr(X, ct), n, C.byref(info)), f"lsx_potri_{sfx}")
+    if info.value != 0:
+        raise ValueError(f"cho_inverse: u[{info.value - 1}, {info.value - 1}] is zero or NaN, the factor has no inverse")
+    X = np.triu(X)
+    return X + np.triu(X, 1).T
+
+
 def _norm_code(which) -> int:
     """1 / "1" / "one" -> the 1-norm (max column sum); inf / "inf" / "I" -> the infinity-norm (max row sum)."""
     if which in (1, "1", "one", "O", "o"):
@@ -497,8 +517,12 @@ def solve_refined(a, b, sweeps: int = 3, handle: Optional[N.Handle] = None):
     return (X[:, 0].copy() if vec else X), 0, ratio.value, corr.value
 
 
-def inv(a, handle: Optional[N.Handle] = None, dtype=np.float64):
-    """Returns (inverse or None, info, pivot_ratio)."""
+def inv(a, handle: Optional[N.Handle] = None, dtype=np.float64, assume_pos: bool = False):
+    """Returns (inverse or None, info, pivot_ratio).
+    assume_pos=True: A is symmetric positive definite and goes through the Cholesky factorisation and LAPACK's potri
+    (lsx_poinv_*: n^3 flops instead of 2 n^3, no pivoting).  Only the upper triangle of a is used and symmetry is not
+    checked; the inverse comes back with both triangles, exactly symmetric; info = j + 1 says the leading minor of order
+    j + 1 is not positive definite; pivot_ratio is 1.0 (nothing is pivoted), as solve(assume_pos=True) returns it."""
     h = _h(handle)
     ct, sfx = _ct(dtype)
     A = np.ascontiguousarray(a, dtype=dtype)
@@ -506,6 +530,14 @@ def inv(a, handle: Optional[N.Handle] = None, dtype=np.float64):
     if A.ndim != 2 or A.shape[1] != n:
         raise ValueError("inv needs a square matrix")
     out = np.empty_like(A)
+    if assume_pos:
+        pinfo = C.c_int(0)
+        if n:
+            N.check(getattr(h.lib, f"lsx_poinv_{sfx}")(h.ptr, n, _ptr(A, ct), n, _ptr(out, ct), n, C.byref(pinfo)),
+                    f"lsx_poinv_{sfx}")
+        if pinfo.value != 0:
+            return None, pinfo.value, 1.0
+        return out, 0, 1.0
     info, ratio = C.c_int(0), C.c_double(1.0)
     N.check(getattr(h.lib, f"lsx_getri_{sfx}")(h.ptr, n, _ptr(A, ct), n, _ptr(out, ct), n, C.byref(info),
                                                 C.byref(ratio)), f"lsx_getri_{sfx}")
@@ -514,8 +546,32 @@ def inv(a, handle: Optional[N.Handle] = None, dtype=np.float64):
     return out, 0, ratio.value
 
 
-def det_parts(a, handle: Optional[N.Handle] = None, dtype=np.float64) -> Tuple[float, float, int]:
-    """det(A) = sign * mant * 2**exp2 with mant in [0.5, 1) (sign 0 for a singular matrix)."""
+def det_parts_pos(a, handle: Optional[N.Handle] = None, dtype=np.float64) -> Tuple[float, float, int, int]:
+    """(sign, mant, exp2, info) of det(A) = prod u_ii^2 from the Cholesky factor of a symmetric positive definite matrix
+    (lsx_podet_*).  Only the upper triangle of a is used; info = j + 1 says the leading minor of order j + 1 is not
+    positive definite, the three parts are 0 then."""
+    h = _h(handle)
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    n = A.shape[0]
+    if A.ndim != 2 or A.shape[1] != n:
+        raise ValueError("det needs a square matrix")
+    s, m, e, info = C.c_double(0), C.c_double(0), C.c_int64(0), C.c_int(0)
+    N.check(getattr(h.lib, f"lsx_podet_{sfx}")(h.ptr, n, _ptr(A, ct), n, C.byref(s), C.byref(m), C.byref(e),
+                                                C.byref(info)), f"lsx_podet_{sfx}")
+    return s.value, m.value, int(e.value), info.value
+
+
+def det_parts(a, handle: Optional[N.Handle] = None, dtype=np.float64, assume_pos: bool = False) -> Tuple[float, float, int]:
+    """det(A) = sign * mant * 2**exp2 with mant in [0.5, 1) (sign 0 for a singular matrix).
+    assume_pos=True: A is symmetric positive definite and the determinant comes from its Cholesky factor
+    (det_parts_pos); a matrix that is not positive definite raises ValueError."""
+    if assume_pos:
+        s, m, e, info = det_parts_pos(a, handle, dtype)
+        if info != 0:
+            raise ValueError(f"matrix is not positive definite: its leading minor of order {info} is not "
+                             "(assume_pos=True asserts a symmetric positive definite matrix)")
+        return s, m, e
     h = _h(handle)
     ct, sfx = _ct(dtype)
     A = np.ascontiguousarray(a, dtype=dtype)
@@ -527,15 +583,15 @@ def det_parts(a, handle: Optional[N.Handle] = None, dtype=np.float64) -> Tuple[f
     return s.value, m.value, int(e.value)
 
 
-def slogdet(a, handle: Optional[N.Handle] = None, dtype=np.float64) -> Tuple[float, float]:
-    s, m, e = det_parts(a, handle, dtype)
+def slogdet(a, handle: Optional[N.Handle] = None, dtype=np.float64, assume_pos: bool = False) -> Tuple[float, float]:
+    s, m, e = det_parts(a, handle, dtype, assume_pos)
     if s == 0.0:
         return 0.0, -math.inf
     return s, math.log(m) + e * math.log(2.0)
 
 
-def det(a, handle: Optional[N.Handle] = None) -> float:
-    s, m, e = det_parts(a, handle)
+def det(a, handle: Optional[N.Handle] = None, assume_pos: bool = False) -> float:
+    s, m, e = det_parts(a, handle, assume_pos=assume_pos)
     if s == 0.0:
         return 0.0
     try:

@@ -120,6 +120,66 @@ class DeviceSolver:
                                         max(C.stride(0), 1)), name)
         return C
 
+    def _square(self, A: torch.Tensor, what: str) -> int:
+        _rowmajor(A, what)
+        if A.shape[0] != A.shape[1]:
+            raise ValueError(f"{what} needs a square matrix")
+        return A.shape[0]
+
+    def potri_(self, U: torch.Tensor, info: Optional[torch.Tensor] = None):
+        """In place: the upper triangle of the factor of potrf_ becomes the upper triangle of inv(A) (LAPACK's potri,
+        lsx_potri_*_dev); the strictly lower triangle is neither read nor written.  Returns info (int32[1] device
+        tensor: 0, or i + 1 for the first u_ii that is zero or NaN); no host sync."""
+        n = self._square(U, "potri_")
+        if info is None:
+            info = torch.zeros(1, dtype=torch.int32, device=U.device)
+        elif info.dtype != torch.int32 or info.device != U.device or info.numel() < 1 or not info.is_contiguous():
+            raise ValueError("potri_: info must be a contiguous int32 tensor with at least one entry on U's device")
+        name = f"lsx_potri_{self._suffix(U)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, n, U.data_ptr(), max(U.stride(0), 1), info.data_ptr()), name)
+        return info
+
+    def symmetrize_upper_(self, A: torch.Tensor):
+        """a_ji = a_ij for every j > i, in place (lsx_symmetrize_upper_*_dev)."""
+        n = self._square(A, "symmetrize_upper_")
+        name = f"lsx_symmetrize_upper_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, n, A.data_ptr(), max(A.stride(0), 1)), name)
+        return A
+
+    def lauum_tn_(self, C: torch.Tensor, V: torch.Tensor):
+        """Upper triangle of C (n x n) = V.T @ V for a lower-triangular V; the blocks of V strictly above its diagonal
+        128-blocks are never read, the strictly lower triangle of C is untouched (lsx_lauum_tn_*_dev)."""
+        n = self._square(V, "lauum_tn_ V")
+        if self._square(C, "lauum_tn_ C") != n:
+            raise ValueError("lauum_tn_: need V (n x n) and C (n x n)")
+        if V.dtype != C.dtype:
+            raise TypeError("lauum_tn_: both operands must have the same dtype")
+        name = f"lsx_lauum_tn_{self._suffix(C)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, n, V.data_ptr(), max(V.stride(0), 1), C.data_ptr(),
+                                        max(C.stride(0), 1)), name)
+        return C
+
+    def trtri_upper_t_(self, V: torch.Tensor, U: torch.Tensor):
+        """V = inv(U^T) on and below the diagonal 128-blocks of V, from the upper triangle of U; the blocks of V strictly
+        above its diagonal blocks are not written (lsx_trtri_upper_t_*_dev)."""
+        n = self._square(U, "trtri_upper_t_ U")
+        if self._square(V, "trtri_upper_t_ V") != n:
+            raise ValueError("trtri_upper_t_: need U (n x n) and V (n x n)")
+        if V.dtype != U.dtype:
+            raise TypeError("trtri_upper_t_: both operands must have the same dtype")
+        name = f"lsx_trtri_upper_t_{self._suffix(U)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, n, U.data_ptr(), max(U.stride(0), 1), V.data_ptr(),
+                                        max(V.stride(0), 1)), name)
+        return V
+
+    def podet_parts(self, U: torch.Tensor) -> torch.Tensor:
+        """Device tensor [sign, mant, exp2] of det(A) = prod u_ii^2 from the factor of potrf_ (lsx_podet_*_dev)."""
+        n = self._square(U, "podet_parts")
+        out = torch.empty(3, dtype=torch.float64, device=U.device)
+        name = f"lsx_podet_{self._suffix(U)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, n, U.data_ptr(), max(U.stride(0), 1), out.data_ptr()), name)
+        return out
+
     @staticmethod
     def _norm_code(which) -> int:
         if which in (1, "1", "one", "O", "o"):

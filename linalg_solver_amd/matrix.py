@@ -635,7 +635,41 @@ class Matrix:
         r = self.rcond(norm, equilibrate)
         return float("inf") if r == 0.0 else 1.0 / r
 
-    def inverse_array(self) -> "np.ndarray | Matrix.NoSolution":
+    def _inverse_pos_def(self):
+        """inverse_array(pos_def=True): Cholesky factorisation and LAPACK's potri (lsx_potrf_* / lsx_potri_*,
+        lsx_poinv_*), mirrored into both triangles."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            n = A.shape[0]
+            if A.shape[1] != n:
+                raise ValueError("Matrix must be square to invert.")
+            dev = DeviceSolver(self._dev.device.index)
+            X = A.clone()
+            info = int(dev.potrf_(X).item()) if n else 0
+            if info != 0:
+                raise self._not_pos_def(info)
+            if n:
+                dev.potri_(X)
+                dev.symmetrize_upper_(X)
+            return X
+        A = self._array()
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("Matrix must be square to invert.")
+        X, info, _ = dense.inv(A, assume_pos=True)
+        if info != 0:
+            raise self._not_pos_def(info)
+        return X
+
+    def inverse_array(self, pos_def: bool = False) -> "np.ndarray | Matrix.NoSolution":
+        """The inverse as an array (a device tensor for a matrix built from one), or NoSolution for a singular matrix.
+        pos_def=True asserts that self is symmetric positive definite and takes the Cholesky route (no pivoting, half
+        the work of the LU route); only the upper triangle of self is used, the result has both triangles, exactly
+        symmetric.  If a leading minor is not positive definite the call raises ValueError, as solve_array(pos_def=True)
+        does."""
+        if pos_def:
+            return self._inverse_pos_def()
         if getattr(self, "_dev", None) is not None and self._items is None:
             if self._dev.shape[0] != self._dev.shape[1]:
                 raise ValueError("Matrix must be square to invert.")
@@ -910,10 +944,17 @@ class Matrix:
             return self.items[0][0]  # :200-201
         return dense.det(self._array())
 
-    def slogdet(self) -> Tuple[float, float]:
-        """(sign, log|det|): the overflow-free form of determinant() (new API)."""
+    def slogdet(self, pos_def: bool = False) -> Tuple[float, float]:
+        """(sign, log|det|): the overflow-free form of determinant() (new API).
+        pos_def=True asserts that self is symmetric positive definite: det = prod u_ii^2 from the Cholesky factor
+        (lsx_podet_*), ValueError if a leading minor is not positive definite."""
         if self.rows != self.cols:
             raise ValueError("Determinant requires a square matrix")
+        if pos_def:
+            s, m, e, info = dense.det_parts_pos(self._array())
+            if info != 0:
+                raise self._not_pos_def(info)
+            return s, math.log(m) + e * math.log(2.0)
         return dense.slogdet(self._array())
 
     def rank(self) -> int:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | posx | gecon | gerfs | equil [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | potri | posx | gecon | gerfs | equil [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -465,6 +465,62 @@ def main():
                       f"({split['gemm']['ms'] / tot * 100:.0f} % of the bracketed time, "
                       f"{split['gemm']['flops'] / max(split['gemm']['ms'], 1e-9) / 1e9:.1f} TFLOP/s)", flush=True)
                 del A, A0
+    if "potri" in args.what:
+        # The SPD inverse beside the LU inverse of the SAME matrix G G^T / n + I, one process: potrf + potri against
+        # getrf + getri, medians of two alternating rounds with the restoring copy timed on its own and subtracted;
+        # then the trapezoid product V^T V alone in both tile orders (0: deepest first, 1: the symmetric update's).
+        for dt in (torch.float64, torch.float32):
+            for n in (2048, 4096, 8192):
+                G = torch.empty(n, n, dtype=dt, device="cuda")
+                dev.fill_(G, gen.U11, 1)
+                A0 = G @ G.t() / n + torch.eye(n, dtype=dt, device="cuda")   # plumbing: builds the input only
+                del G
+                A = A0.clone()
+                Inv = torch.empty_like(A)
+                ipiv = torch.empty(n, dtype=torch.int32, device="cuda")
+                info = torch.zeros(1, dtype=torch.int32, device="cuda")
+                res = {}
+                for rnd in range(2):
+                    t_copy = timeit(lambda: A.copy_(A0), reps=5, warm=2)[1]
+
+                    def chol():
+                        A.copy_(A0)
+                        dev.potrf_(A, info)
+                        dev.potri_(A, info)
+
+                    def chol_f():
+                        A.copy_(A0)
+                        dev.potrf_(A, info)
+
+                    def lu():
+                        A.copy_(A0)
+                        dev.getrf_(A, ipiv, info)
+                        dev.getri(A, ipiv, Inv)
+                    for name, fn in (("potrf+potri", chol), ("potrf", chol_f), ("getrf+getri", lu)):
+                        res.setdefault(name, []).append(timeit(fn, reps=5, warm=2)[1] - t_copy)
+                        assert int(info.item()) == 0, (name, int(info.item()))
+                pi, pf, gi = (min(res[k]) for k in ("potrf+potri", "potrf", "getrf+getri"))
+                print(f"potri {str(dt)[6:]} n={n}: potrf+potri {pi:.3f} ms ({n ** 3 / pi / 1e9:.1f} TFLOP/s of n^3; potrf {pf:.3f}, "
+                      f"potri {pi - pf:.3f})  getrf+getri {gi:.3f} ms  | Cholesky/LU {pi / gi:.3f}  (rounds: "
+                      f"{res['potrf+potri'][0]:.3f}/{res['potrf+potri'][1]:.3f} against {res['getrf+getri'][0]:.3f}/"
+                      f"{res['getrf+getri'][1]:.3f}; copy {t_copy:.3f})", flush=True)
+                V = torch.tril(A0)                      # any lower-triangular operand times the same
+                Cm = torch.zeros_like(A0)
+                t_ord = {}
+                dev.h.set_option("lauum_descending", 1)      # the k-slab order potri runs
+                for rnd in range(2):
+                    for order in (0, 1):
+                        dev.h.set_option("potri_order", order)
+                        t_ord.setdefault(order, []).append(timeit(lambda: dev.lauum_tn_(Cm, V), reps=7, warm=2)[1])
+                dev.h.set_option("potri_order", 0)
+                dev.h.set_option("lauum_descending", 0)
+                t_asc = timeit(lambda: dev.lauum_tn_(Cm, V), reps=7, warm=2)[1]
+                t0, t1 = min(t_ord[0]), min(t_ord[1])
+                print(f"    V^T V alone, {dev.h.get_option('potri_tiles')} tiles: deepest first {t0:.3f} ms ({n ** 3 / 3 / t0 / 1e9:.1f} "
+                      f"TFLOP/s of n^3/3)  update order {t1:.3f} ms  | deepest/update {t0 / t1:.3f}  (rounds: "
+                      f"{t_ord[0][0]:.3f}/{t_ord[0][1]:.3f} against {t_ord[1][0]:.3f}/{t_ord[1][1]:.3f}; k ascending, deepest first: "
+                      f"{t_asc:.3f} ms)", flush=True)
+                del A, A0, Inv, V, Cm
     if "posx" in args.what:
         # Condition estimate and error bounds of the Cholesky family beside their LU counterparts on the SAME matrix
         # G G^T / n + I, one process, medians of 7 after warm-up:
