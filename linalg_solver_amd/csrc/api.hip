@@ -129,6 +129,32 @@ struct JoinSide {
     }
 };
 
+// The panel settings of the shared-CU schedule for panels of up to m rows; hybrid: as the phase in front of
+// getrf_lookahead_x.  One function for the driver and for ensure_getrf_workspace, which sizes the driver's areas.
+static PanelArgs shared_cu_panel(PanelArgs pa, size_t elem, bool hybrid, int m) {
+    // this schedule shares the CUs between the panel and the update: the XCD-scope panel (which fills an XCD) has
+    // its own driver, getrf_lookahead_x; here it would stall every launch beside it
+    if (pa.mode == 4) pa.mode = 3;
+    // Panels taller than one XCD holds (the phase in front of getrf_lookahead_x): 256-row slices, i.e. half as many
+    // workgroups of the device-scope panel.  Its time per column does not depend on the slicing (2.5-2.6 us, kbench
+    // panel3tall), but every CU it holds is one the update -- the bottleneck of this phase -- does not have:
+    // 16384^2 fp64 77.8 -> 74.6 ms, 12288^2 38.5 -> 37.9 ms, same bits (tools/lu_tall.py).
+    if (elem == 8 && hybrid && pa.nt == 0 && m > 8192) { pa.nt = 512; pa.rt = 8; }
+    return pa;
+}
+// Scratch of the shared-CU driver (pa: shared_cu_panel's).  Two exchange areas of the pipelined panel, used alternately
+// and cleared by the DRIVER on the main stream as soon as their panel has finished -- a clear in front of every panel
+// launch sits on the chain (area = 0: no such area, every launch clears its own); then the counted first tile columns' words.
+struct SharedCuScratch {
+    size_t area = 0; char *areas = nullptr; int *c0words = nullptr;
+    void lay(Carver &c, lsx_handle_t h, const PanelArgs &pa, int m, int nwords) {
+        area = panel_pipe_area_bytes(h, pa.mode, pa.nt, pa.rt, m);
+        if (!area) return;
+        areas = c.take<char>(2 * area);
+        if (nwords) c0words = c.take<int>(nwords);
+    }
+};
+
 // k0 = first column handled here (columns < k0 were factored by the sequential driver).  k_stop > 0: stop in
 // front of the panel that starts at column k_stop (trailing matrix fully updated, that panel not yet factored):
 // the XCD-scope driver takes over from there.
@@ -140,32 +166,21 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
     JoinSide join{h, side, main_s, main_s};
     GemmPlan mfma;   // every update of an LU: see GemmPlan
     mfma.mfma_only = true;
-    // this schedule shares the CUs between the panel and the update: the XCD-scope panel (which fills an XCD) has
-    // its own driver, getrf_lookahead_x; here it would stall every launch beside it
-    if (pa.mode == 4) pa.mode = 3;
-    // Panels taller than one XCD holds (the phase in front of getrf_lookahead_x): 256-row slices, i.e. half as many
-    // workgroups of the device-scope panel.  Its time per column does not depend on the slicing (2.5-2.6 us, kbench
-    // panel3tall), but every CU it holds is one the update -- the bottleneck of this phase -- does not have:
-    // 16384^2 fp64 77.8 -> 74.6 ms, 12288^2 38.5 -> 37.9 ms, same bits (tools/lu_tall.py).
-    if (sizeof(T) == 8 && k_stop > 0 && pa.nt == 0 && n - k0 > 8192) { pa.nt = 512; pa.rt = 8; }
-    // Exchange areas of the pipelined panel: two, used alternately, and cleared HERE on the main stream as
-    // soon as their panel has finished -- a clear in front of every panel launch sits on the chain.
-    size_t area = panel_pipe_area_bytes(h, pa.mode, pa.nt, pa.rt, n - k0);
-    if (2 * area > h->scratch.bytes) area = 0;
-    if (area) LSX_HIP(hipMemsetAsync(h->scratch.p, 0, 2 * area, main_s));
+    pa = shared_cu_panel(pa, sizeof(T), k_stop > 0, n - k0);
     // Counted first tile column of the big update (fp64, this driver as the phase in front of getrf_lookahead_x): the
     // chain of step k then waits, inside its first kernel, for update k-1 on the NEXT panel's columns only and runs
     // beside the rest of that update -- the update of step k follows update k-1 without the chain in between
     // (16384^2: the chain was ~45 us of every one of the 64 steps of this phase).
     const int nst = (n - k0 + nb - 1) / nb;
-    int *c0words = nullptr;
-    if (sizeof(T) == 8 && k_stop > 0 && area && 2 * area + pad256((size_t)nst * sizeof(int)) <= h->scratch.bytes && !h->x_events) {
-        c0words = (int *)((char *)h->scratch.p + 2 * area);
-        LSX_HIP(hipMemsetAsync(c0words, 0, (size_t)nst * sizeof(int), main_s));
-    }
+    SharedCuScratch ws;   // inside the scratch that came with pa
+    const int nwords = sizeof(T) == 8 && k_stop > 0 && !h->x_events ? nst : 0;
+    LSX_TRY(carve_in(pa.area, pa.area_bytes, "getrf_lookahead", [&](Carver &c) { ws.lay(c, h, pa, n - k0, nwords); }));
+    const size_t area = ws.area; int *const c0words = ws.c0words;
+    if (area) LSX_HIP(hipMemsetAsync(ws.areas, 0, 2 * area, main_s));
+    if (c0words) LSX_HIP(hipMemsetAsync(c0words, 0, (size_t)nst * sizeof(int), main_s));
     bool prev_counted = false;
     int prev_tiles = 0;
-    pa.area_bytes = area;
+    pa.cleared = area > 0;
     // the side stream starts after everything already queued on the main stream (info memset, fills)
     LSX_HIP(hipEventRecord(h->ev_start, main_s));
     LSX_HIP(hipStreamWaitEvent(side, h->ev_start, 0));
@@ -187,7 +202,7 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
         OnStream g(h, side);
         const int jb0 = (n - k0) < nb ? (n - k0) : nb;
         pa.list = h->moves_buf[0];
-        pa.area_off = 0;
+        if (area) pa.area = ws.areas, pa.area_bytes = area;
         LSX_TRY(launch_panel<T>(h, n - k0, jb0, A + (size_t)k0 * lda + k0, lda, k0, d_ipiv + k0, d_info, pa));
     }
     bool listed = pa.listed;    // panel k came with a gather list
@@ -241,14 +256,14 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
             // left-hand interchanges (with the counted column the chain above no longer waited for them)
             if (have_update && prev_counted) LSX_HIP(hipStreamWaitEvent(side, h->ev_next, 0));
             pa.list = h->moves_buf[(step + 1) & 1];
-            pa.area_off = (size_t)((step + 1) & 1) * area;
+            if (area) pa.area = ws.areas + (size_t)((step + 1) & 1) * area;
             LSX_TRY(launch_panel<T>(h, rest, jb2, A22, lda, k + jb, d_ipiv + k + jb, d_info, pa));
         }
         LSX_HIP(hipStreamWaitEvent(main_s, h->ev_panel, 0));
         bool cur_counted = false;
         int cur_tiles = 0;
         // panel k is done with its exchange area; panel k+2 reuses it, behind ev_next below
-        if (area) LSX_HIP(hipMemsetAsync((char *)h->scratch.p + (size_t)(step & 1) * area, 0, area, main_s));
+        if (area) LSX_HIP(hipMemsetAsync(ws.areas + (size_t)(step & 1) * area, 0, area, main_s));
         if (rest > jb2) {
             LSX_TRY(apply_panel_swaps<T>(h, mv, rest - jb2, A + k + jb + jb2, lda, k, jb, d_ipiv + k));
             LSX_TRY(launch_trsm_block<T>(h, 1, jb, rest - jb2, Akk, lda, Ti, A12 + jb2, lda));
@@ -273,6 +288,22 @@ static int getrf_lookahead(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv
     return LSX_OK;
 }
 
+// Scratch of getrf_lookahead_x: three exchange areas of the XCD panel in rotation (panel j uses area j % 3, cleared behind
+// update j; each launch needs its area all zero), sized for the tallest panel; then the words the kernels count in (one memset).
+struct XcdScratch {
+    size_t area = 0; char *areas = nullptr;
+    int *xcc_word = nullptr, *pass = nullptr, *counters = nullptr, *col0 = nullptr, *ready = nullptr;
+    void lay(Carver &c, lsx_handle_t h, const PanelArgs &pa, int m, size_t elem, int nsteps) {
+        area = panel_x_area_bytes(h, pa.mode, m, elem);
+        if (!area) return;
+        areas = c.take<char>(3 * area);
+        xcc_word = c.take<int>(1);                    // 1 + XCC id of the panel's XCD (blocks = 0 mod 8 land on XCC 0)
+        pass = c.take<int>(nsteps);                   // per step: update workgroups that left the panel's XCD
+        counters = c.take<int>(8 * (size_t)nsteps);   // per step: the update's eight strip queues
+        col0 = c.take<int>(2 * (size_t)nsteps);       // per step: {ticket, finished tiles} of the update's tile column 0
+        ready = c.take<int>(nsteps);                  // per step: block inverses finished (fused chain launch)
+    }
+};
 // ---------------------------------------------------------------- look-ahead LU driver, XCD-scope panel
 // The panel of step k+1 (kernels_panel_x.hip) fills every CU of ONE XCD while it runs, and the hardware deals an
 // eighth of EVERY kernel's workgroups to that XCD whatever the stream or CU mask (measured: lsx_diag_cu_mask_probe),
@@ -293,25 +324,17 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
     hipStream_t main_s = h->stream, side = h->side_stream;
     GemmPlan mfma;   // every update of an LU: see GemmPlan
     mfma.mfma_only = true;
-    // exchange area of the XCD panel (kernels_panel_x.hip) sized for the tallest panel; each launch needs it all zero
-    const size_t area_x = panel_x_area_bytes(h, pa.mode, n - k0, sizeof(T));
-    const size_t pass_bytes = pad256(256 + (size_t)nsteps * sizeof(int)), ctr_bytes = pad256((size_t)nsteps * 8 * sizeof(int));
-    const size_t col0_bytes = pad256((size_t)nsteps * 2 * sizeof(int));
-    const size_t words = pass_bytes + ctr_bytes + col0_bytes + pad256((size_t)nsteps * sizeof(int));
-    if (area_x == 0 || 3 * area_x + words > h->scratch.bytes) { set_error("getrf_lookahead_x: scratch"); return LSX_ERR_INTERNAL; }
+    XcdScratch ws;   // inside the scratch that came with pa
+    LSX_TRY(carve_in(pa.area, pa.area_bytes, "getrf_lookahead_x", [&](Carver &c) { ws.lay(c, h, pa, n - k0, sizeof(T), nsteps); }));
+    const size_t area_x = ws.area;
+    if (area_x == 0) { set_error("getrf_lookahead_x: panel settings without an exchange area"); return LSX_ERR_INTERNAL; }
     LSX_TRY(reserve(h, h->moves_all, (size_t)nsteps * 2048));
     JoinSide join{h, side, main_s, main_s};
-    // three exchange areas in rotation (panel j uses area j % 3, cleared behind update j), then the words
-    char *wbase = (char *)h->scratch.p + 3 * area_x;
-    int *xcc_word = (int *)wbase;                    // 1 + XCC id of the panel's XCD (blocks = 0 mod 8 land on XCC 0)
-    int *pass = (int *)(wbase + 256);                // per step: update workgroups that left the panel's XCD
-    int *counters = (int *)(wbase + pass_bytes);     // per step: the update's eight strip queues
-    int *col0 = (int *)(wbase + pass_bytes + ctr_bytes);   // per step: {ticket, finished tiles} of the update's tile column 0
-    int *ready = (int *)(wbase + pass_bytes + ctr_bytes + col0_bytes);   // per step: block inverses finished (fused chain launch)
-    for (int s = 0; s < 3; ++s) LSX_HIP(hipMemsetAsync((char *)h->scratch.p + (size_t)s * area_x, 0, area_x, main_s));
-    LSX_HIP(hipMemsetAsync(wbase, 0, words, main_s));
+    int *const xcc_word = ws.xcc_word, *const pass = ws.pass, *const counters = ws.counters, *const col0 = ws.col0, *const ready = ws.ready;
+    for (int s = 0; s < 3; ++s) LSX_HIP(hipMemsetAsync(ws.areas + (size_t)s * area_x, 0, area_x, main_s));
+    LSX_HIP(hipMemsetAsync(xcc_word, 0, (char *)(ready + nsteps) - (char *)xcc_word, main_s));
     LSX_HIP(hipMemsetD32Async((hipDeviceptr_t)xcc_word, 1, 1, main_s));
-    pa.area_bytes = area_x;
+    pa.area_bytes = area_x, pa.cleared = true;
     pa.xcc_word = xcc_word;
     LSX_HIP(hipEventRecord(h->ev_start, main_s));
     LSX_HIP(hipStreamWaitEvent(side, h->ev_start, 0));
@@ -320,7 +343,7 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
     {
         OnStream g(h, side);
         pa.list = list(0);
-        pa.area_off = 0;
+        pa.area = ws.areas;
         LSX_TRY(launch_panel<T>(h, n - k0, (n - k0) < nb ? (n - k0) : nb, A + (size_t)k0 * lda + k0, lda, k0, d_ipiv + k0, d_info, pa));
         if (!pa.listed) { set_error("getrf_lookahead_x: panel without a gather list"); return LSX_ERR_INTERNAL; }
     }
@@ -401,7 +424,7 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
         const bool cur_col0 = did.queued && did.col0_complete;
         // panel k is done with its exchange area and panel k+3 reuses it: cleared behind the update, off the path
         // HEAD -> update start -> panel k+1; the chain of panel k+3 waits for (a part of) update k+1, behind this
-        LSX_HIP(hipMemsetAsync((char *)h->scratch.p + (size_t)(step % 3) * area_x, 0, area_x, main_s));
+        LSX_HIP(hipMemsetAsync(ws.areas + (size_t)(step % 3) * area_x, 0, area_x, main_s));
         LSX_HIP(hipEventRecord(h->ev_next, main_s));
         // panel k's interchanges on the columns LEFT of it: behind the update, where this stream only waits for the next
         // HEAD (one launch for all panels at the very end was 0.3 ms of an 8192^2 factorisation, on the critical path).
@@ -426,7 +449,7 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
             const bool tall = (rest > 6400 && (sizeof(T) == 8 || rest <= 8192)) || rest > 12800;
             if (did.queued && (!cur_col0 || tall)) LSX_TRY(launch_gate(h, pass + step, 2 * h->num_cu / 8));
             pa.list = list(step + 1);
-            pa.area_off = (size_t)((step + 1) % 3) * area_x;
+            pa.area = ws.areas + (size_t)((step + 1) % 3) * area_x;
             LSX_TRY(launch_panel<T>(h, rest, jb2, A22, lda, k + jb, d_ipiv + k + jb, d_info, pa));
             if (!pa.listed) { set_error("getrf_lookahead_x: panel without a gather list"); return LSX_ERR_INTERNAL; }
         }
@@ -441,14 +464,19 @@ static int getrf_lookahead_x(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ip
     return launch_laswp_left_all<T>(h, A, lda, k0 + left_done * nb, nb, nsteps - left_done, list(left_done));
 }
 
-// Workspaces of one factorisation of order n: scratch and tinv (block inverses, two sets: the look-ahead driver
-// alternates).  One computation for getrf_dev and the multi-device driver (mg.hip), so the two cannot drift apart.
+// Workspaces of one factorisation of order n, sized before its first launch: tinv (block inverses, two sets: the
+// look-ahead driver alternates) and scratch, which every stage lays out from its start -- so scratch is the LARGEST of
+// the layouts that can run for this n, element size and options, each counted by the code that places it: a panel that clears
+// its own area (sequential driver, mg.hip, first-rule row reduction) and the two look-ahead drivers from column 0 (a later start
+// needs no more).  Nothing reserves scratch again until the factorisation is queued; a PanelArgs is made after this.  mg.hip sizes here too.
 int ensure_getrf_workspace(lsx_handle_t h, int n, size_t elem) {
-    const size_t panel = panel_scratch_bytes(n);                                  // a panel launch that clears its own area
-    const size_t row_bufs = 2 * pad256(elem * 2 * (size_t)n);                      // two buffers of 2 n elements
-    const size_t xcd_areas = 3 * panel_x_area_bytes(h, h->panel_mode, n, elem);    // getrf_lookahead_x rotates three
-    const size_t driver_words = 16384 + ((size_t)n / 16 + 2) * 40;                 // its per-step counters and flags
-    LSX_TRY(reserve(h, h->scratch, panel + row_bufs + xcd_areas + driver_words));
+    const PanelArgs pa(h, nullptr);
+    const int nsteps = (n + h->nb - 1) / h->nb;
+    size_t need = panel_scratch_bytes(h, pa.mode, pa.nt, pa.rt, n, elem);
+    for (const bool hybrid : {false, true})
+        need = std::max(need, carve_bytes([&](Carver &c) { SharedCuScratch().lay(c, h, shared_cu_panel(pa, elem, hybrid, n), n, nsteps); }));
+    need = std::max(need, carve_bytes([&](Carver &c) { XcdScratch().lay(c, h, pa, n, elem, nsteps); }));
+    LSX_TRY(reserve(h, h->scratch, need));
     const size_t tinv_elems = (size_t)((h->nb * h->kblock + 63) / 64) * 64 * 64;
     return reserve(h, h->tinv, 2 * pad256(tinv_elems * elem));   // x2: the look-ahead driver alternates
 }
@@ -461,11 +489,11 @@ static int getrf_dev(lsx_handle_t h, int n, T *A, int lda, int32_t *d_ipiv, int 
     LSX_ARG(n >= 0 && lda >= n && A && d_ipiv);
     if (n == 0) return LSX_OK;
     const int nb = h->nb;
-    PanelArgs pa(h, h->moves_buf[0]);
-    if (percolumn) pa.mode = 0;
     GemmPlan mfma;   // every update of an LU: see GemmPlan
     mfma.mfma_only = true;
     LSX_TRY(ensure_getrf_workspace(h, n, sizeof(T)));
+    PanelArgs pa(h, h->moves_buf[0]);
+    if (percolumn) pa.mode = 0;
     T *Tinv = (T *)h->tinv.p;
     if (!d_info) d_info = h->dev_status + 2;   // a time-out must be recorded somewhere: lsx_check_status reads it
     LSX_HIP(hipMemsetAsync(d_info, 0, sizeof(int), h->stream));
@@ -665,7 +693,6 @@ static int getrs_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, cons
         }));
         BlockInv<T> bi;
         LSX_TRY(carve_block_inv<T>(h, n, &bi));
-        LSX_TRY(reserve(h, h->scratch, few_rhs_scratch_bytes(n, nr)));
         if (h->trsv_mode == 2) {   // 128-row steps, helper workgroups, interchanges + gather fused into the preparation launch
             const int r2 = lu_solve_few_rhs2<T>(h, n, nrhs, nr, LU, lda, d_ipiv, B, ldb, bi.inv64L, bi.inv64U, bi.inv128L,
                                                 bi.inv128U, Bp, X);
@@ -681,7 +708,6 @@ static int getrs_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, cons
     // perm + a copy of B for the row gather
     int32_t *perm = nullptr; T *Bc = nullptr;
     LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) { perm = c.take<int32_t>(n); Bc = c.take<T>((size_t)n * nrhs); }));
-    LSX_TRY(reserve(h, h->scratch, ipiv_to_perm_scratch_bytes(n)));
     LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
     LSX_TRY(launch_copy2d<T>(h, n, nrhs, B, ldb, Bc, nrhs));
     LSX_TRY(launch_gather_rows<T>(h, n, nrhs, perm, Bc, nrhs, B, ldb));
@@ -695,7 +721,6 @@ static int getri_dev(lsx_handle_t h, int n, const T *LU, int lda, const int32_t 
     if (n == 0) return LSX_OK;
     int32_t *perm = nullptr;
     LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) { perm = c.take<int32_t>(n); }));
-    LSX_TRY(reserve(h, h->scratch, ipiv_to_perm_scratch_bytes(n)));
     LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
     if (n >= 512 && !h->getri_plain) {
         // A^-1 = U^-1 L^-1 P with the permutation applied LAST: L^-1 of the identity is lower triangular, so the
@@ -1237,7 +1262,6 @@ static int getrs_t_dev(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, co
     }));
     BlockInv<T> bi;
     LSX_TRY(carve_block_inv<T>(h, n, &bi));
-    LSX_TRY(reserve(h, h->scratch, ipiv_to_perm_scratch_bytes(n)));
     LSX_TRY(launch_ipiv_to_perm(h, n, d_ipiv, perm));
     if (blocked) {
         LSX_TRY(launch_inv128_natural<T>(h, n, LU, lda, bi.inv64L, bi.inv64U, bi.inv128L, bi.inv128U));
@@ -2466,7 +2490,6 @@ static int rref_host(lsx_handle_t h, int m, int n, int bar_col, const T *A, int 
         dp = c.take<int32_t>(2 * (size_t)np);
         drank = c.take<int>(1);
     }));
-    LSX_TRY(reserve(h, h->scratch, rref_scratch_bytes(m, n)));
     LSX_TRY(h2d<T>(h, m, n, A, lda, dR, ld));
     LSX_TRY(rref_any<T>(h, m, n, bar, dR, ld, dp, drank, tol, pivot_rule));
     LSX_TRY(d2h<T>(h, m, n, dR, ld, R, ldr));
@@ -2824,7 +2847,6 @@ int lsx_rref_trace_f64(lsx_handle_t h, int m, int n, int bar_col, const double *
         dT = c.take<unsigned char>((size_t)m * n);
         dout = c.take<int>(4);
     }));
-    LSX_TRY(reserve(h, h->scratch, rref_trace_scratch_bytes()));
     LSX_TRY(h2d<double>(h, m, n, A, lda, dR, ld));
     if (int_mask) LSX_HIP(hipMemcpyAsync(dT, int_mask, (size_t)m * n, hipMemcpyHostToDevice, h->stream));
     else LSX_HIP(hipMemsetAsync(dT, 0, (size_t)m * n, h->stream));
@@ -2851,7 +2873,6 @@ int lsx_rref_f64_dev(lsx_handle_t h, int m, int n, int bar_col, double *dR, int 
     LSX_ARG(pivot_rule == LSX_PIVOT_FIRST || pivot_rule == LSX_PIVOT_MAX);
     const int bar = bar_col > 0 ? bar_col : n - 1;
     LSX_ARG(bar <= n);
-    LSX_TRY(reserve(h, h->scratch, rref_scratch_bytes(m, n)));
     return rref_any<double>(h, m, n, bar, dR, ldr, d_pivots, d_rank, tol, pivot_rule);
 }
 
@@ -2859,7 +2880,7 @@ int lsx_panel_f64_dev(lsx_handle_t h, int m, int jb, double *dP, int ldp, int ro
                       int *d_info) {
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && m >= 1 && jb >= 1 && jb <= 256 && dP && d_ipiv && ldp >= jb);
-    LSX_TRY(reserve(h, h->scratch, std::max(panel_scratch_bytes(m), panel_x_area_bytes(h, h->panel_mode, m, 8) + 4096)));
+    LSX_TRY(reserve(h, h->scratch, panel_scratch_bytes(h, h->panel_mode, h->panel_nt, h->panel_rt, m, 8)));
     PanelArgs pa(h, h->moves_api);
     const int r = launch_panel<double>(h, m, jb, dP, ldp, row0, d_ipiv, d_info, pa);
     h->moves_api_valid = pa.listed;
@@ -2898,15 +2919,15 @@ int lsx_gemm_sub_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dA, 
     LSX_DEVICE_GUARD(h);
     LSX_ARG(h && dA && dB && dC && lda >= k && ldb >= n && ldc >= n);
     if (h->gemm_queue_test) {   // measurements: the work-queue form alone (1: all XCDs, 2: XCD 0 left out as beside a panel)
-        LSX_TRY(reserve(h, h->scratch, 4096));
-        int *w = (int *)h->scratch.p;
-        LSX_HIP(hipMemsetAsync(w, 0, 1024, h->stream));
-        if (h->gemm_queue_test >= 2) LSX_HIP(hipMemsetD32Async((hipDeviceptr_t)w, 1, 1, h->stream));
+        int *avoid = nullptr, *pass = nullptr, *col0 = nullptr, *counters = nullptr;   // the words of XcdScratch, for one update
+        LSX_TRY(carve(h, h->scratch, [&](Carver &c) { avoid = c.take<int>(1); pass = c.take<int>(1); col0 = c.take<int>(2); counters = c.take<int>(8); }));
+        LSX_HIP(hipMemsetAsync(avoid, 0, (char *)(counters + 8) - (char *)avoid, h->stream));
+        if (h->gemm_queue_test >= 2) LSX_HIP(hipMemsetD32Async((hipDeviceptr_t)avoid, 1, 1, h->stream));
         GemmPlan plan;
-        plan.counters = w + 64;
-        plan.avoid_word = h->gemm_queue_test >= 2 ? w : nullptr;
-        plan.pass_word = w + 1;
-        plan.col0 = h->gemm_queue_test == 3 ? w + 32 : nullptr;   // 3: with the column-0-first phase
+        plan.counters = counters;
+        plan.avoid_word = h->gemm_queue_test >= 2 ? avoid : nullptr;
+        plan.pass_word = pass;
+        plan.col0 = h->gemm_queue_test == 3 ? col0 : nullptr;   // 3: with the column-0-first phase
         return launch_gemm_sub<double>(h, m, n, k, dA, lda, dB, ldb, dC, ldc, plan);
     }
     return launch_gemm_sub<double>(h, m, n, k, dA, lda, dB, ldb, dC, ldc);

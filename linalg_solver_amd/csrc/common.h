@@ -134,9 +134,11 @@ struct lsx_handle_s {
     // block, so no function keeps a pointer into a buffer across a call that may grow the SAME buffer.  Who holds what
     // across which calls (a callee is listed with what it grows itself):
     //   host-buffer entry points  staging, across everything below; no driver touches it
-    //   getrf_dev                 scratch, tinv (ensure_getrf_workspace), moves_all (look-ahead); calls no other driver
-    //   getrs_dev, getrs_t_dev    rhs_work, tinv, scratch: the same pieces, so the two share what they grow; the many-column
-    //                             getrs_dev is done with rhs_work before lu_solve_permuted carves tinv; xchg in the launcher
+    //   getrf_dev                 scratch (in its PanelArgs), tinv (ensure_getrf_workspace), moves_all (look-ahead);
+    //                             calls no other driver, and no launcher that carves scratch
+    //   getrs_dev, getrs_t_dev    rhs_work, tinv: the same pieces, so the two share what they grow; the many-column
+    //                             getrs_dev is done with rhs_work before lu_solve_permuted carves tinv; xchg and scratch
+    //                             (ipiv_to_perm, cooperative solve) in the launchers
     //   getri_dev                 rhs_work (permutation) and getri_work, across tinv (its own or lu_solve_permuted's)
     //   potrf_dev, potrs_dev      tinv, rhs_work
     //   potri_dev                 getri_work (V = inv(U^T)), across trtri_upper_t (tinv: block inverses, rhs_work: one
@@ -148,11 +150,15 @@ struct lsx_handle_s {
     //   gesvx_dev                 equil, across geequ_dev (equil again, never more than gesvx_dev carved), lange_dev
     //                             (scratch), getrf_dev, gecon_dev, getrs_dev / getrs_t_dev and gerfs_dev
     //   gesv_refined_dev          mixed_resid, across getrs_dev
-    //   rref_blocked              rhs_work (its column block and block inverses), scratch
-    //   rref_first_fast           rref_first, across rref_blocked, getrf_dev and getrs_dev; tinv for its own first-rule
-    //                             factorisation, which is finished before those two are called
-    // scratch belongs to the launchers: each lays it out from offset 0 (or a driver's area offset) at launch time and
-    // says how much it needs (*_scratch_bytes, *_work_bytes, *_area_bytes below); no launch relies on what an earlier call left there.
+    //   rref_blocked              rhs_work (its column block and block inverses), scratch; calls block solves and updates only
+    //   rref_first_fast           rref_first, across rref_blocked, getrf_dev and getrs_dev; tinv and scratch (its PanelArgs) for
+    //                             its own first-rule factorisation, begun after rref_blocked and finished before those two
+    // scratch belongs to the launchers; no launch relies on what an earlier call left there.  Each user writes its layout
+    // once, as Carver::take calls beside the code that uses the pieces, and placement and size both come from it.  Nobody
+    // holds a piece across a launcher that carves scratch itself: launch_rref, rref_blocked, launch_rref_trace,
+    // launch_ipiv_to_perm, lu_solve_few_rhs, the probes.  A panel launch runs under OnStream and never reserves: it lays out
+    // inside the area its PanelArgs hands over (carve_in) and exports the counted size (panel_*_bytes); so do the LU drivers,
+    // inside the scratch ensure_getrf_workspace sized as the largest layout that can run.  (*_work_bytes: ONE array by pointer.)
     DevBuf staging;      // staging of caller matrices (host-buffer entry points)
     DevBuf tinv;         // triangular block inverses of every driver and solve
     DevBuf rhs_work;     // permutation + right-hand-side / panel work copies
@@ -209,10 +215,13 @@ struct GemmDone {
 struct PanelArgs {
     int mode, nt, rt;             // effective panel mode, threads per workgroup, rows per thread
     void *list;                   // int2[256]: where a cooperative kernel writes this panel's gather list
-    size_t area_off = 0, area_bytes = 0;   // exchange area inside scratch that the DRIVER keeps cleared (off the panel-to-panel chain); 0 bytes = the launch clears its own
+    // Where the launch lays out its exchange area or pivot candidates: to begin with all of scratch as it stands (so a
+    // PanelArgs is made AFTER scratch was sized) and the launch clears what it uses; a look-ahead driver hands over one
+    // of its rotating areas and keeps it cleared itself, off the panel-to-panel chain (cleared = true).
+    void *area; size_t area_bytes; bool cleared = false;
     int *xcc_word = nullptr;      // where the XCD-scope kernel records 1 + its XCC id
     bool listed = false;          // out: a cooperative kernel ran, `list` describes this panel's interchanges
-    PanelArgs(lsx_handle_t h, void *list_) : mode(h->panel_mode), nt(h->panel_nt), rt(h->panel_rt), list(list_) {}
+    PanelArgs(lsx_handle_t h, void *list_) : mode(h->panel_mode), nt(h->panel_nt), rt(h->panel_rt), list(list_), area(h->scratch.p), area_bytes(h->scratch.bytes) {}
 };
 
 // b holds at least `need` bytes afterwards: no HIP call when it already does (a warmed-up call stays graph-capturable),
@@ -233,13 +242,35 @@ struct Carver {
 };
 // Size b from its own layout and lay it out: `layout` (take calls only, pointers derived from a taken one are formed
 // after carve returns) runs once to count and once on the block.
-template <class F> int carve(lsx_handle_t h, DevBuf &b, F &&layout) {
+template <class F> size_t carve_bytes(F &&layout) {
     Carver count(nullptr);
     layout(count);
-    LSX_TRY(reserve(h, b, count.off));
+    return count.off;
+}
+template <class F> int carve(lsx_handle_t h, DevBuf &b, F &&layout, bool *fresh = nullptr) {
+    LSX_TRY(reserve(h, b, carve_bytes(layout), fresh));
     Carver c(b.p);
     layout(c);
     return LSX_OK;
+}
+// A layout placed inside an area sized earlier: no reserve (usable under OnStream); too small is an error, never another schedule.
+template <class F> int carve_in(void *area, size_t bytes, const char *who, F &&layout) {
+    Carver c(area);
+    layout(c);
+    if (area && c.off <= bytes) return LSX_OK;
+    set_error("%s: needs %zu bytes of scratch, was handed %zu", who, c.off, bytes);
+    return LSX_ERR_INTERNAL;
+}
+// Largest bytes(height) over panel heights <= m (a taller panel may take fewer, larger row slices; slice heights and the
+// thresholds between forms are multiples of 64, so m and the multiples of 64 below it cover every case).  every: 0 if some height gives 0.
+template <class F> size_t max_over_heights(int m, bool every, F &&bytes) {
+    size_t need = 0;
+    for (int mm = m; mm > 0; mm = (mm - 1) / 64 * 64) {
+        const size_t b = bytes(mm);
+        if (every && !b) return 0;
+        if (b > need) need = b;
+    }
+    return need;
 }
 int ensure_getrf_workspace(lsx_handle_t h, int n, size_t elem);
 // XCD-scope panel under the reference's first-non-zero pivot rule (kernels_panel_x.hip); 1 = shape not served
@@ -332,19 +363,19 @@ int launch_gemm_tn_sub(lsx_handle_t h, int m, int n, int k, const T *A, int lda,
 // k-slabs of 16 from the last one down (k ascending inside a slab) instead of k ascending throughout.  Sets h->potri_tiles.
 template <typename T>
 int launch_lauum_tn(lsx_handle_t h, int n, const T *V, int ldv, T *C, int ldc, int order, bool descending);
-// traced reference-order row reduction (kernels_trace.hip); d_out = {pivots, steps, overflow}
+// traced reference-order row reduction (kernels_trace.hip), carves scratch; d_out = {pivots, steps, overflow}
 int launch_rref_trace(lsx_handle_t h, int m, int n, int bar, double *R, int ldr, unsigned char *Tm,
                       int32_t *d_pivots, int32_t *d_steps, int max_steps, double *d_snaps,
                       unsigned char *d_snap_t, int max_snaps, int *d_out);
 template <typename T>
 int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t *d_ipiv,
                  int *d_info, PanelArgs &pa);
-// scratch of a panel launch (<= m rows) that clears its own area: per-column candidates or the pipelined exchange area
-size_t panel_scratch_bytes(int m);
-// bytes of one exchange area of the pipelined panel for panels of up to m rows; 0 = these panel
-// settings are not ones the pipelined kernel serves for every height <= m
-size_t panel_pipe_area_bytes(lsx_handle_t h, int mode, int nt, int rt, int m);
-size_t panel_x_area_bytes(lsx_handle_t h, int mode, int m, size_t elem);
+// Counts of the launchers' own layouts for panels of up to m rows.  panel_scratch_bytes: a self-clearing launch_panel,
+// whichever form takes a height.  The other two: one exchange area of the pipelined / XCD-scope kernel; for_driver: one a
+// look-ahead driver keeps cleared, 0 = these settings do not serve every height (else: the largest among those served).
+size_t panel_scratch_bytes(lsx_handle_t h, int mode, int nt, int rt, int m, size_t elem);
+size_t panel_pipe_area_bytes(lsx_handle_t h, int mode, int nt, int rt, int m, bool for_driver = true);
+size_t panel_x_area_bytes(lsx_handle_t h, int mode, int m, size_t elem, bool for_driver = true);
 template <typename T>
 int launch_laswp(lsx_handle_t h, int ncols, T *A, int lda, int row0, int jb, const int32_t *d_ipiv);
 // same interchanges from a gather list (written by the cooperative panel kernel)
@@ -383,7 +414,7 @@ int launch_trtri_both(lsx_handle_t h, int n, const T *LU, int lda, T *invL, T *i
 template <typename T>
 int launch_trsm_block(lsx_handle_t h, int lower, int jb, int ncols, const T *Tm, int ldt,
                       const T *Tinv, T *B, int ldb);
-size_t ipiv_to_perm_scratch_bytes(int n);   // two index arrays; with less scratch the launch takes its slow form
+// carves scratch (two index arrays of n)
 int launch_ipiv_to_perm(lsx_handle_t h, int n, const int32_t *d_ipiv, int32_t *d_perm);
 template <typename T>
 int launch_gather_rows(lsx_handle_t h, int n, int ncols, const int32_t *d_perm, const T *S, int lds,
@@ -395,9 +426,7 @@ int launch_scatter_cols(lsx_handle_t h, int n, const int32_t *d_perm, const T *S
 // d_ipiv == nullptr: no interchanges (a Cholesky factor); square: the (sign, mant, exp2) triple of the product squared
 template <typename T>
 int launch_det(lsx_handle_t h, int n, const T *LU, int lda, const int32_t *d_ipiv, double *d_out, bool square = false);
-// scratch of an m x n row reduction: state and two rows (per-column form) or row-group candidates (blocked); the trace's state
-size_t rref_scratch_bytes(int m, int n);
-size_t rref_trace_scratch_bytes();
+// carves scratch: state and two rows (per-column form) or row-group candidates (blocked, which also carves rhs_work)
 template <typename T>
 int launch_rref(lsx_handle_t h, int m, int n, int bar, T *R, int ldr, int32_t *d_pivots,
                 int *d_rank, double tol, int pivot_rule);
@@ -413,8 +442,6 @@ int lu_solve_few_rhs2(lsx_handle_t h, int n, int nrhs, int nr, const T *LU, int 
 template <typename T>
 int lu_solve_few_rhs(lsx_handle_t h, int n, int nrhs, const T *LU, int lda, T *B, int ldb, T *X, T *inv64L,
                      T *inv64U, T *inv128L, T *inv128U);
-// scratch of lu_solve_few_rhs for nr (1, 2, 4 or 8) columns: the two exchange areas of its cooperative form
-size_t few_rhs_scratch_bytes(int n, int nr);
 // block inverses of both triangles, 128 x 128, natural orientation (kernels_trsv.hip), and the transposed solve,
 // the norms and the estimator's vector steps built on them (kernels_trsvt.hip)
 template <typename T>

@@ -66,11 +66,11 @@ __global__ __launch_bounds__(256) void mfma_peak_f32_kernel(int iters, double *o
 
 int diag_mfma_peak(lsx_handle_t h, int is_f32, int iters, int blocks_per_cu, double *tflops, double *clock_mhz) {
     const int grid = h->num_cu * blocks_per_cu;
-    unsigned long long *stamps = (unsigned long long *)((char *)h->scratch.p + 4096);
+    double *out = nullptr; unsigned long long *stamps = nullptr;   // per workgroup: {clocks, wall ticks}
+    LSX_TRY(carve(h, h->scratch, [&](Carver &c) { out = c.take<double>(1); stamps = c.take<unsigned long long>(2 * (size_t)grid); }));
     hipEvent_t e0, e1;
     LSX_HIP(hipEventCreate(&e0));
     LSX_HIP(hipEventCreate(&e1));
-    double *out = (double *)h->scratch.p;
     for (int rep = 0; rep < 2; ++rep) {  // first pass warms up clocks and code
         LSX_HIP(hipEventRecord(e0, h->stream));
         if (is_f32)
@@ -214,11 +214,10 @@ __global__ __launch_bounds__(256) void xchg_probe_kernel(int mode, int stride, i
 // us_per_epoch: mean over participants; xcc_ids[G] (may be null); failures through *nfail
 int diag_xchg_probe(lsx_handle_t h, int mode, int G, int stride, int wt, int epochs, double *us_per_epoch,
                     int *xcc_ids, int *nfail) {
-    const size_t body = ((size_t)G * HDR_STRIDE + (size_t)G * 128 * 16 + 255) & ~(size_t)255;
-    const size_t need = body + (size_t)G * 24 + 256;
-    if (need > h->scratch.bytes) { set_error("xchg_probe: scratch too small"); return LSX_ERR_INTERNAL; }
-    char *area = (char *)h->scratch.p;
-    unsigned long long *out = (unsigned long long *)(area + body);
+    // headers and granule rows as one block (the kernel finds the rows behind the headers), then {ticks, xcc, failures} each
+    char *area = nullptr; unsigned long long *out = nullptr;
+    LSX_TRY(carve(h, h->scratch, [&](Carver &c) { area = c.take<char>((size_t)G * (HDR_STRIDE + 128 * 16)); out = c.take<unsigned long long>(3 * (size_t)G); }));
+    const size_t need = (char *)(out + 3 * (size_t)G) - area;
     std::vector<unsigned long long> ho(3 * (size_t)G);
     for (int rep = 0; rep < 2; ++rep) {
         LSX_HIP(hipMemsetAsync(area, 0, need, h->stream));
@@ -260,15 +259,16 @@ __global__ __launch_bounds__(256) void where_kernel(unsigned *out, int spin) {
 
 // mask_words: the CU mask (ncu bits); out: per block {xcc, hw_id}
 int diag_cu_mask_probe(lsx_handle_t h, const uint32_t *mask_words, int nwords, int nblocks, unsigned *out_host) {
-    if ((size_t)nblocks * 8 > h->scratch.bytes) { set_error("cu_mask_probe: scratch too small"); return LSX_ERR_INTERNAL; }
+    unsigned *where = nullptr;
+    LSX_TRY(carve(h, h->scratch, [&](Carver &c) { where = c.take<unsigned>(2 * (size_t)nblocks); }));
     hipStream_t st = nullptr;
     if (nwords > 0) LSX_HIP(hipExtStreamCreateWithCUMask(&st, (uint32_t)nwords, mask_words));
     else st = h->stream;
     LSX_HIP(hipStreamSynchronize(h->stream));
-    hipLaunchKernelGGL(where_kernel, dim3(nblocks), dim3(256), 0, st, (unsigned *)h->scratch.p, 20);
+    hipLaunchKernelGGL(where_kernel, dim3(nblocks), dim3(256), 0, st, where, 20);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMemcpy(out_host, h->scratch.p, (size_t)nblocks * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_host, where, (size_t)nblocks * 8, hipMemcpyDeviceToHost);
     if (nwords > 0) (void)hipStreamDestroy(st);
     if (e != hipSuccess) { set_error("cu_mask_probe: %s", hipGetErrorString(e)); return LSX_ERR_HIP; }
     return LSX_OK;

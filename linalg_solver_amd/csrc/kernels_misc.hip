@@ -849,53 +849,6 @@ int launch_chain_fused(lsx_handle_t h, const int2 *moves, int *info, int jb, con
 
 // ------------------------------------------------------------------ permutation helpers
 
-// perm[i] = original row that ends at position i after all n interchanges.
-// Each thread walks the interchange list backwards from its own position (the list is staged in LDS),
-// so the conversion is O(n) deep and n-wide instead of an n-step serial chain.  Two facts keep it
-// short: an interchange (t, p) has p >= t, so it cannot touch a walker whose position is below t --
-// position i starts at step t = i, not n-1; four steps share one 16-byte LDS read; and a group of four
-// that touches no lane of the wave costs five independent compares instead of an 8-deep select chain.  (At n = 4096 a
-// plain full-length walk took 236 us: more than half of a one-right-hand-side solve.)
-__global__ __launch_bounds__(256) void ipiv_to_perm_kernel(int n, const int32_t *__restrict__ ipiv,
-                                                           int32_t *__restrict__ perm) {
-    __shared__ __attribute__((aligned(16))) int s_piv[2048];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int imax = min(n - 1, (int)blockIdx.x * 256 + 255);   // highest position walked by this workgroup
-    int x = i;
-    for (int base = (imax / 2048) * 2048; base >= 0; base -= 2048) {
-        const int cnt = min(2048, n - base);
-        __syncthreads();
-        // beyond the list: identity interchanges (t, t), which leave every walker where it is
-        for (int k = threadIdx.x; k < 2048; k += 256) s_piv[k] = (k < cnt) ? ipiv[base + k] : base + k;
-        __syncthreads();
-        // eight steps per trip, the next trip's two 16-byte LDS reads already in flight
-        const int top = min(2047, imax - base) | 7;
-        int4 pa = *(const int4 *)&s_piv[top - 3], pb = *(const int4 *)&s_piv[top - 7];
-        for (int k = top; k >= 7; k -= 8) {
-            const int4 qa = pa, qb = pb;
-            if (k >= 15) {
-                pa = *(const int4 *)&s_piv[k - 11];
-                pb = *(const int4 *)&s_piv[k - 15];
-            }
-            const int t = base + k;
-            // the eight interchanges touch a walker only if it sits on one of their 16 rows: test that
-            // with independent compares and skip the dependent chain when no lane of the wave is hit
-            const bool hit = ((unsigned)(x - (t - 7)) < 8u) | (x == qa.w) | (x == qa.z) | (x == qa.y) | (x == qa.x) |
-                             (x == qb.w) | (x == qb.z) | (x == qb.y) | (x == qb.x);
-            if (!__any(hit)) continue;
-            x = (x == t) ? qa.w : ((x == qa.w) ? t : x);
-            x = (x == t - 1) ? qa.z : ((x == qa.z) ? t - 1 : x);
-            x = (x == t - 2) ? qa.y : ((x == qa.y) ? t - 2 : x);
-            x = (x == t - 3) ? qa.x : ((x == qa.x) ? t - 3 : x);
-            x = (x == t - 4) ? qb.w : ((x == qb.w) ? t - 4 : x);
-            x = (x == t - 5) ? qb.z : ((x == qb.z) ? t - 5 : x);
-            x = (x == t - 6) ? qb.y : ((x == qb.y) ? t - 6 : x);
-            x = (x == t - 7) ? qb.x : ((x == qb.x) ? t - 7 : x);
-        }
-    }
-    if (i < n) perm[i] = x;
-}
-
 // D[i][:] = S[perm[i]][:]
 template <typename T>
 __global__ void gather_rows_kernel(int n, int ncols, const int32_t *__restrict__ perm,
@@ -905,7 +858,9 @@ __global__ void gather_rows_kernel(int n, int ncols, const int32_t *__restrict__
     if (j < ncols) D[(size_t)i * ldd + j] = S[(size_t)perm[i] * lds + j];
 }
 
-// The same conversion without an O(n)-deep dependent chain.  Forward view: at step k the rows at
+// perm[i] = original row that ends at position i after all n interchanges, without an O(n)-deep dependent chain (a
+// walk of every position back through the interchange list took 236 us at n = 4096: more than half of a
+// one-right-hand-side solve).  Forward view: at step k the rows at
 // positions k and p_k = ipiv[k] >= k swap; position k is final afterwards, so
 //     perm[k] = content of position p_k just before step k,
 // and the content of a position v just before step `bound` is the content position c had just before
@@ -913,7 +868,7 @@ __global__ void gather_rows_kernel(int n, int ncols, const int32_t *__restrict__
 // Two index arrays make every hop O(1) apart from skipping later steps that target the same position:
 //     last_target[v] = largest c with p_c == v,       prev_same[c] = largest c' < c with p_c' == p_c.
 // Building them is one pass of independent compares per entry (no loop-carried select chain across
-// 16 dependent operations as in the walk above); the chase itself takes a few hops per row.
+// 16 dependent operations as in such a walk); the chase itself takes a few hops per row.
 __global__ __launch_bounds__(256) void perm_index_kernel(int n, const int32_t *__restrict__ ipiv,
                                                          int32_t *__restrict__ last_target,
                                                          int32_t *__restrict__ prev_same) {
@@ -976,21 +931,13 @@ __global__ __launch_bounds__(256) void perm_chase_kernel(int n, const int32_t *_
     perm[k] = v;
 }
 
-size_t ipiv_to_perm_scratch_bytes(int n) { return 2 * sizeof(int32_t) * (size_t)n + 256; }
-
 int launch_ipiv_to_perm(lsx_handle_t h, int n, const int32_t *d_ipiv, int32_t *d_perm) {
     if (n <= 0) return LSX_OK;
-    const size_t need = 2 * sizeof(int32_t) * (size_t)n;
-    if (h->scratch.p && h->scratch.bytes >= need) {
-        // the two index arrays live in the handle's scratch (every later user of it is stream-ordered)
-        int32_t *last_target = (int32_t *)h->scratch.p, *prev_same = last_target + n;
-        hipLaunchKernelGGL(perm_index_kernel, dim3((n + 63) / 64, 2), dim3(256), 0, h->stream, n, d_ipiv, last_target,
-                           prev_same);
-        hipLaunchKernelGGL(perm_chase_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, d_ipiv, last_target,
-                           prev_same, d_perm);
-    } else {
-        hipLaunchKernelGGL(ipiv_to_perm_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, d_ipiv, d_perm);
-    }
+    // the two index arrays live in the handle's scratch (every later user of it is stream-ordered)
+    int32_t *last_target = nullptr, *prev_same = nullptr;
+    LSX_TRY(carve(h, h->scratch, [&](Carver &c) { last_target = c.take<int32_t>(n); prev_same = c.take<int32_t>(n); }));
+    hipLaunchKernelGGL(perm_index_kernel, dim3((n + 63) / 64, 2), dim3(256), 0, h->stream, n, d_ipiv, last_target, prev_same);
+    hipLaunchKernelGGL(perm_chase_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, d_ipiv, last_target, prev_same, d_perm);
     LSX_HIP(hipGetLastError());
     return LSX_OK;
 }

@@ -12,6 +12,8 @@
 // two panel rows) and `panel_update` (scale the column, rank-1 update of the
 // remaining panel columns, and the per-workgroup arg-max partials of the NEXT
 // column in the same pass).  Simple and robust; launch-latency bound.
+#include <algorithm>
+
 #include "common.h"
 
 namespace lsx {
@@ -126,17 +128,22 @@ __global__ __launch_bounds__(256) void panel_update_kernel(int m, int jb, T *__r
     }
 }
 
+// scratch of the per-column form: one pivot candidate (value of elem bytes, row) per workgroup of the widest launch
+struct PanelCand {
+    void *val; int *idx;
+    void lay(Carver &c, int m, size_t elem) {
+        const size_t ngrid_max = (m + PROWS - 1) / PROWS + 1;
+        val = c.take<char>(ngrid_max * elem);
+        idx = c.take<int>(ngrid_max);
+    }
+};
+
 template <typename T>
 int panel_percolumn(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0,
-                    int32_t *d_ipiv, int *d_info) {
-    // scratch layout: cand_val[ngrid] | cand_idx[ngrid]
-    const int ngrid_max = (m + PROWS - 1) / PROWS + 1;
-    T *cand_val = (T *)h->scratch.p;
-    int *cand_idx = (int *)((char *)h->scratch.p + sizeof(double) * ngrid_max);
-    if (sizeof(double) * ngrid_max + sizeof(int) * ngrid_max > h->scratch.bytes) {
-        set_error("panel: scratch too small for m=%d", m);
-        return LSX_ERR_INTERNAL;
-    }
+                    int32_t *d_ipiv, int *d_info, PanelArgs &pa) {
+    PanelCand cand;
+    LSX_TRY(carve_in(pa.area, pa.area_bytes, "panel", [&](Carver &c) { cand.lay(c, m, sizeof(T)); }));
+    T *const cand_val = (T *)cand.val; int *const cand_idx = cand.idx;
     int ncand = (m + PROWS - 1) / PROWS;
     hipLaunchKernelGGL(panel_update_kernel<T>, dim3(ncand), dim3(256), 0, h->stream, m, jb, P, ldp, -1,
                        cand_val, cand_idx);
@@ -160,9 +167,11 @@ int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
 template <typename T>
 int panel_xcd(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, PanelArgs &pa);
 
-size_t panel_scratch_bytes(int m) {
-    const size_t groups = (size_t)m / 32 + 2;   // 32-row groups: more than either form has workgroups
-    return ((16 * groups + 255) & ~(size_t)255) + groups * 5248 + 8192;
+size_t panel_scratch_bytes(lsx_handle_t h, int mode, int nt, int rt, int m, size_t elem) {
+    size_t need = carve_bytes([&](Carver &c) { PanelCand().lay(c, m, elem); });   // where every shape may end up
+    if (mode >= 3) need = std::max(need, panel_pipe_area_bytes(h, mode, nt, rt, m, false));
+    if (mode == 4) need = std::max(need, panel_x_area_bytes(h, mode, m, elem, false));
+    return need;
 }
 
 template <typename T>
@@ -180,7 +189,7 @@ int launch_panel(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int32_t
         const int r = panel_pipelined<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info, pa);
         if (r != 1) return r;  // 1 = shape not supported: per-column launches
     }
-    return panel_percolumn<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info);
+    return panel_percolumn<T>(h, m, jb, P, ldp, row0, row0, d_ipiv, d_info, pa);
 }
 
 template int launch_panel<double>(lsx_handle_t, int, int, double *, int, int, int32_t *, int *, PanelArgs &);

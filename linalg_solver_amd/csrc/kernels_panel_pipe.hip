@@ -511,59 +511,64 @@ __global__ __launch_bounds__(NT, NT / 256) void panel_pipe_kernel(int m, int jb,
                                         status, dbg, moves);
 }
 
+// One exchange area, in the order the kernel and the tools' stamp readers rely on: status word at 0 | headers[2][G] at
+// 256 (HDR_STRIDE apart) | granule rows[2][G][128] | debug stamps at the next 256-byte boundary.  Headers and granules
+// are multiples of 256 bytes, so taken in this order the Carver's alignment leaves them back to back.
+struct PipeArea {
+    int *status; char *hdr; XGran *xrow; unsigned long long *dbg = nullptr;
+    size_t bytes;   // all of it is zero at EVERY launch (epoch 0 never matches)
+    void lay(Carver &c, int G, bool debug) {
+        status = c.take<int>(64);
+        hdr = c.take<char>((size_t)2 * G * HDR_STRIDE);
+        xrow = c.take<XGran>((size_t)2 * G * PC_COLS);
+        if (debug) dbg = c.take<unsigned long long>((size_t)G * 8);
+        bytes = c.off;
+    }
+};
+
 template <typename T, int RT, int NT, int KS>
 static int panel_pipe_launch(lsx_handle_t h, int G, int m, int jb, T *P, int ldp, int row0, int col0,
                              int32_t *d_ipiv, int *d_info, PanelArgs &pa) {
-    // exchange area in scratch: status | headers[2][G] (HDR_STRIDE apart) | granule rows[2][G][128]
-    const size_t hdr_bytes = (size_t)2 * G * HDR_STRIDE;
-    const size_t need = 256 + hdr_bytes + (size_t)2 * G * PC_COLS * sizeof(XGran);
-    const size_t dbg_off = (need + 255) & ~(size_t)255;
-    const size_t total = dbg_off + (h->panel_debug ? (size_t)G * 64 : 0);
-    const bool driver_clears = pa.area_bytes > 0 && !h->panel_debug;
-    const size_t base_off = driver_clears ? pa.area_off : 0;
-    if (base_off + total > h->scratch.bytes || (driver_clears && need > pa.area_bytes)) {
-        set_error("panel_pipe: scratch too small (%zu + %zu > %zu)", base_off, total, h->scratch.bytes);
-        return LSX_ERR_INTERNAL;
-    }
-    char *base = (char *)h->scratch.p + base_off;
-    int *status = (int *)base;
-    char *hdr = base + 256;
-    XGran *xrow = (XGran *)(base + 256 + hdr_bytes);
-    // status word, headers AND granules are zero at EVERY launch (epoch 0 never matches): cleared here, or
-    // by the look-ahead driver beside the previous panel so that the memset is not on the panel-to-panel chain
-    if (!driver_clears) LSX_HIP(hipMemsetAsync(base, 0, h->panel_debug ? total : need, h->stream));
-    unsigned long long *dbg = h->panel_debug ? (unsigned long long *)(base + dbg_off) : nullptr;
+    PipeArea a;
+    LSX_TRY(carve_in(pa.area, pa.area_bytes, "panel_pipe", [&](Carver &c) { a.lay(c, G, h->panel_debug); }));
+    // cleared here, or by the look-ahead driver beside the previous panel: off the panel-to-panel chain
+    if (!pa.cleared) LSX_HIP(hipMemsetAsync(a.status, 0, a.bytes, h->stream));
     if (h->panel_debug) {
         hipLaunchKernelGGL((panel_pipe_kernel<T, RT, NT, KS, true>), dim3(G), dim3(NT), 0, h->stream, m, jb, P, ldp,
-                           row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)pa.list);
+                           row0, col0, d_ipiv, d_info, a.hdr, a.xrow, a.status, a.dbg, (int2 *)pa.list);
     } else {
         hipLaunchKernelGGL((panel_pipe_kernel<T, RT, NT, KS, false>), dim3(G), dim3(NT), 0, h->stream, m, jb, P, ldp,
-                           row0, col0, d_ipiv, d_info, hdr, xrow, status, dbg, (int2 *)pa.list);
+                           row0, col0, d_ipiv, d_info, a.hdr, a.xrow, a.status, a.dbg, (int2 *)pa.list);
     }
     LSX_HIP(hipGetLastError());
     pa.listed = true;
     return LSX_OK;
 }
 
+// Workgroup shape for an m-row panel: NT threads (16 thread columns x NT/16 thread rows), RT rows per thread, G
+// workgroups; G = 0: outside what the kernel serves.  One wave per SIMD (NT = 256) keeps the critical wave's issue
+// slots to itself; taller panels take 512 threads so that every workgroup is still resident at once.
+struct PipeShape { int nt, rt, G; };
+static PipeShape pipe_shape(lsx_handle_t h, int nt, int rt, int m) {
+    auto wgs = [&](int nt_, int rt_) { return (m + nt_ / 16 * rt_ - 1) / (nt_ / 16 * rt_); };
+    if (nt == 0) {  // measured: one header per polling lane (<= 64 workgroups) wins
+        nt = 256, rt = 4;
+        if (wgs(nt, rt) > 64) nt = 512;
+    }
+    if (nt != 256 && nt != 512) return {nt, rt, 0};
+    if (wgs(nt, rt) > h->num_cu) { nt = 512; rt = 8; }  // 256-row slices
+    const int G = wgs(nt, rt);
+    const bool served = G <= h->num_cu && G <= 256 && (rt == 4 || (rt == 8 && nt == 512));
+    return {nt, rt, served ? G : 0};
+}
+
 // Returns 1 when the shape is outside what the kernel supports (caller falls back).
 template <typename T>
 int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv,
                     int *d_info, PanelArgs &pa) {
-    if (jb > PC_COLS) return 1;
-    // workgroup shape: NT threads (16 thread columns x NT/16 thread rows), RT rows per thread.  One
-    // wave per SIMD (NT = 256) keeps the critical wave's issue slots to itself; taller panels take
-    // 512 threads so that every workgroup is still resident at once.
-    int nt = pa.nt, rt = pa.rt;
-    auto rows = [](int nt_, int rt_) { return nt_ / 16 * rt_; };
-    auto wgs = [&](int nt_, int rt_) { return (m + rows(nt_, rt_) - 1) / rows(nt_, rt_); };
-    if (pa.nt == 0) {  // measured: one header per polling lane (<= 64 workgroups) wins
-        nt = 256, rt = 4;
-        if (wgs(nt, rt) > 64) nt = 512;
-    }
-    if (nt != 256 && nt != 512) return 1;
-    if (wgs(nt, rt) > h->num_cu) { nt = 512; rt = 8; }  // 256-row slices
-    const int G = wgs(nt, rt);
-    if (G > h->num_cu || G > 256) return 1;
+    const PipeShape s = pipe_shape(h, pa.nt, pa.rt, m);
+    const int nt = s.nt, rt = s.rt, G = s.G;
+    if (jb > PC_COLS || G == 0) return 1;
     const int ks = G <= 64 ? 1 : (G <= 128 ? 2 : 4);
 #define LSX_PP(RT_, NT_, KS_)                     \
     if (rt == RT_ && nt == NT_ && ks == KS_)      \
@@ -575,16 +580,13 @@ int panel_pipelined(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int 
     return 1;
 }
 
-size_t panel_pipe_area_bytes(lsx_handle_t h, int mode, int nt, int rt, int m) {
-    if (mode < 3 || h->panel_debug || h->nb > PC_COLS) return 0;
-    if (nt != 0 && nt != 256 && nt != 512) return 0;
-    if (!(rt == 4 || (rt == 8 && nt == 512))) return 0;
-    if (m > 256 * (h->num_cu < 256 ? h->num_cu : 256)) return 0;
-    int G = (m + 127) / 128;        // 128-row slices above 4096 rows, never more than 64 slices below
-    if (G < 64) G = 64;
-    if (nt == 256 && rt == 4) G = (m + 63) / 64;
-    if (G > 256) G = 256;
-    return ((size_t)256 + (size_t)G * (2 * HDR_STRIDE + 2 * PC_COLS * sizeof(XGran)) + 255) & ~(size_t)255;
+size_t panel_pipe_area_bytes(lsx_handle_t h, int mode, int nt, int rt, int m, bool for_driver) {
+    if (mode < 3 || (for_driver && (h->panel_debug || h->nb > PC_COLS))) return 0;
+    const size_t need = max_over_heights(m, for_driver, [&](int mm) {
+        const int G = pipe_shape(h, nt, rt, mm).G;
+        return G ? carve_bytes([&](Carver &c) { PipeArea().lay(c, G, h->panel_debug); }) : (size_t)0;
+    });
+    return (need + 255) & ~(size_t)255;   // a driver takes several, back to back
 }
 
 template int panel_pipelined<double>(lsx_handle_t, int, int, double *, int, int, int, int32_t *, int *, PanelArgs &);

@@ -26,6 +26,7 @@
 //    which it brings up to date after the barrier while its header shot for the next column is in flight).
 //  * Arg-max.  The three-phase DPP arg-max runs its first phase only when the high word of |a| already
 //    separates the candidates (ties fall back to the full form, so the choice is unchanged).
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -688,66 +689,74 @@ __global__ __launch_bounds__(PX_NT, PX_NT / 256) void panel_x_kernel(int m, int 
         panel_x_body<T, RT, DBG, false, FIRST>(G, g, m, jb, P, ldp, row0, col0, ipiv, info, rec, far, status, dbg, moves, spin_limit, tol);
 }
 
-// bytes of one exchange area for panels of up to m rows (0: not served)
-size_t panel_x_area_bytes(lsx_handle_t h, int mode, int m, size_t elem) {
-    const int rt = elem == 8 ? 4 : 8;
-    if (mode != 4 || h->panel_debug || h->nb > PC_COLS) return 0;
-    if (m > 32 * 64 * rt) m = 32 * 64 * rt;   // taller panels take the device-scope kernel (its own area size)
-    return ((size_t)256 + (size_t)32 * (2 * PX_REC + 4 * PC_COLS * sizeof(XGran)) + 255) & ~(size_t)255;
+// One exchange area, in the order the kernel and the tools' stamp readers rely on: status word at 0, XCC handshake words
+// at +64 | records[2][G] at 256 | far granule rows[4][G][128] | debug stamps at the next 256-byte boundary.  Records and
+// granules are multiples of 256 bytes, so taken in this order the Carver's alignment leaves them back to back.
+struct XArea {
+    int *status, *xcc; char *rec; XGran *far; unsigned long long *dbg = nullptr;
+    size_t bytes;   // all of it is zero at every launch
+    void lay(Carver &c, int G, bool debug) {
+        status = c.take<int>(64), xcc = status + 16;
+        rec = c.take<char>((size_t)2 * G * PX_REC);
+        far = c.take<XGran>((size_t)4 * G * PC_COLS);
+        if (debug) dbg = c.take<unsigned long long>((size_t)G * 16);
+        bytes = c.off;
+    }
+};
+// Rows per lane (RT) and workgroups (G, of 64 RT rows; 0 = height not served): as few rows per lane as the panel's height
+// allows with at most 32 workgroups -- 1 up to 2048 rows, 2 up to 4096, 4 up to 8192, and in fp32 (which has the registers)
+// 8 up to 16384.  The owner wave's per-column work (multipliers, update of its block, choice of the next candidate) is
+// proportional to RT and outweighs the dearer all-gather of more workgroups: 4 -> 2 -> 1 took 8192^2 fp64 from 17.1 to 16.6 to
+// 16.3 ms and 4096^2 from 6.95 to 6.36 to 6.23 ms, 8 -> 4 took 8192^2 fp32 from 16.9 to 14.5 ms.  Same arithmetic per element, same pivots.
+struct XShape { int rt, G; };
+static XShape x_shape(lsx_handle_t h, int m, size_t elem) {
+    const int rt = m <= 32 * 64 * 1 ? 1 : m <= 32 * 64 * 2 ? 2 : (elem == 4 && m > 32 * 64 * 4) ? 8 : 4;
+    const int G = (m + 64 * rt - 1) / (64 * rt);
+    return {rt, (G > 32 || G > h->num_cu) ? 0 : G};
+}
+
+size_t panel_x_area_bytes(lsx_handle_t h, int mode, int m, size_t elem, bool for_driver) {
+    if (mode != 4 || (for_driver && (h->panel_debug || h->nb > PC_COLS))) return 0;
+    m = std::min(m, 32 * 64 * (elem == 8 ? 4 : 8));   // taller panels take the device-scope kernel (its own area size)
+    const size_t need = max_over_heights(m, for_driver, [&](int mm) {
+        const int G = x_shape(h, mm, elem).G;
+        return G ? carve_bytes([&](Carver &c) { XArea().lay(c, G, h->panel_debug); }) : (size_t)0;
+    });
+    return (need + 255) & ~(size_t)255;   // a driver takes several, back to back
 }
 
 // Returns 1 when the shape is outside what the kernel serves (caller falls back to the device-scope kernel).
 template <typename T, int RT>
 static int panel_xcd_rt(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info,
                         PanelArgs &pa, const double first_tol = -1.0) {
-    if (jb > PC_COLS) return 1;
-    const int G = (m + 64 * RT - 1) / (64 * RT);
-    if (G > 32 || 8 * G > 8 * h->num_cu) return 1;
-    // exchange area in scratch: status (+ XCC handshake words at +64) | records[2][G] | far granule rows[4][G][128]
-    const size_t rec_bytes = (size_t)2 * G * PX_REC;
-    const size_t need = 256 + rec_bytes + (size_t)4 * G * PC_COLS * sizeof(XGran);
-    const size_t dbg_off = (need + 255) & ~(size_t)255;
-    const size_t total = dbg_off + (h->panel_debug ? (size_t)G * 128 : 0);
-    const bool driver_clears = pa.area_bytes > 0 && !h->panel_debug;
-    const size_t base_off = driver_clears ? pa.area_off : 0;
-    if (base_off + total > h->scratch.bytes || (driver_clears && need > pa.area_bytes)) {
-        set_error("panel_xcd: scratch too small (%zu + %zu > %zu)", base_off, total, h->scratch.bytes);
-        return LSX_ERR_INTERNAL;
-    }
-    char *base = (char *)h->scratch.p + base_off;
-    int *status = (int *)base;
-    int *xcc = (int *)(base + 64);
-    char *rec = base + 256;
-    XGran *far = (XGran *)(base + 256 + rec_bytes);
-    if (!driver_clears) LSX_HIP(hipMemsetAsync(base, 0, h->panel_debug ? total : need, h->stream));
-    unsigned long long *dbg = h->panel_debug ? (unsigned long long *)(base + dbg_off) : nullptr;
+    const int G = x_shape(h, m, sizeof(T)).G;
+    if (jb > PC_COLS || G == 0) return 1;
+    XArea a;
+    LSX_TRY(carve_in(pa.area, pa.area_bytes, "panel_xcd", [&](Carver &c) { a.lay(c, G, h->panel_debug); }));
+    if (!pa.cleared) LSX_HIP(hipMemsetAsync(a.status, 0, a.bytes, h->stream));
     if (first_tol >= 0.0) {   // the reference's first-non-zero rule (fp64, up to 8192 rows: callers check)
         if constexpr (sizeof(T) == 8 && RT <= 4)
             hipLaunchKernelGGL((panel_x_kernel<T, RT, false, true>), dim3(8 * G), dim3(PX_NT), 0, h->stream, m, jb, P, ldp, row0,
-                               col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)pa.list, xcc, pa.xcc_word, h->panel_spin_limit, first_tol);
+                               col0, d_ipiv, d_info, a.rec, a.far, a.status, a.dbg, (int2 *)pa.list, a.xcc, pa.xcc_word, h->panel_spin_limit, first_tol);
         else
             return 1;
     } else if (h->panel_debug)
         hipLaunchKernelGGL((panel_x_kernel<T, RT, true>), dim3(8 * G), dim3(PX_NT), 0, h->stream, m, jb, P, ldp, row0,
-                           col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)pa.list, xcc, pa.xcc_word, h->panel_spin_limit, -1.0);
+                           col0, d_ipiv, d_info, a.rec, a.far, a.status, a.dbg, (int2 *)pa.list, a.xcc, pa.xcc_word, h->panel_spin_limit, -1.0);
     else
         hipLaunchKernelGGL((panel_x_kernel<T, RT, false>), dim3(8 * G), dim3(PX_NT), 0, h->stream, m, jb, P, ldp, row0,
-                           col0, d_ipiv, d_info, rec, far, status, dbg, (int2 *)pa.list, xcc, pa.xcc_word, h->panel_spin_limit, -1.0);
+                           col0, d_ipiv, d_info, a.rec, a.far, a.status, a.dbg, (int2 *)pa.list, a.xcc, pa.xcc_word, h->panel_spin_limit, -1.0);
     LSX_HIP(hipGetLastError());
     pa.listed = true;
     return LSX_OK;
 }
 
-// Rows per lane (RT): as few as the panel's height allows with at most 32 workgroups of 64 RT rows -- 1 up to 2048 rows,
-// 2 up to 4096, 4 up to 8192, and in fp32 (which has the registers) 8 up to 16384.  The owner wave's per-column work
-// (multipliers, update of its block, choice of the next candidate) is proportional to RT and outweighs the dearer
-// all-gather of more workgroups: 4 -> 2 -> 1 took 8192^2 fp64 from 17.1 to 16.6 to 16.3 ms and 4096^2 from 6.95 to
-// 6.36 to 6.23 ms, 8 -> 4 took 8192^2 fp32 from 16.9 to 14.5 ms.  Same arithmetic per element, same pivots.
 template <typename T>
 int panel_xcd(lsx_handle_t h, int m, int jb, T *P, int ldp, int row0, int col0, int32_t *d_ipiv, int *d_info, PanelArgs &pa) {
-    if (m <= 32 * 64 * 1) return panel_xcd_rt<T, 1>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
-    if (m <= 32 * 64 * 2) return panel_xcd_rt<T, 2>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
-    if (sizeof(T) == 4 && m > 32 * 64 * 4) return panel_xcd_rt<T, sizeof(T) == 4 ? 8 : 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
+    const int rt = x_shape(h, m, sizeof(T)).rt;
+    if (rt == 1) return panel_xcd_rt<T, 1>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
+    if (rt == 2) return panel_xcd_rt<T, 2>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
+    if (rt == 8) return panel_xcd_rt<T, sizeof(T) == 4 ? 8 : 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
     return panel_xcd_rt<T, 4>(h, m, jb, P, ldp, row0, col0, d_ipiv, d_info, pa);
 }
 

@@ -171,8 +171,6 @@ template <typename T>
 int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *d_pivots, int *d_rank, double tol,
                  int pivot_rule);
 
-size_t rref_scratch_bytes(int m, int n) { return 256 + 2 * sizeof(double) * (size_t)n + 4096 + 2 * (size_t)m; }
-
 template <typename T>
 int launch_rref(lsx_handle_t h, int m, int n, int bar, T *R, int ldr, int32_t *d_pivots, int *d_rank,
                 double tol, int pivot_rule) {
@@ -181,15 +179,9 @@ int launch_rref(lsx_handle_t h, int m, int n, int bar, T *R, int ldr, int32_t *d
         if (rb != 1) return rb;
     }
     ProfScope ps(h, LSX_PROF_OTHER);
-    // scratch: state | prow[n] | orow[n]
-    const size_t need = 256 + 2 * (size_t)n * sizeof(T);
-    if (need > h->scratch.bytes) {
-        set_error("rref: scratch too small (need %zu)", need);
-        return LSX_ERR_INTERNAL;
-    }
-    RrefState *st = (RrefState *)h->scratch.p;
-    T *prow = (T *)((char *)h->scratch.p + 256);
-    T *orow = prow + n;
+    // scratch (rref_blocked is done with its own): the state and two rows
+    RrefState *st = nullptr; T *prow = nullptr, *orow = nullptr;
+    LSX_TRY(carve(h, h->scratch, [&](Carver &c) { st = c.take<RrefState>(1); prow = c.take<T>(n); orow = c.take<T>(n); }));
     LSX_HIP(hipMemsetAsync(st, 0, sizeof(RrefState), h->stream));
     if (tol < 0 && bar > 0)
         hipLaunchKernelGGL(rref_amax_kernel<T>, dim3(256), dim3(256), 0, h->stream, m, bar, R, ldr, st);

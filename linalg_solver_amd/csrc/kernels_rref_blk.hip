@@ -300,12 +300,9 @@ int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *
     if (pivot_rule != LSX_PIVOT_MAX || (size_t)m * bar < (size_t)256 * 256 || bar < 1) return 1;
     ProfScope ps(h, LSX_PROF_OTHER);
     const int ncand = (m + RRB_ROWS - 1) / RRB_ROWS;
-    // scratch: state | amax | cand_val | cand_idx (2048 + 12 or 16 bytes per row group: within rref_scratch_bytes)
-    if (rref_scratch_bytes(m, n) > h->scratch.bytes) { set_error("rref_blocked: scratch too small"); return LSX_ERR_INTERNAL; }
-    RrbState *st = (RrbState *)h->scratch.p;
-    double *amax = (double *)((char *)h->scratch.p + 1536);
-    T *cand_val = (T *)((char *)h->scratch.p + 2048);
-    int *cand_idx = (int *)((char *)h->scratch.p + 2048 + (((size_t)ncand * sizeof(T) + 15) & ~(size_t)15));
+    // scratch: state and running maximum (cleared together), one pivot candidate per row group
+    RrbState *st = nullptr; double *amax = nullptr; T *cand_val = nullptr; int *cand_idx = nullptr;
+    LSX_TRY(carve(h, h->scratch, [&](Carver &c) { st = c.take<RrbState>(1); amax = c.take<double>(1); cand_val = c.take<T>(ncand); cand_idx = c.take<int>(ncand); }));
     // rhs_work: L / G buffer m x 128, block inverses (two 64 x 64)
     T *L = nullptr, *Tinv = nullptr;
     LSX_TRY(carve(h, h->rhs_work, [&](Carver &c) {
@@ -315,7 +312,7 @@ int rref_blocked(lsx_handle_t h, int m, int n, int bar, T *W, int ldw, int32_t *
     GemmPlan mfma;   // as in the LU drivers: narrow updates on the MFMA kernel too
     mfma.mfma_only = true;
     hipStream_t s = h->stream;
-    LSX_HIP(hipMemsetAsync(h->scratch.p, 0, 2048, s));
+    LSX_HIP(hipMemsetAsync(st, 0, (char *)(amax + 1) - (char *)st, s));
     if (tol < 0) hipLaunchKernelGGL(rrb_amax_kernel<T>, dim3(256), dim3(256), 0, s, m, bar, W, ldw, amax);
     // 32 eps max(m, n): the residue of a dependent column after k elimination steps is ~k eps times the running
     // maximum with a tail; a factor of 1 put exactly-rank-517 integer products of order 1000 at rank 518

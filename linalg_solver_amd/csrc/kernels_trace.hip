@@ -235,15 +235,13 @@ __global__ void trace_result_kernel(const TraceState *st, int *out) {
     if (threadIdx.x == 0) { out[0] = st->npiv; out[1] = st->nsteps; out[2] = st->overflow; }
 }
 
-size_t rref_trace_scratch_bytes() { return 4096; }
-
 // d_out: {number of pivots, number of steps, overflow flag}
 // Tm: m x n bytes (dense): in = which entries are ints, out = which still are; d_snap_t: max_snaps x m x n.
 int launch_rref_trace(lsx_handle_t h, int m, int n, int bar, double *R, int ldr, unsigned char *Tm,
                       int32_t *d_pivots, int32_t *d_steps, int max_steps, double *d_snaps,
                       unsigned char *d_snap_t, int max_snaps, int *d_out) {
-    // the caller (api.hip) has made sure the handle's scratch holds rref_trace_scratch_bytes()
-    TraceState *st = (TraceState *)h->scratch.p;
+    TraceState *st = nullptr;
+    LSX_TRY(carve(h, h->scratch, [&](Carver &c) { st = c.take<TraceState>(1); }));
     hipStream_t s = h->stream;
     const int iters = m < bar ? m : bar;
     const int rows_grid = m < 1024 ? (m > 0 ? m : 1) : 1024;

@@ -356,13 +356,13 @@ static int trsv_coop_run(lsx_handle_t h, int n, const T *LU, int lda, T *B, int 
                          const T *inv64U) {
     const int wgs = (n + CB - 1) / CB;
     {
-        // one launch per direction; exchange area (zeroed) + status word in the scratch
-        const size_t xbytes = (size_t)wgs * CB * NR * sizeof(XGran);
-        if (256 + 2 * xbytes > h->scratch.bytes) { set_error("trsv: scratch too small"); return LSX_ERR_INTERNAL; }
+        // one launch per direction, each with an exchange area (zeroed, in one memset) in scratch: no caller holds a piece of it
+        const size_t xgran = (size_t)wgs * CB * NR;
+        XGran *xb0 = nullptr, *xb1 = nullptr;
+        LSX_TRY(carve(h, h->scratch, [&](Carver &c) { xb0 = c.take<XGran>(xgran); xb1 = c.take<XGran>(xgran); }));
         int *status = h->dev_status + 1;   // persistent word: read (and cleared) by the host entry points / lsx_check_status
         const int spin_limit = h->spin_limit;
-        XGran *xb0 = (XGran *)((char *)h->scratch.p + 256), *xb1 = (XGran *)((char *)h->scratch.p + 256 + xbytes);
-        LSX_HIP(hipMemsetAsync(h->scratch.p, 0, 256 + 2 * xbytes, h->stream));
+        LSX_HIP(hipMemsetAsync(xb0, 0, (char *)(xb1 + xgran) - (char *)xb0, h->stream));
         hipLaunchKernelGGL((trsv_coop_kernel<T, NR, true>), dim3(wgs), dim3(256), 0, h->stream, n, LU, lda, inv64L,
                            (const T *)B, ldb, X, xb0, status, spin_limit);
         LSX_TRY(launch_copy2d<T>(h, n, NR, X, NR, B, ldb));  // y is the right-hand side of U x = y
@@ -897,10 +897,12 @@ int lu_solve_few_rhs2(lsx_handle_t h, int n, int nrhs, int nr, const T *LU, int 
     int H = 1;
     while (2 * H * NB <= h->num_cu && H < 8) H *= 2;     // every workgroup resident at once: one per CU (9 waves of 168 registers)
     if (nr >= 8 && H > 4) H = 4;                           // 8 right-hand sides: the helpers' partial sums are 8 x the traffic
-    const size_t xbytes = (size_t)NB * SB * nr * sizeof(XGran), pbytes = xbytes * H;
-    const size_t need = 2 * (xbytes + pbytes) + 256;
+    // xchg: the owners' x granules and the helpers' partial sums, per direction
+    const size_t xgran = (size_t)NB * SB * nr;
+    XGran *xgL = nullptr, *pgL = nullptr, *xgU = nullptr, *pgU = nullptr;
     bool fresh = false;
-    LSX_TRY(reserve(h, h->xchg, need, &fresh));
+    auto lay = [&](Carver &c) { xgL = c.take<XGran>(xgran); pgL = c.take<XGran>(xgran * H); xgU = c.take<XGran>(xgran); pgU = c.take<XGran>(xgran * H); };
+    LSX_TRY(carve(h, h->xchg, lay, &fresh));
     if (fresh) {   // zeroed: tags of another life of the memory must not pass for this handle's epochs
         LSX_HIP(hipMemsetAsync(h->xchg.p, 0, h->xchg.bytes, h->stream));
         h->xchg_epoch = 0;
@@ -910,8 +912,6 @@ int lu_solve_few_rhs2(lsx_handle_t h, int n, int nrhs, int nr, const T *LU, int 
         h->xchg_epoch = 1;
     }
     ProfScope ps(h, LSX_PROF_TRSM, 2.0 * n * (double)n * nrhs, 2.0 * sizeof(T) * n * (double)n);
-    XGran *xgL = (XGran *)((char *)h->xchg.p + 256), *pgL = (XGran *)((char *)xgL + xbytes);
-    XGran *xgU = (XGran *)((char *)pgL + pbytes), *pgU = (XGran *)((char *)xgU + xbytes);
     int *status = h->dev_status + 1;
     LSX_TRY(launch_trtri_both<T>(h, n, LU, lda, inv64L, inv64U));
     LSX_HIP(hipFuncSetAttribute((const void *)solve_prep_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
@@ -947,9 +947,6 @@ template int lu_solve_few_rhs2<double>(lsx_handle_t, int, int, int, const double
                                        double *, double *, double *, double *, double *, double *);
 template int lu_solve_few_rhs2<float>(lsx_handle_t, int, int, int, const float *, int, const int32_t *, float *, int, float *,
                                       float *, float *, float *, float *, float *);
-
-// (sized for 128-row steps: no less than the 64-row workgroups of trsv_coop_run take)
-size_t few_rhs_scratch_bytes(int n, int nr) { return 512 + 2 * (size_t)((n + 127) / 128) * 128 * nr * sizeof(XGran); }
 
 // X (n x nrhs, dense) <- U^-1 L^-1 B for B already row-permuted; B is used as work space.
 // nrhs must be 1, 2, 4 or 8 (the caller pads).
