@@ -501,6 +501,73 @@ int lsx_podet_f32_dev(lsx_handle_t h, int n, const float *dU, int lda, double *d
 int lsx_podet_f64(lsx_handle_t h, int n, const double *A, int lda, double *sign, double *mant, int64_t *exp2, int *info);
 int lsx_podet_f32(lsx_handle_t h, int n, const float *A, int lda, double *sign, double *mant, int64_t *exp2, int *info);
 
+/* ---- Householder QR and least squares (LAPACK's geqrf, ormqr, orgqr, gels) ---- */
+/* Row-major like everything else: element (i, j) at base[i * ld + j].  Nothing here is cooperative: no kernel waits
+ * for another workgroup, there is no spin and no time-out outcome, lsx_check_status has nothing to report.  Everything
+ * runs on the handle's stream; the _dev forms are asynchronous, the host-buffer forms copy in, compute, copy out and
+ * synchronise.  Any alignment and any leading dimension work and give the same bits; two calls give identical bits.
+ *
+ * lsx_geqrf_*_dev: A (m x n, any m, n >= 0) = Q R with k = min(m, n) reflectors.  On return R lies on and above the
+ * diagonal; reflector j lies below the diagonal of column j with v_jj = 1 implied (LAPACK's layout); d_tau holds k
+ * entries of the matrix's type, H_j = I - tau_j v_j v_j^T, A = H_0 .. H_{k-1} R.
+ * Arithmetic of reflector j, with g_c = sum_{i > j} a_ij a_ic over the rows below it (c = j .. the panel's last column):
+ *     alpha = a_jj,  xnorm^2 = g_j.   g_j == 0: tau_j = 0 and nothing changes (dlarfg).   Otherwise
+ *     beta = -copysign(sqrt(alpha^2 + g_j), alpha),  tau = (beta - alpha) / beta,  s = 1 / (alpha - beta),
+ *     v_i = s a_ij,  w_c = a_jc + s g_c,  a_jc -= tau w_c,  a_ic -= tau v_i w_c,  a_jj = beta.
+ * The sums, their reduction and the scalars are fp64 for both precisions; every stored element is rounded to the
+ * matrix's type once.  Columns right of a 128-column panel receive the block reflector I - V T V^T (T as dlarft forms
+ * it, from V^T V) through the MFMA tiles.
+ * Numeric domain: dlarfg's rescaling loop is not reproduced, so alpha^2 + g_j must be a finite normal number (entries
+ * between about 1e-150 and 1e150 in fp64: the sums are fp64 for fp32 matrices too, whose whole range is therefore
+ * served).  A NaN propagates to what it reaches; nothing faults or loops on it.
+ *
+ * lsx_ormqr_*_dev: C (m x ncols) <- Q^T C (trans = 1) or Q C (trans = 0), left side only, Q = H_0 .. H_{k-1} from the
+ * first k columns of a factored array (lda >= k) and d_tau.  V and T are formed again per 128-reflector block.
+ * lsx_orgqr_*_dev: the thin Q (m x n, k <= n <= m), out of place: Q applied to the leading columns of the identity.
+ * lsx_gels_*_dev: min ||b - A x||_2 for m >= n (m < n is LSX_ERR_ARG: minimum-norm solutions need LQ).  dA is
+ * overwritten by its QR, d_tau (n entries) by the scalars; dB (m x nrhs) is overwritten: rows [0, n) become the
+ * solution, rows [n, m) the tail of Q^T B, whose column norms are the residual norms (dgels's contract).  *d_info (may
+ * be NULL) is 0, or i + 1 for the first r_ii that is exactly zero or NaN; the solution rows are then unspecified.  The
+ * solve with R never loads what lies below the diagonal.
+ * lsx_colnrm2_*_dev: d_out[c] = the 2-norm of column c of A (m x n), n device doubles.  The squares are summed in fp64
+ * in a fixed order, without atomics and without scaling: their sum must not overflow.
+ *
+ * Host forms: lsx_geqrf_*, lsx_ormqr_*, lsx_orgqr_* as above on host buffers.  lsx_gels_*: A (m x n) and B (m x nrhs)
+ * are not modified; X is n x nrhs; resid (host double[nrhs], may be NULL) receives ||b - A x||_2 per column; *info (may
+ * be NULL) as above, and with info > 0 X is not written and resid is +inf.
+ *
+ * LSX_ERR_ARG for negative sizes, lda < n (lda < k where only k columns are read), ldc < ncols, ldq < n, ldb or ldx <
+ * nrhs, k out of range (k > m; for orgqr k > n or n > m), trans other than 0 or 1, or a NULL pointer with non-zero
+ * sizes.  Zero extents are LSX_OK with nothing touched. */
+int lsx_geqrf_f64_dev(lsx_handle_t h, int m, int n, double *dA, int lda, double *d_tau);
+int lsx_geqrf_f32_dev(lsx_handle_t h, int m, int n, float *dA, int lda, float *d_tau);
+int lsx_ormqr_f64_dev(lsx_handle_t h, int trans, int m, int ncols, int k, const double *dQR, int lda, const double *d_tau,
+                      double *dC, int ldc);
+int lsx_ormqr_f32_dev(lsx_handle_t h, int trans, int m, int ncols, int k, const float *dQR, int lda, const float *d_tau,
+                      float *dC, int ldc);
+int lsx_orgqr_f64_dev(lsx_handle_t h, int m, int n, int k, const double *dQR, int lda, const double *d_tau, double *dQ,
+                      int ldq);
+int lsx_orgqr_f32_dev(lsx_handle_t h, int m, int n, int k, const float *dQR, int lda, const float *d_tau, float *dQ,
+                      int ldq);
+int lsx_gels_f64_dev(lsx_handle_t h, int m, int n, int nrhs, double *dA, int lda, double *d_tau, double *dB, int ldb,
+                     int *d_info);
+int lsx_gels_f32_dev(lsx_handle_t h, int m, int n, int nrhs, float *dA, int lda, float *d_tau, float *dB, int ldb,
+                     int *d_info);
+int lsx_colnrm2_f64_dev(lsx_handle_t h, int m, int n, const double *dA, int lda, double *d_out);
+int lsx_colnrm2_f32_dev(lsx_handle_t h, int m, int n, const float *dA, int lda, double *d_out);
+int lsx_geqrf_f64(lsx_handle_t h, int m, int n, double *A, int lda, double *tau);
+int lsx_geqrf_f32(lsx_handle_t h, int m, int n, float *A, int lda, float *tau);
+int lsx_ormqr_f64(lsx_handle_t h, int trans, int m, int ncols, int k, const double *QR, int lda, const double *tau, double *C,
+                  int ldc);
+int lsx_ormqr_f32(lsx_handle_t h, int trans, int m, int ncols, int k, const float *QR, int lda, const float *tau, float *C,
+                  int ldc);
+int lsx_orgqr_f64(lsx_handle_t h, int m, int n, int k, const double *QR, int lda, const double *tau, double *Q, int ldq);
+int lsx_orgqr_f32(lsx_handle_t h, int m, int n, int k, const float *QR, int lda, const float *tau, float *Q, int ldq);
+int lsx_gels_f64(lsx_handle_t h, int m, int n, int nrhs, const double *A, int lda, const double *B, int ldb, double *X, int ldx,
+                 double *resid, int *info);
+int lsx_gels_f32(lsx_handle_t h, int m, int n, int nrhs, const float *A, int lda, const float *B, int ldb, float *X, int ldx,
+                 double *resid, int *info);
+
 /* ---- Cholesky: condition estimate and error bounds (LAPACK's lansy, pocon, porfs) ---- */
 /* Storage as above: row-major, UPPER, A = U^T U.  The strictly lower triangle of A and of U is never loaded and never
  * written by any of these, inside a diagonal tile or block included: it may hold NaN.  Nothing here is cooperative: no

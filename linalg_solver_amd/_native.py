@@ -156,6 +156,24 @@ _SIGS = {
     "lsx_podet_f32_dev": [_vp, _i, _vp, _i, _vp],
     "lsx_podet_f64": [_vp, _i, _dp, _i, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(_i)],
     "lsx_podet_f32": [_vp, _i, _fp, _i, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(_i)],
+    "lsx_geqrf_f64_dev": [_vp, _i, _i, _vp, _i, _vp],
+    "lsx_geqrf_f32_dev": [_vp, _i, _i, _vp, _i, _vp],
+    "lsx_ormqr_f64_dev": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_ormqr_f32_dev": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_orgqr_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_orgqr_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i],
+    "lsx_gels_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp],
+    "lsx_gels_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp],
+    "lsx_colnrm2_f64_dev": [_vp, _i, _i, _vp, _i, _vp],
+    "lsx_colnrm2_f32_dev": [_vp, _i, _i, _vp, _i, _vp],
+    "lsx_geqrf_f64": [_vp, _i, _i, _dp, _i, _dp],
+    "lsx_geqrf_f32": [_vp, _i, _i, _fp, _i, _fp],
+    "lsx_ormqr_f64": [_vp, _i, _i, _i, _i, _dp, _i, _dp, _dp, _i],
+    "lsx_ormqr_f32": [_vp, _i, _i, _i, _i, _fp, _i, _fp, _fp, _i],
+    "lsx_orgqr_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _dp, _i],
+    "lsx_orgqr_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _fp, _i],
+    "lsx_gels_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, _dp, C.POINTER(_i)],
+    "lsx_gels_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, _dp, C.POINTER(_i)],
     "lsx_matmul_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i],
     "lsx_fill_f64_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],
     "lsx_fill_f32_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],

@@ -1234,6 +1234,221 @@ static int podet_host(lsx_handle_t h, int n, const T *A, int lda, double *sign, 
     return LSX_OK;
 }
 
+// ---------------------------------------------------------------- Householder QR: A = Q R, row-major (kernels_qr.hip)
+// Right-looking over 128-column panels on one stream, no look-ahead, nothing cooperative:
+//   panel kb: columns [kb, kb + jb), rows [kb, m): jb + 1 launches over row slabs                     [PANEL]
+//   V (explicit ones and zeros), G = V^T V on the TN tile, T from G and tau (dlarft)                 [TRSM]
+//   block apply  W = V^T C,  W <- T^T W (Q^T) or T W (Q),  C -= V W  on the existing tiles           [GEMM]
+// geqrf applies Q^T of a panel to the columns right of it; ormqr and orgqr form V and T again per block from the
+// factored array and tau, as LAPACK does.  qr_work is laid out here, from its start, by whoever runs blocks.
+template <typename T>
+struct QrWork {
+    T *V = nullptr, *G = nullptr, *Tm = nullptr, *Tt = nullptr, *W = nullptr, *W2 = nullptr, *prow = nullptr;
+    double *slots = nullptr;
+    int ldw = 0;
+};
+template <typename T>
+static int carve_qr(lsx_handle_t h, int m, int nc, QrWork<T> *w) {
+    w->ldw = ld_for(nc > 0 ? nc : 1);
+    return carve(h, h->qr_work, [&](Carver &c) {
+        w->V = c.take<T>((size_t)m * 128);
+        w->G = c.take<T>((size_t)128 * 128);
+        w->Tm = c.take<T>((size_t)128 * 128);
+        w->Tt = c.take<T>((size_t)128 * 128);
+        w->W = c.take<T>((size_t)128 * w->ldw);
+        w->W2 = c.take<T>((size_t)128 * w->ldw);
+        w->prow = c.take<T>((size_t)2 * 128);
+        w->slots = c.take<double>(qr_slot_elems());
+    });
+}
+// V and T of the block whose reflectors lie below the diagonal of P (mp x jb) with scalars tau
+template <typename T>
+static int qr_block_form(lsx_handle_t h, int mp, int jb, const T *P, int ldp, const T *tau, const QrWork<T> &w) {
+    LSX_TRY(launch_qr_extract_v<T>(h, mp, jb, P, ldp, w.V));
+    LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, jb, mp, w.V, 128, w.V, 128, w.G, 128, LSX_PROF_TRSM));
+    return launch_qr_larft<T>(h, jb, w.G, tau, w.Tm, w.Tt);
+}
+// C (mp x nc) <- H^T C (trans) or H C, H = I - V T V^T
+template <typename T>
+static int qr_block_apply(lsx_handle_t h, int trans, int mp, int jb, int nc, const QrWork<T> &w, T *C, int ldc) {
+    LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nc, mp, w.V, 128, C, ldc, w.W, w.ldw));
+    LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nc, jb, trans ? w.Tm : w.Tt, 128, w.W, w.ldw, w.W2, w.ldw));
+    return launch_gemm_sub<T>(h, mp, nc, jb, w.V, 128, w.W2, w.ldw, C, ldc);
+}
+
+template <typename T>
+static int geqrf_dev(lsx_handle_t h, int m, int n, T *A, int lda, T *d_tau) {
+    LSX_ARG(h && m >= 0 && n >= 0 && lda >= n);
+    const int k = m < n ? m : n;
+    if (k == 0) return LSX_OK;
+    LSX_ARG(A && d_tau);
+    QrWork<T> w;
+    LSX_TRY(carve_qr<T>(h, m, n, &w));
+    for (int kb = 0; kb < k; kb += 128) {
+        const int jb = (k - kb < 128) ? k - kb : 128, mp = m - kb, rest = n - kb - jb;
+        T *P = A + (size_t)kb * lda + kb;
+        LSX_TRY(launch_qr_panel<T>(h, mp, jb, P, lda, d_tau + kb, w.slots, w.prow));
+        if (rest <= 0) continue;
+        LSX_TRY(qr_block_form<T>(h, mp, jb, P, lda, d_tau + kb, w));
+        LSX_TRY(qr_block_apply<T>(h, 1, mp, jb, rest, w, P + jb, lda));
+    }
+    return LSX_OK;
+}
+
+// C (m x ncols) <- Q^T C (trans = 1: the blocks forward) or Q C (trans = 0: backward), Q = H_0 .. H_{k-1}
+template <typename T>
+static int ormqr_dev(lsx_handle_t h, int trans, int m, int ncols, int k, const T *QR, int lda, const T *d_tau, T *C, int ldc) {
+    LSX_ARG(h && (trans == 0 || trans == 1) && m >= 0 && ncols >= 0 && k >= 0 && k <= m && lda >= k && ldc >= ncols);
+    if (m == 0 || ncols == 0 || k == 0) return LSX_OK;
+    LSX_ARG(QR && d_tau && C);
+    QrWork<T> w;
+    LSX_TRY(carve_qr<T>(h, m, ncols, &w));
+    const int last = (k - 1) / 128 * 128;
+    for (int b = 0; b <= last; b += 128) {
+        const int kb = trans ? b : last - b;
+        const int jb = (k - kb < 128) ? k - kb : 128, mp = m - kb;
+        LSX_TRY(qr_block_form<T>(h, mp, jb, QR + (size_t)kb * lda + kb, lda, d_tau + kb, w));
+        LSX_TRY(qr_block_apply<T>(h, trans, mp, jb, ncols, w, C + (size_t)kb * ldc, ldc));
+    }
+    return LSX_OK;
+}
+
+// the thin Q (m x n, k <= n <= m), out of place: Q applied to the leading columns of the identity
+template <typename T>
+static int orgqr_dev(lsx_handle_t h, int m, int n, int k, const T *QR, int lda, const T *d_tau, T *Q, int ldq) {
+    LSX_ARG(h && m >= 0 && n >= 0 && k >= 0 && k <= n && n <= m && lda >= k && ldq >= n);
+    if (m == 0 || n == 0) return LSX_OK;
+    LSX_ARG(Q && (k == 0 || (QR && d_tau)));
+    LSX_TRY(launch_qr_identity<T>(h, m, n, Q, ldq));
+    return ormqr_dev<T>(h, 0, m, n, k, QR, lda, d_tau, Q, ldq);
+}
+
+template <typename T>
+static int colnrm2_dev(lsx_handle_t h, int m, int n, const T *dA, int lda, double *d_out) {
+    LSX_ARG(h && m >= 0 && n >= 0 && lda >= n);
+    if (m == 0 || n == 0) return LSX_OK;
+    LSX_ARG(dA && d_out);
+    return launch_colnrm2<T>(h, m, n, dA, lda, d_out);
+}
+
+// min ||b - A x||_2 for m >= n: geqrf, Q^T B, the info word (the first r_ii that is zero or NaN), then R X = (Q^T B)[0:n]
+// in place on the leading rows of B: the block inverses of R come from its upper triangle alone (launch_chol_inv), and
+// sweep_backward reads the blocks on and above the diagonal blocks only -- what lies below the diagonal is V.
+template <typename T>
+static int gels_dev(lsx_handle_t h, int m, int n, int nrhs, T *A, int lda, T *d_tau, T *B, int ldb, int *d_info) {
+    LSX_ARG(h && m >= 0 && n >= 0 && nrhs >= 0 && m >= n && lda >= n && ldb >= nrhs);
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(A && d_tau && B);
+    LSX_TRY(geqrf_dev<T>(h, m, n, A, lda, d_tau));
+    LSX_TRY(ormqr_dev<T>(h, 1, m, nrhs, n, A, lda, d_tau, B, ldb));
+    if (d_info) LSX_TRY(launch_diag_zero_info<T>(h, n, A, lda, d_info));
+    T *inv64 = nullptr, *inv128 = nullptr;
+    LSX_TRY(carve(h, h->tinv, [&](Carver &c) { inv64 = c.take<T>(inv64_elems(n)); inv128 = c.take<T>(inv128_elems(n)); }));
+    LSX_TRY(launch_chol_inv<T>(h, n, A, lda, inv64, inv128));
+    return sweep_backward<T>(h, n, nrhs, sweep_pairs(h, n, nrhs), A, lda, inv64, B, ldb);
+}
+
+template <typename T>
+static int geqrf_host(lsx_handle_t h, int m, int n, T *A, int lda, T *tau) {
+    LSX_ARG(h && m >= 0 && n >= 0 && lda >= n);
+    const int k = m < n ? m : n;
+    if (k == 0) return LSX_OK;
+    LSX_ARG(A && tau);
+    const int ld = ld_for(n);
+    T *dA = nullptr, *dtau = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) { dA = c.take<T>((size_t)m * ld); dtau = c.take<T>(k); }));
+    LSX_TRY(h2d<T>(h, m, n, A, lda, dA, ld));
+    LSX_TRY(geqrf_dev<T>(h, m, n, dA, ld, dtau));
+    LSX_TRY(d2h<T>(h, m, n, dA, ld, A, lda));
+    LSX_HIP(hipMemcpyAsync(tau, dtau, sizeof(T) * k, hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+template <typename T>
+static int ormqr_host(lsx_handle_t h, int trans, int m, int ncols, int k, const T *QR, int lda, const T *tau, T *C, int ldc) {
+    LSX_ARG(h && (trans == 0 || trans == 1) && m >= 0 && ncols >= 0 && k >= 0 && k <= m && lda >= k && ldc >= ncols);
+    if (m == 0 || ncols == 0 || k == 0) return LSX_OK;
+    LSX_ARG(QR && tau && C);
+    const int ld = ld_for(k), ldx = ld_for(ncols);
+    T *dQR = nullptr, *dtau = nullptr, *dC = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dQR = c.take<T>((size_t)m * ld);
+        dtau = c.take<T>(k);
+        dC = c.take<T>((size_t)m * ldx);
+    }));
+    LSX_TRY(h2d<T>(h, m, k, QR, lda, dQR, ld));
+    LSX_HIP(hipMemcpyAsync(dtau, tau, sizeof(T) * k, hipMemcpyHostToDevice, h->stream));
+    LSX_TRY(h2d<T>(h, m, ncols, C, ldc, dC, ldx));
+    LSX_TRY(ormqr_dev<T>(h, trans, m, ncols, k, dQR, ld, dtau, dC, ldx));
+    LSX_TRY(d2h<T>(h, m, ncols, dC, ldx, C, ldc));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+template <typename T>
+static int orgqr_host(lsx_handle_t h, int m, int n, int k, const T *QR, int lda, const T *tau, T *Q, int ldq) {
+    LSX_ARG(h && m >= 0 && n >= 0 && k >= 0 && k <= n && n <= m && lda >= k && ldq >= n);
+    if (m == 0 || n == 0) return LSX_OK;
+    LSX_ARG(Q && (k == 0 || (QR && tau)));
+    const int ld = ld_for(k > 0 ? k : 1), ldx = ld_for(n);
+    T *dQR = nullptr, *dtau = nullptr, *dQ = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dQR = c.take<T>((size_t)m * ld);
+        dtau = c.take<T>(k > 0 ? k : 1);
+        dQ = c.take<T>((size_t)m * ldx);
+    }));
+    if (k > 0) {
+        LSX_TRY(h2d<T>(h, m, k, QR, lda, dQR, ld));
+        LSX_HIP(hipMemcpyAsync(dtau, tau, sizeof(T) * k, hipMemcpyHostToDevice, h->stream));
+    }
+    LSX_TRY(orgqr_dev<T>(h, m, n, k, dQR, ld, dtau, dQ, ldx));
+    LSX_TRY(d2h<T>(h, m, n, dQ, ldx, Q, ldq));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+// A and B are not modified; X (n x nrhs) and resid[nrhs] (may be NULL) are written only when info == 0
+template <typename T>
+static int gels_host(lsx_handle_t h, int m, int n, int nrhs, const T *A, int lda, const T *B, int ldb, T *X, int ldx,
+                     double *resid, int *info) {
+    LSX_ARG(h && m >= 0 && n >= 0 && nrhs >= 0 && m >= n && lda >= n && ldb >= nrhs && ldx >= nrhs);
+    if (info) *info = 0;
+    if (n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(A && B && X);
+    const int ld = ld_for(n), ldr = ld_for(nrhs);
+    T *dA = nullptr, *dtau = nullptr, *dB = nullptr; int *dinfo = nullptr; double *dres = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)m * ld);
+        dtau = c.take<T>(n);
+        dB = c.take<T>((size_t)m * ldr);
+        dinfo = c.take<int>(1);
+        dres = c.take<double>(nrhs);
+    }));
+    int hinfo = 0;
+    LSX_TRY(h2d<T>(h, m, n, A, lda, dA, ld));
+    LSX_TRY(h2d<T>(h, m, nrhs, B, ldb, dB, ldr));
+    LSX_TRY(gels_dev<T>(h, m, n, nrhs, dA, ld, dtau, dB, ldr, dinfo));
+    LSX_HIP(hipMemcpyAsync(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    if (info) *info = hinfo;
+    if (hinfo != 0) {
+        if (resid) for (int j = 0; j < nrhs; ++j) resid[j] = INFINITY;
+        return LSX_OK;
+    }
+    LSX_TRY(d2h<T>(h, n, nrhs, dB, ldr, X, ldx));
+    if (resid) {
+        if (m > n) {
+            LSX_TRY(colnrm2_dev<T>(h, m - n, nrhs, dB + (size_t)n * ldr, ldr, dres));
+            LSX_HIP(hipMemcpyAsync(resid, dres, sizeof(double) * nrhs, hipMemcpyDeviceToHost, h->stream));
+        } else {
+            for (int j = 0; j < nrhs; ++j) resid[j] = 0.0;
+        }
+    }
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
 // A^T X = B from the factors (kernels_trsvt.hip).  Work space as in getrs_dev, so the two share what they grow.
 // may_block = false: the single-column solves inside the estimators, which keep the grouped path whatever the option says.
 template <typename T>
@@ -2085,7 +2300,7 @@ int lsx_destroy(lsx_handle_t h) {
     for (auto &ev : h->prof.pending) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &e : h->prof.pool) (void)hipEventDestroy(e);
     for (DevBuf *b : {&h->staging, &h->tinv, &h->rhs_work, &h->mixed_resid, &h->getri_work, &h->rref_first, &h->cond,
-                      &h->refine, &h->equil, &h->xchg, &h->moves_all, &h->scratch})
+                      &h->refine, &h->equil, &h->qr_work, &h->xchg, &h->moves_all, &h->scratch})
         if (b->p) (void)hipFree(b->p);
     if (h->moves_buf[0]) (void)hipFree(h->moves_buf[0]);
     if (h->dev_status) (void)hipFree(h->dev_status);
@@ -3068,6 +3283,53 @@ LSX_POSX_ENTRIES(f32, float)
 LSX_CHOL_ENTRIES(f64, double)
 LSX_CHOL_ENTRIES(f32, float)
 #undef LSX_CHOL_ENTRIES
+
+// ---- Householder QR and least squares
+#define LSX_QR_ENTRIES(SFX, T)                                                                                            \
+    int lsx_geqrf_##SFX##_dev(lsx_handle_t h, int m, int n, T *dA, int lda, T *d_tau) {                                   \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return geqrf_dev<T>(h, m, n, dA, lda, d_tau);                                                                     \
+    }                                                                                                                     \
+    int lsx_ormqr_##SFX##_dev(lsx_handle_t h, int trans, int m, int ncols, int k, const T *dQR, int lda, const T *d_tau,  \
+                              T *dC, int ldc) {                                                                           \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return ormqr_dev<T>(h, trans, m, ncols, k, dQR, lda, d_tau, dC, ldc);                                             \
+    }                                                                                                                     \
+    int lsx_orgqr_##SFX##_dev(lsx_handle_t h, int m, int n, int k, const T *dQR, int lda, const T *d_tau, T *dQ,          \
+                              int ldq) {                                                                                  \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return orgqr_dev<T>(h, m, n, k, dQR, lda, d_tau, dQ, ldq);                                                        \
+    }                                                                                                                     \
+    int lsx_gels_##SFX##_dev(lsx_handle_t h, int m, int n, int nrhs, T *dA, int lda, T *d_tau, T *dB, int ldb,            \
+                             int *d_info) {                                                                               \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return gels_dev<T>(h, m, n, nrhs, dA, lda, d_tau, dB, ldb, d_info);                                               \
+    }                                                                                                                     \
+    int lsx_colnrm2_##SFX##_dev(lsx_handle_t h, int m, int n, const T *dA, int lda, double *d_out) {                      \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return colnrm2_dev<T>(h, m, n, dA, lda, d_out);                                                                   \
+    }                                                                                                                     \
+    int lsx_geqrf_##SFX(lsx_handle_t h, int m, int n, T *A, int lda, T *tau) {                                            \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return geqrf_host<T>(h, m, n, A, lda, tau);                                                                       \
+    }                                                                                                                     \
+    int lsx_ormqr_##SFX(lsx_handle_t h, int trans, int m, int ncols, int k, const T *QR, int lda, const T *tau, T *C,     \
+                        int ldc) {                                                                                        \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return ormqr_host<T>(h, trans, m, ncols, k, QR, lda, tau, C, ldc);                                                \
+    }                                                                                                                     \
+    int lsx_orgqr_##SFX(lsx_handle_t h, int m, int n, int k, const T *QR, int lda, const T *tau, T *Q, int ldq) {         \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return orgqr_host<T>(h, m, n, k, QR, lda, tau, Q, ldq);                                                           \
+    }                                                                                                                     \
+    int lsx_gels_##SFX(lsx_handle_t h, int m, int n, int nrhs, const T *A, int lda, const T *B, int ldb, T *X, int ldx,   \
+                       double *resid, int *info) {                                                                        \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return gels_host<T>(h, m, n, nrhs, A, lda, B, ldb, X, ldx, resid, info);                                          \
+    }
+LSX_QR_ENTRIES(f64, double)
+LSX_QR_ENTRIES(f32, float)
+#undef LSX_QR_ENTRIES
 
 int lsx_fill_f64_dev(lsx_handle_t h, int kind, uint64_t seed, int m, int n, double *dA, int lda,
                      int row_off, int col_off) {

@@ -145,6 +145,9 @@ struct lsx_handle_s {
     //                             128-row strip); getri_dev and potri_dev each lay getri_work out from its start
     //   potrs_few_prepare         tinv, rhs_work, in a PotrsFew that pocon_dev / porfs_dev keep across all their
     //                             potrs_few_apply calls: they call nothing else that grows these two
+    //   geqrf_dev, ormqr_dev      qr_work, each laid out from its start by carve_qr; neither keeps a piece across the other
+    //   orgqr_dev                 nothing of its own: the identity, then ormqr_dev
+    //   gels_dev                  tinv (block inverses of R), after geqrf_dev and ormqr_dev are done with qr_work
     //   gecon_dev, pocon_dev      cond, across getrs_dev / getrs_t_dev and potrs_few_*
     //   refine_loop               refine, across getrs_dev / getrs_t_dev (gerfs_dev) and potrs_few_apply (porfs_dev)
     //   gesvx_dev                 equil, across geequ_dev (equil again, never more than gesvx_dev carved), lange_dev
@@ -168,6 +171,7 @@ struct lsx_handle_s {
     DevBuf cond;         // condition estimators (gecon, pocon): iteration vector, sign vector, record, identity interchanges
     DevBuf refine;       // refinement loop (gerfs, porfs): residual and bound of a group, two vectors, records, partial sums
     DevBuf equil;        // equilibration (geequ, gesvx): the drivers' records, then row maxima and partial column maxima
+    DevBuf qr_work;      // Householder QR: V, V^T V, T and its transpose, the two W strips, partial-sum slots, pivot rows
     DevBuf xchg;         // few-RHS solve (kernels_trsv.hip, third form): exchange granules validated by an epoch, never cleared
     unsigned xchg_epoch = 0;
     DevBuf moves_all;    // look-ahead driver with the XCD-scope panel: one gather list per panel
@@ -537,5 +541,21 @@ int launch_trsvt_forward_upper(lsx_handle_t h, int n, int nr, int w, const T *U,
 template <typename T>
 int launch_posx_backward(lsx_handle_t h, int n, int nr, int w, const T *U, int lda, const T *inv128, T *W, T *B, int ldb,
                          int c0);
+// Householder QR (kernels_qr.hip).  launch_qr_panel: the jb <= 128 reflectors of a panel of mp >= jb rows, jb + 1 plain
+// launches over row slabs; slots = qr_slot_elems() doubles (two sets of per-slab partial sums in turn), prow = 2 x 128
+// elements (the copied pivot row, two in turn); tau receives jb entries.  launch_qr_extract_v: V (mp x 128, dense) =
+// the panel's unit lower trapezoid, zero columns beyond jb.  launch_qr_larft: T (and its transpose, both 128 x 128,
+// zero outside the triangle) from G = V^T V and tau.  launch_colnrm2: lsx_colnrm2_*_dev.
+size_t qr_slot_elems();
+template <typename T>
+int launch_qr_panel(lsx_handle_t h, int mp, int jb, T *P, int ldp, T *tau, double *slots, T *prow);
+template <typename T>
+int launch_qr_extract_v(lsx_handle_t h, int mp, int jb, const T *P, int ldp, T *V);
+template <typename T>
+int launch_qr_larft(lsx_handle_t h, int jb, const T *G, const T *tau, T *Tm, T *Tt);
+template <typename T>
+int launch_qr_identity(lsx_handle_t h, int m, int n, T *Q, int ldq);
+template <typename T>
+int launch_colnrm2(lsx_handle_t h, int m, int n, const T *A, int lda, double *out);
 
 }  // namespace lsx

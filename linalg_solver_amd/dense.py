@@ -106,6 +106,85 @@ def cho_inverse(U: np.ndarray, handle: Optional[N.Handle] = None) -> np.ndarray:
     return X + np.triu(X, 1).T
 
 
+def qr_factor(a, dtype=np.float64, handle: Optional[N.Handle] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Householder QR of an m x n matrix (lsx_geqrf_*).  Returns (QR, tau) in LAPACK's layout: R on and above the
+    diagonal, reflector j below the diagonal of column j (v_jj = 1 implied), tau of length min(m, n)."""
+    ct, sfx = _ct(dtype)
+    QR = np.array(a, dtype=dtype, order="C", copy=True)
+    if QR.ndim != 2:
+        raise ValueError("qr_factor needs a matrix")
+    m, n = QR.shape
+    tau = np.zeros(min(m, n), dtype=dtype)
+    if min(m, n):
+        h = _h(handle)
+        N.check(getattr(h.lib, f"lsx_geqrf_{sfx}")(h.ptr, m, n, _ptr(QR, ct), n, _ptr(tau, ct)), f"lsx_geqrf_{sfx}")
+    return QR, tau
+
+
+def qr_multiply(QR: np.ndarray, tau: np.ndarray, c, trans: bool = True, handle: Optional[N.Handle] = None) -> np.ndarray:
+    """Q^T c (trans=True) or Q c from the result of qr_factor, Q = H_0 .. H_{k-1} with k = len(tau) (lsx_ormqr_*)."""
+    QR = np.ascontiguousarray(QR)
+    if QR.ndim != 2:
+        raise ValueError("qr_multiply needs the factored matrix")
+    ct, sfx = _ct(QR.dtype)
+    m, k = QR.shape[0], len(tau)
+    if np.shape(c)[:1] != (m,):
+        raise ValueError("qr_multiply: c has the wrong number of rows")
+    tau = np.ascontiguousarray(tau, dtype=QR.dtype)
+    X = np.array(c, dtype=QR.dtype, order="C", copy=True)
+    vec = X.ndim == 1
+    if vec:
+        X = X.reshape(m, 1).copy()
+    if m and k and X.shape[1]:
+        h = _h(handle)
+        N.check(getattr(h.lib, f"lsx_ormqr_{sfx}")(h.ptr, 1 if trans else 0, m, X.shape[1], k, _ptr(QR, ct), QR.shape[1],
+                                                  _ptr(tau, ct), _ptr(X, ct), X.shape[1]), f"lsx_ormqr_{sfx}")
+    return X[:, 0].copy() if vec else X
+
+
+def qr(a, dtype=np.float64, handle: Optional[N.Handle] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(Q, R) of an m x n matrix with m >= n: the thin Q (m x n, lsx_orgqr_*) and the n x n upper triangular R."""
+    QR, tau = qr_factor(a, dtype=dtype, handle=handle)
+    m, n = QR.shape
+    if m < n:
+        raise ValueError("qr needs a matrix with at least as many rows as columns")
+    ct, sfx = _ct(dtype)
+    Q = np.zeros((m, n), dtype=dtype)
+    if n:
+        h = _h(handle)
+        N.check(getattr(h.lib, f"lsx_orgqr_{sfx}")(h.ptr, m, n, n, _ptr(QR, ct), n, _ptr(tau, ct), _ptr(Q, ct), n),
+                f"lsx_orgqr_{sfx}")
+    return Q, np.triu(QR[:n, :])
+
+
+def lstsq(a, b, dtype=np.float64, handle: Optional[N.Handle] = None):
+    """Least-squares solution of an overdetermined system through Householder QR (lsx_gels_*): min ||b - a x||_2 for an
+    m x n matrix with m >= n.  Returns (x, resid, info): resid holds ||b - a x||_2 per right-hand side; info = i + 1
+    says r_ii is zero or NaN (a does not have full column rank to working precision): x is then None and resid +inf."""
+    ct, sfx = _ct(dtype)
+    A = np.array(a, dtype=dtype, order="C", copy=True)
+    if A.ndim != 2 or A.shape[0] < A.shape[1]:
+        raise ValueError("lstsq needs a matrix with at least as many rows as columns")
+    m, n = A.shape
+    if np.shape(b)[:1] != (m,):
+        raise ValueError("right-hand side has the wrong number of rows")
+    B = np.array(b, dtype=dtype, order="C", copy=True)
+    vec = B.ndim == 1
+    if vec:
+        B = B.reshape(m, 1).copy()
+    nrhs = B.shape[1]
+    X = np.zeros((n, nrhs), dtype=dtype)
+    resid = np.zeros(nrhs, dtype=np.float64)
+    info = C.c_int(0)
+    if n and nrhs:
+        h = _h(handle)
+        N.check(getattr(h.lib, f"lsx_gels_{sfx}")(h.ptr, m, n, nrhs, _ptr(A, ct), n, _ptr(B, ct), nrhs, _ptr(X, ct), nrhs,
+                                                 _ptr(resid, C.c_double), C.byref(info)), f"lsx_gels_{sfx}")
+    if info.value != 0:
+        return None, (resid[0] if vec else resid), info.value
+    return (X[:, 0].copy() if vec else X), (float(resid[0]) if vec else resid), 0
+
+
 def _norm_code(which) -> int:
     """1 / "1" / "one" -> the 1-norm (max column sum); inf / "inf" / "I" -> the infinity-norm (max row sum)."""
     if which in (1, "1", "one", "O", "o"):

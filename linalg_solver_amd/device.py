@@ -180,6 +180,92 @@ class DeviceSolver:
         N.check(getattr(self.lib, name)(self.h.ptr, n, U.data_ptr(), max(U.stride(0), 1), out.data_ptr()), name)
         return out
 
+    # -- Householder QR and least squares
+    def _tau(self, A: torch.Tensor, tau: Optional[torch.Tensor], k: int, what: str) -> torch.Tensor:
+        if tau is None:
+            return torch.zeros(max(k, 1), dtype=A.dtype, device=A.device)
+        if tau.dtype != A.dtype or tau.device != A.device or tau.dim() != 1 or tau.numel() < k or \
+                (tau.numel() > 1 and tau.stride(0) != 1):
+            raise ValueError(f"{what}: tau must be a dense vector of the matrix's dtype and device with at least {k} entries")
+        return tau
+
+    def geqrf_(self, A: torch.Tensor, tau: Optional[torch.Tensor] = None):
+        """In-place Householder QR of A (m x n) in HBM (lsx_geqrf_*_dev): R on and above the diagonal, reflector j below
+        the diagonal of column j.  Returns tau (min(m, n) entries of A's dtype); no host sync."""
+        _rowmajor(A, "geqrf_")
+        m, n = A.shape
+        tau = self._tau(A, tau, min(m, n), "geqrf_")
+        name = f"lsx_geqrf_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, m, n, A.data_ptr(), max(A.stride(0), 1), tau.data_ptr()), name)
+        return tau
+
+    def ormqr_(self, QR: torch.Tensor, tau: torch.Tensor, C: torch.Tensor, trans: bool = True):
+        """C <- Q^T C (trans=True) or Q C in place, Q from the first len(tau) reflectors of geqrf_'s result
+        (lsx_ormqr_*_dev)."""
+        _rowmajor(QR, "ormqr_ QR")
+        _rowmajor(C, "ormqr_ C")
+        k = min(tau.numel(), QR.shape[0], QR.shape[1])
+        if C.shape[0] != QR.shape[0]:
+            raise ValueError("ormqr_: C needs as many rows as the factored matrix")
+        if C.dtype != QR.dtype:
+            raise TypeError("ormqr_: both operands must have the same dtype")
+        tau = self._tau(QR, tau, k, "ormqr_")
+        name = f"lsx_ormqr_{self._suffix(QR)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, 1 if trans else 0, QR.shape[0], C.shape[1], k, QR.data_ptr(),
+                                        max(QR.stride(0), 1), tau.data_ptr(), C.data_ptr(), max(C.stride(0), 1)), name)
+        return C
+
+    def orgqr(self, QR: torch.Tensor, tau: torch.Tensor, out: Optional[torch.Tensor] = None):
+        """The thin Q (m x n, m >= n) of geqrf_'s result, out of place (lsx_orgqr_*_dev)."""
+        _rowmajor(QR, "orgqr")
+        m, n = QR.shape
+        if m < n:
+            raise ValueError("orgqr: the thin Q needs at least as many rows as columns")
+        if out is None:
+            out = torch.empty((m, n), dtype=QR.dtype, device=QR.device)
+        _rowmajor(out, "orgqr out")
+        if tuple(out.shape) != (m, n) or out.dtype != QR.dtype:
+            raise ValueError("orgqr: out must have the shape and dtype of the factored matrix")
+        k = min(tau.numel(), n)
+        tau = self._tau(QR, tau, k, "orgqr")
+        name = f"lsx_orgqr_{self._suffix(QR)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, m, n, k, QR.data_ptr(), max(QR.stride(0), 1), tau.data_ptr(),
+                                        out.data_ptr(), max(out.stride(0), 1)), name)
+        return out
+
+    def gels_(self, A: torch.Tensor, B: torch.Tensor, tau: Optional[torch.Tensor] = None,
+              info: Optional[torch.Tensor] = None):
+        """Least squares in place for m >= n (lsx_gels_*_dev): A becomes its QR, rows [0, n) of B the solution, rows
+        [n, m) the tail of Q^T B (col_norms of it gives the residual norms).  Returns (tau, info): info is 0, or
+        i + 1 for the first r_ii that is zero or NaN; no host sync."""
+        _rowmajor(A, "gels_ A")
+        _rowmajor(B, "gels_ B")
+        m, n = A.shape
+        if m < n:
+            raise ValueError("gels_: needs at least as many rows as columns")
+        if B.shape[0] != m:
+            raise ValueError("gels_: B needs as many rows as A")
+        if B.dtype != A.dtype:
+            raise TypeError("gels_: both operands must have the same dtype")
+        tau = self._tau(A, tau, n, "gels_")
+        if info is None:
+            info = torch.zeros(1, dtype=torch.int32, device=A.device)
+        elif info.dtype != torch.int32 or info.device != A.device or info.numel() < 1 or not info.is_contiguous():
+            raise ValueError("gels_: info must be a contiguous int32 tensor with at least one entry on A's device")
+        name = f"lsx_gels_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, m, n, B.shape[1], A.data_ptr(), max(A.stride(0), 1), tau.data_ptr(),
+                                        B.data_ptr(), max(B.stride(0), 1), info.data_ptr()), name)
+        return tau, info
+
+    def col_norms(self, A: torch.Tensor) -> torch.Tensor:
+        """The 2-norm of every column of A: a device double[n], fp64 sums in a fixed order (lsx_colnrm2_*_dev)."""
+        _rowmajor(A, "col_norms")
+        out = torch.zeros(A.shape[1], dtype=torch.float64, device=A.device)
+        name = f"lsx_colnrm2_{self._suffix(A)}_dev"
+        N.check(getattr(self.lib, name)(self.h.ptr, A.shape[0], A.shape[1], A.data_ptr(), max(A.stride(0), 1),
+                                        out.data_ptr()), name)
+        return out
+
     @staticmethod
     def _norm_code(which) -> int:
         if which in (1, "1", "one", "O", "o"):

@@ -684,6 +684,68 @@ class Matrix:
         with np.errstate(over="ignore"):   # the inverse of a matrix of tiny entries may not be representable: inf there
             return np.ldexp(X, ka)
 
+    # ---- Householder QR and least squares (lsx_geqrf_*, lsx_orgqr_*, lsx_gels_*) ----
+    def qr_array(self):
+        """(Q, R) as arrays (device tensors for a matrix built from one): the thin Q (rows x cols) and the upper
+        triangular R (cols x cols) of self = Q R, for rows >= cols; ValueError otherwise."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            import torch
+
+            from .device import DeviceSolver
+
+            QR = self._dev64().clone()
+            m, n = QR.shape
+            if m < n:
+                raise ValueError("qr_array needs at least as many rows as columns")
+            dev = DeviceSolver(self._dev.device.index)
+            tau = dev.geqrf_(QR)
+            return dev.orgqr(QR, tau), torch.triu(QR[:n, :])
+        A = self._array()
+        if A.shape[0] < A.shape[1]:
+            raise ValueError("qr_array needs at least as many rows as columns")
+        return dense.qr(A)
+
+    def least_squares_array(self, rhs, residuals: bool = False):
+        """The x that minimises ||rhs - self x||_2, through Householder QR, for rows >= cols (ValueError otherwise; an
+        underdetermined system has no unique minimiser).  rhs: a vector or a rows x nrhs array.  residuals=True
+        returns (x, ||rhs - self x||_2 per right-hand side).  NoSolution() when a diagonal entry of R is exactly zero or
+        NaN -- self does not have full column rank -- as inverse_array answers for a singular matrix.  Unlike
+        find_preimage_of this does not ask for a consistent system."""
+        if getattr(self, "_dev", None) is not None and self._items is None:
+            import torch
+
+            from .device import DeviceSolver
+
+            A = self._dev64().clone()
+            m, n = A.shape
+            if m < n:
+                raise ValueError("least_squares_array needs at least as many rows as columns")
+            B = rhs if hasattr(rhs, "is_cuda") else torch.as_tensor(np.asarray(rhs, dtype=np.float64))
+            B = B.to(device=A.device, dtype=torch.float64)
+            vec = B.dim() == 1
+            if B.shape[0] != m:
+                raise ValueError("Matrix dimensions must match")
+            W = B.reshape(m, -1).contiguous().clone()
+            dev = DeviceSolver(self._dev.device.index)
+            _, info = dev.gels_(A, W)
+            if int(info.item()) != 0:
+                return Matrix.NoSolution()
+            X = W[:n, 0].clone() if vec else W[:n].clone()
+            if not residuals:
+                return X
+            res = dev.col_norms(W[n:]) if m > n else torch.zeros(W.shape[1], dtype=torch.float64, device=A.device)
+            return X, (res[0] if vec else res)
+        A = self._array()
+        if A.shape[0] < A.shape[1]:
+            raise ValueError("least_squares_array needs at least as many rows as columns")
+        b = np.asarray(rhs, dtype=np.float64)
+        if b.shape[:1] != (A.shape[0],):
+            raise ValueError("Matrix dimensions must match")
+        x, resid, info = dense.lstsq(A, b)
+        if info != 0:
+            return Matrix.NoSolution()
+        return (x, resid) if residuals else x
+
     def transpose(self) -> "Matrix":
         return Matrix([[self.items[j][i] for j in range(self.rows)] for i in range(self.cols)])
 

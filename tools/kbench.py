@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | potri | posx | gecon | gerfs | equil [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | potri | posx | gecon | gerfs | equil | qr [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -39,6 +39,63 @@ def main():
     ap.add_argument("--nb", type=int, default=128)
     args = ap.parse_args()
     dev = DeviceSolver()
+    if "qr" in args.what:
+        # Householder QR: geqrf beside getrf of the same square matrix, geqrf and gels on tall shapes, and the shares of
+        # the panel steps, the T factor (with V and V^T V) and the block applies from the profile buckets
+        def shares(fn):
+            dev.h.prof_enable(True)
+            dev.h.prof_reset()
+            fn()
+            pr = dev.h.prof_read()
+            dev.h.prof_enable(False)
+            return "  ".join(f"{k} {pr[k]['ms']:.3f} ms / {pr[k]['launches']}" for k in ("panel", "trsm", "gemm", "other"))
+
+        for dt in ((torch.float32,) if args.f32 else (torch.float64, torch.float32)):
+            for n in (4096, 8192):
+                A0 = torch.empty(n, n, dtype=dt, device="cuda")
+                dev.fill_(A0, gen.U11, 5)
+                A = A0.clone()
+                tau = torch.zeros(n, dtype=dt, device="cuda")
+                ipiv = torch.zeros(n, dtype=torch.int32, device="cuda")
+                info = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+                def qrf():
+                    A.copy_(A0)
+                    dev.geqrf_(A, tau)
+
+                def luf():
+                    A.copy_(A0)
+                    dev.getrf_(A, ipiv, info)
+                tcopy, _ = timeit(lambda: A.copy_(A0), reps=3, warm=1)
+                tq, _ = timeit(qrf, reps=3, warm=1)
+                tl, _ = timeit(luf, reps=3, warm=1)
+                tq, tl = tq - tcopy, tl - tcopy
+                print(f"qr {str(dt)[6:]} n={n}: geqrf {tq:.3f} ms ({4 / 3 * n ** 3 / tq / 1e9:.1f} TFLOP/s)  getrf {tl:.3f} ms  "
+                      f"| QR/LU {tq / tl:.2f}\n    geqrf shares: {shares(qrf)}", flush=True)
+            for m, n in ((16384, 1024), (65536, 256)):
+                nrhs = 16
+                A0 = torch.empty(m, n, dtype=dt, device="cuda")
+                dev.fill_(A0, gen.U11, 6)
+                B0 = torch.empty(m, nrhs, dtype=dt, device="cuda")
+                dev.fill_(B0, gen.U11, 7)
+                A, B = A0.clone(), B0.clone()
+                tau = torch.zeros(n, dtype=dt, device="cuda")
+                info = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+                def qrf():
+                    A.copy_(A0)
+                    dev.geqrf_(A, tau)
+
+                def ls():
+                    A.copy_(A0)
+                    B.copy_(B0)
+                    dev.gels_(A, B, tau, info)
+                tcopy, _ = timeit(lambda: A.copy_(A0), reps=3, warm=1)
+                tq, _ = timeit(qrf, reps=3, warm=1)
+                tg, _ = timeit(ls, reps=3, warm=1)
+                fl = 2.0 * m * n * n - 2.0 / 3 * n ** 3
+                print(f"qr {str(dt)[6:]} {m} x {n}: geqrf {tq - tcopy:.3f} ms ({fl / (tq - tcopy) / 1e9:.1f} TFLOP/s)  gels nrhs={nrhs} "
+                      f"{tg - tcopy:.3f} ms\n    geqrf shares: {shares(qrf)}", flush=True)
     if "mfma" in args.what:
         for bpc in (1, 2):
             t64, mhz = dev.h.mfma_peak(False, 200000, bpc)
