@@ -1241,15 +1241,24 @@ static int podet_host(lsx_handle_t h, int n, const T *A, int lda, double *sign, 
 //   block apply  W = V^T C,  W <- T^T W (Q^T) or T W (Q),  C -= V W  on the existing tiles           [GEMM]
 // geqrf applies Q^T of a panel to the columns right of it; ormqr and orgqr form V and T again per block from the
 // factored array and tau, as LAPACK does.  qr_work is laid out here, from its start, by whoever runs blocks.
+// The products with V^T (G = V^T V, W = V^T C) run over all rows of the panel, and the TN tile adds them in one
+// accumulator of the working precision.  Above QR_KSPLIT_MIN rows the depth is cut into pieces of QR_KCHUNK rows, each
+// piece a product of its own, and the pieces are added in fp64 (qr_vt_times): 16386 rows as one running sum put the
+// orthogonality and least-squares ratios of a 16514 x 130 U(-1, 1) matrix at 4 times LAPACK's.  Panels
+// of at most QR_KSPLIT_MIN rows are computed as before, bit for bit.  The pieces take 128 / QR_KCHUNK of C's size.
+constexpr int QR_KSPLIT_MIN = 4096, QR_KCHUNK = 1024;
+static int qr_parts(int mp) { return mp > QR_KSPLIT_MIN ? (mp + QR_KCHUNK - 1) / QR_KCHUNK : 1; }
 template <typename T>
 struct QrWork {
-    T *V = nullptr, *G = nullptr, *Tm = nullptr, *Tt = nullptr, *W = nullptr, *W2 = nullptr, *prow = nullptr;
+    T *V = nullptr, *G = nullptr, *Tm = nullptr, *Tt = nullptr, *W = nullptr, *W2 = nullptr, *prow = nullptr, *parts = nullptr;
     double *slots = nullptr;
-    int ldw = 0;
+    int ldw = 0, pcols = 0;   // pcols: columns (and leading dimension) of a piece, a multiple of 128
 };
 template <typename T>
 static int carve_qr(lsx_handle_t h, int m, int nc, QrWork<T> *w) {
     w->ldw = ld_for(nc > 0 ? nc : 1);
+    const int np = qr_parts(m);
+    if (np > 1) w->pcols = ((nc > 128 ? nc : 128) + 127) / 128 * 128;   // G = V^T V has 128 columns
     return carve(h, h->qr_work, [&](Carver &c) {
         w->V = c.take<T>((size_t)m * 128);
         w->G = c.take<T>((size_t)128 * 128);
@@ -1259,19 +1268,37 @@ static int carve_qr(lsx_handle_t h, int m, int nc, QrWork<T> *w) {
         w->W2 = c.take<T>((size_t)128 * w->ldw);
         w->prow = c.take<T>((size_t)2 * 128);
         w->slots = c.take<double>(qr_slot_elems());
+        if (np > 1) w->parts = c.take<T>((size_t)np * 128 * w->pcols);
     });
+}
+// out (jb x nc) = V^T B for the mp x 128 V of the block and B (mp x nc)
+template <typename T>
+static int qr_vt_times(lsx_handle_t h, int jb, int nc, int mp, const QrWork<T> &w, const T *B, int ldb, T *out, int ldo,
+                       int bucket) {
+    const int np = qr_parts(mp);
+    if (np == 1) return launch_gemm_tn_acc<T>(h, 3, jb, nc, mp, w.V, 128, B, ldb, out, ldo, bucket);
+    if (!w.parts || nc > w.pcols) {
+        set_error("qr: no room for the partial products of %d rows, %d columns", mp, nc);
+        return LSX_ERR_INTERNAL;
+    }
+    for (int p = 0; p < np; ++p) {
+        const int r0 = p * QR_KCHUNK, rows = mp - r0 < QR_KCHUNK ? mp - r0 : QR_KCHUNK;
+        LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nc, rows, w.V + (size_t)r0 * 128, 128, B + (size_t)r0 * ldb, ldb,
+                                      w.parts + (size_t)p * 128 * w.pcols, w.pcols, bucket));
+    }
+    return launch_qr_sum_parts<T>(h, jb, nc, np, w.parts, w.pcols, (size_t)128 * w.pcols, out, ldo);
 }
 // V and T of the block whose reflectors lie below the diagonal of P (mp x jb) with scalars tau
 template <typename T>
 static int qr_block_form(lsx_handle_t h, int mp, int jb, const T *P, int ldp, const T *tau, const QrWork<T> &w) {
     LSX_TRY(launch_qr_extract_v<T>(h, mp, jb, P, ldp, w.V));
-    LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, jb, mp, w.V, 128, w.V, 128, w.G, 128, LSX_PROF_TRSM));
+    LSX_TRY(qr_vt_times<T>(h, jb, jb, mp, w, w.V, 128, w.G, 128, LSX_PROF_TRSM));
     return launch_qr_larft<T>(h, jb, w.G, tau, w.Tm, w.Tt);
 }
 // C (mp x nc) <- H^T C (trans) or H C, H = I - V T V^T
 template <typename T>
 static int qr_block_apply(lsx_handle_t h, int trans, int mp, int jb, int nc, const QrWork<T> &w, T *C, int ldc) {
-    LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nc, mp, w.V, 128, C, ldc, w.W, w.ldw));
+    LSX_TRY(qr_vt_times<T>(h, jb, nc, mp, w, C, ldc, w.W, w.ldw, LSX_PROF_GEMM));
     LSX_TRY(launch_gemm_tn_acc<T>(h, 3, jb, nc, jb, trans ? w.Tm : w.Tt, 128, w.W, w.ldw, w.W2, w.ldw));
     return launch_gemm_sub<T>(h, mp, nc, jb, w.V, 128, w.W2, w.ldw, C, ldc);
 }

@@ -171,7 +171,8 @@ struct lsx_handle_s {
     DevBuf cond;         // condition estimators (gecon, pocon): iteration vector, sign vector, record, identity interchanges
     DevBuf refine;       // refinement loop (gerfs, porfs): residual and bound of a group, two vectors, records, partial sums
     DevBuf equil;        // equilibration (geequ, gesvx): the drivers' records, then row maxima and partial column maxima
-    DevBuf qr_work;      // Householder QR: V, V^T V, T and its transpose, the two W strips, partial-sum slots, pivot rows
+    DevBuf qr_work;      // Householder QR: V, V^T V, T and its transpose, the two W strips, partial-sum slots, pivot rows,
+                         // and for panels of more than 4096 rows the pieces of V^T C (qr_vt_times)
     DevBuf xchg;         // few-RHS solve (kernels_trsv.hip, third form): exchange granules validated by an epoch, never cleared
     unsigned xchg_epoch = 0;
     DevBuf moves_all;    // look-ahead driver with the XCD-scope panel: one gather list per panel
@@ -555,6 +556,9 @@ template <typename T>
 int launch_qr_larft(lsx_handle_t h, int jb, const T *G, const T *tau, T *Tm, T *Tt);
 template <typename T>
 int launch_qr_identity(lsx_handle_t h, int m, int n, T *Q, int ldq);
+// out (rows x nc) = the sum of `parts` partial products, `stride` elements apart, in order, fp64, one rounding
+template <typename T>
+int launch_qr_sum_parts(lsx_handle_t h, int rows, int nc, int parts, const T *P, int ldp, size_t stride, T *out, int ldo);
 template <typename T>
 int launch_colnrm2(lsx_handle_t h, int m, int n, const T *A, int lda, double *out);
 

@@ -253,11 +253,33 @@ int launch_colnrm2(lsx_handle_t h, int m, int n, const T *A, int lda, double *ou
     return LSX_OK;
 }
 
+// out (rows x nc) = part 0 + part 1 + .. of a product whose depth was cut into `parts` pieces (api.hip, qr_vt_times):
+// part p lies `stride` elements behind part p - 1 with leading dimension ldp; added in that order in fp64, one rounding
+template <typename T>
+__global__ __launch_bounds__(256) void qr_sum_parts_kernel(int rows, int nc, int parts, const T *__restrict__ P, int ldp,
+                                                           size_t stride, T *__restrict__ out, int ldo) {
+    const int c = (int)blockIdx.x * 256 + (int)threadIdx.x, i = blockIdx.y;
+    if (c >= nc || i >= rows) return;
+    double s = 0.0;
+    for (int p = 0; p < parts; ++p) s += (double)P[(size_t)p * stride + (size_t)i * ldp + c];
+    out[(size_t)i * ldo + c] = (T)s;
+}
+template <typename T>
+int launch_qr_sum_parts(lsx_handle_t h, int rows, int nc, int parts, const T *P, int ldp, size_t stride, T *out, int ldo) {
+    if (rows <= 0 || nc <= 0 || parts <= 0) return LSX_OK;
+    ProfScope ps(h, LSX_PROF_OTHER, (double)parts * rows * nc, sizeof(T) * (double)(parts + 1) * rows * nc);
+    hipLaunchKernelGGL(qr_sum_parts_kernel<T>, dim3((nc + 255) / 256, rows), dim3(256), 0, h->stream, rows, nc, parts, P, ldp,
+                       stride, out, ldo);
+    LSX_HIP(hipGetLastError());
+    return LSX_OK;
+}
+
 #define LSX_QR_PIECES(T)                                                                         \
     template int launch_qr_panel<T>(lsx_handle_t, int, int, T *, int, T *, double *, T *);       \
     template int launch_qr_extract_v<T>(lsx_handle_t, int, int, const T *, int, T *);            \
     template int launch_qr_larft<T>(lsx_handle_t, int, const T *, const T *, T *, T *);          \
     template int launch_qr_identity<T>(lsx_handle_t, int, int, T *, int);                        \
+    template int launch_qr_sum_parts<T>(lsx_handle_t, int, int, int, const T *, int, size_t, T *, int); \
     template int launch_colnrm2<T>(lsx_handle_t, int, int, const T *, int, double *);
 LSX_QR_PIECES(double)
 LSX_QR_PIECES(float)

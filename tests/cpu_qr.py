@@ -9,6 +9,11 @@ launch_chol_inv (cpu_chol.diag_block).  It does not model the order of summation
 multiply-adds, so on rounded inputs it agrees with the GPU to rounding; on the planted inputs below every intermediate
 is a small integer (or a power of two) and the model, LAPACK and the GPU must agree bit for bit
 (tests/test_qr_host.py proves that of the model and LAPACK for every shape and seed the GPU tests use).
+
+Two plants: A = P [U; 0], whose reflectors are e_j +- e_k (one-term Gram sums; it crosses the tau = 0 branch and the
+block edges), and A = [0; H[:, :n] U] with a Sylvester-Hadamard H, whose reflectors are dense and whose Gram sums
+cancel exactly (see "the dense-reflector plant" below).  The tall shapes of either (16500 and 16514 rows) are the
+first with qr_slab_rows = 128, two 64-row chunks per slab of qr_panel_step_kernel.
 """
 import functools
 
@@ -79,6 +84,93 @@ def planted_rhs(m, n, nrhs, seed=PLANTED_SEED, dtype=np.float64):
     return x0.astype(dtype), b.astype(dtype), np.sqrt((e.astype(np.float64) ** 2).sum(axis=0))
 
 
+# ------------------------------------------------------------------ the dense-reflector plant
+# In the plant above every reflector is e_j +- e_k: each Gram sum g_c = sum_{i > j} a_ij a_ic of the panel step, each
+# slot of the cross-slab reduction, each entry of V^T V and each V^T C / C -= V W product has ONE non-zero term, so a
+# dropped, doubled or misplaced slab slot, 64-row chunk or K-slice changes nothing those tests can see.  Here every
+# reflector is dense and the results are still exact.
+#
+# H: the Sylvester Hadamard matrix of order N = 4^q, h_ij = (-1)^popcount(i & j); H^T H = N I.
+# A = [0 (n x n); H[:, :n] U] with U the signed sparse upper plant of _planted(n, n, seed), n <= N.  At step j the
+# column below the diagonal is u_jj H[:, j] (the earlier reflectors removed the other columns of H exactly), so
+# alpha = 0, g_j = 4^q u_jj^2, beta = -2^q |u_jj|, tau_j = 1, s = 2^-q / |u_jj| and, with S = diag(sign u_jj):
+#   R = -2^q S U,   rows n.. of the array = 2^-q H[:, :n] S,   the strict lower triangle of the top n rows = 0,
+#   V^T V = 2 I and T = I,   Q = -2^-q [0; H[:, :n]] S.
+# Every reflector has N non-zeros; every off-diagonal Gram sum is N terms of +-integers that cancel to exactly zero or
+# add up to 4^q u_jj u_jc.  tests/test_qr_host.py proves all of it of the model and of LAPACK.
+# (q, n): 385 x 129 two panels; 512 x 256 two full panels; 1324 x 300 three panels; 16514 x 130 THE TALL CASE:
+# qr_slab_rows(16514) = 128, so a workgroup of qr_panel_step_kernel runs its 64-row chunk loop twice (130 slabs, the
+# last of 2 rows), the second panel (16386 rows) as well; columns 64 .. 127 put the diagonal row in a second chunk.
+HADAMARD_SHAPES = [(4, 129), (4, 256), (5, 300), (7, 130)]
+HADAMARD_TALL = (7, 130)
+HADAMARD_NRHS = {(4, 129): 7, (4, 256): 64, (5, 300): 200, (7, 130): 3}
+TALL_SPARSE = [(16500, 5), (16500, 129)]    # the one-non-zero plant with two chunks per slab: tau = 0 rows included
+
+
+def hadamard_columns(q, cols):
+    """Columns `cols` of the Sylvester Hadamard matrix of order 4^q, as int64 (4^q x len(cols))."""
+    N = 4 ** q
+    x = np.arange(N, dtype=np.int64)[:, None] & np.asarray(cols, dtype=np.int64)[None, :]
+    for sh in (16, 8, 4, 2, 1):               # parity of the set bits
+        x ^= x >> sh
+    return 1 - 2 * (x & 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _hadamard_plant(q, n, seed):
+    N = 4 ** q
+    assert 1 <= n <= N
+    U = _planted(n, n, seed)[0]
+    H = hadamard_columns(q, np.arange(n))
+    return U, np.vstack([np.zeros((n, n), dtype=np.int64), H @ U]), H
+
+
+def hadamard_plant(q, n, seed=PLANTED_SEED, dtype=np.float64):
+    """(U, A): A = [0; H[:, :n] U], (n + 4^q) x n, small integers.  Fresh copies."""
+    U, A, _ = _hadamard_plant(q, n, seed)
+    return U.astype(dtype), A.astype(dtype)
+
+
+def hadamard_expected(q, n, seed=PLANTED_SEED, dtype=np.float64):
+    """(QR, tau, Q): the exact factorisation of hadamard_plant in LAPACK's layout, and the thin Q."""
+    U, _, H = _hadamard_plant(q, n, seed)
+    S = np.sign(np.diagonal(U))
+    below = np.ldexp((H * S[None, :]).astype(np.float64), -q)
+    QR = np.vstack([np.ldexp(-(S[:, None] * U).astype(np.float64), q), below])
+    Q = np.vstack([np.zeros((n, n)), -below])
+    return QR.astype(dtype), np.ones(n, dtype=dtype), Q.astype(dtype)
+
+
+def hadamard_rhs(q, n, nrhs, seed=PLANTED_SEED, dtype=np.float64):
+    """(x0, b, enorm): b = A x0 + [0; e], x0 integer in [-3, 3], column c of e = k_c H[:, p_c] with an integer k_c of
+    [-3, 3] and p_c >= n -- a Hadamard column orthogonal to the range of A: the least-squares solution is x0 and the
+    residual norm 2^q |k_c|.  n = 4^q leaves no such column: e = 0."""
+    N = 4 ** q
+    _, A, _ = _hadamard_plant(q, n, seed)
+    rng = np.random.default_rng(11 * N + 3 * n + nrhs + seed)
+    x0 = rng.integers(-3, 4, (n, nrhs))
+    k = rng.integers(-3, 4, nrhs) if n < N else np.zeros(nrhs, dtype=np.int64)
+    p = rng.integers(n, N, nrhs) if n < N else np.zeros(nrhs, dtype=np.int64)
+    b = A @ x0
+    b[n:] += hadamard_columns(q, p) * k[None, :]
+    assert np.abs(b).max() < 2 ** 22
+    return x0.astype(dtype), b.astype(dtype), np.ldexp(np.abs(k).astype(np.float64), q)
+
+
+def hadamard_c(m, ncols, dtype=np.float64):
+    """The integer C (m x ncols, entries of [-3, 3]) that ormqr is applied to on the Hadamard plant."""
+    return np.random.default_rng(1000 * ncols + m).integers(-3, 4, (m, ncols)).astype(dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def hadamard_model(q, n, dtype_name, seed=PLANTED_SEED):
+    """(QR, tau) of the numpy model on the Hadamard plant, computed once, read-only."""
+    QR, tau = geqrf(hadamard_plant(q, n, seed, np.dtype(dtype_name).type)[1])
+    QR.setflags(write=False)
+    tau.setflags(write=False)
+    return QR, tau
+
+
 @functools.lru_cache(maxsize=None)
 def _uniform(m, n, seed):
     return np.random.default_rng(31 * m + n + seed).uniform(-1.0, 1.0, (m, n))
@@ -98,15 +190,20 @@ LAPACK_THRESH = 30.0                       # LAPACK's own test programs accept t
 
 
 # ------------------------------------------------------------------ the algorithm
-def panel(P):
-    """The jb reflectors of the panel P (mp x jb, working precision), in place; returns tau."""
+def panel(P, gram_rows=None):
+    """The jb reflectors of the panel P (mp x jb, working precision), in place; returns tau.  gram_rows (a boolean
+    mask over the panel's rows, default all): the rows whose terms enter the Gram sums -- only for showing that an
+    input tells a complete sum from one that misses a chunk of rows."""
     dt = P.dtype
     mp, jb = P.shape
     tau = np.zeros(jb, dtype=dt)
     with np.errstate(all="ignore"):
         for j in range(jb):
             below = P[j + 1:, j:].astype(np.float64)
-            g = below[:, 0] @ below if mp > j + 1 else np.zeros(jb - j)
+            if gram_rows is None:
+                g = below[:, 0] @ below if mp > j + 1 else np.zeros(jb - j)
+            else:
+                g = (below[:, 0] * gram_rows[j + 1:]) @ below if mp > j + 1 else np.zeros(jb - j)
             alpha = float(P[j, j])
             if g[0] == 0.0:
                 continue
@@ -230,23 +327,24 @@ def _norm1(M):
     return np.abs(M).sum(axis=0).max() if M.size else np.longdouble(0)
 
 
-def qr_ratios(A, Q, R):
-    """(||A - Q R||_1 / (m u ||A||_1),  ||I - Q^T Q||_1 / (m u)) with u the unit roundoff of A's type."""
+def qr_ratios(A, Q, R, wide=np.longdouble):
+    """(||A - Q R||_1 / (m u ||A||_1),  ||I - Q^T Q||_1 / (m u)) with u the unit roundoff of A's type, evaluated in
+    `wide`."""
     u = UNIT[np.dtype(A.dtype)]
     m = A.shape[0]
-    Al, Ql, Rl = (np.asarray(x, dtype=np.longdouble) for x in (A, Q, R))
+    Al, Ql, Rl = (np.asarray(x, dtype=wide) for x in (A, Q, R))
     r1 = _norm1(Al - Ql @ Rl) / (m * u * _norm1(Al))
-    r2 = _norm1(np.eye(Ql.shape[1], dtype=np.longdouble) - Ql.T @ Ql) / (m * u)
+    r2 = _norm1(np.eye(Ql.shape[1], dtype=wide) - Ql.T @ Ql) / (m * u)
     return float(r1), float(r2)
 
 
-def ls_ratio(A, b, x):
+def ls_ratio(A, b, x, wide=np.longdouble):
     """||A^T (b - A x)||_1 / (m u ||A||_1 (||b||_1 + ||A||_1 ||x||_1))."""
     u = UNIT[np.dtype(A.dtype)]
     m = A.shape[0]
-    Al = np.asarray(A, dtype=np.longdouble)
-    bl = np.asarray(b, dtype=np.longdouble).reshape(m, -1)
-    xl = np.asarray(x, dtype=np.longdouble).reshape(A.shape[1], -1)
+    Al = np.asarray(A, dtype=wide)
+    bl = np.asarray(b, dtype=wide).reshape(m, -1)
+    xl = np.asarray(x, dtype=wide).reshape(A.shape[1], -1)
     an = _norm1(Al)
     return float(_norm1(Al.T @ (bl - Al @ xl)) / (m * u * an * (_norm1(bl) + an * _norm1(xl))))
 
@@ -254,6 +352,9 @@ def ls_ratio(A, b, x):
 # the four rounded shapes of the comparison beside LAPACK, and their right-hand sides
 ROUNDED = [(129, 129), (300, 129), (600, 384), (1000, 257)]
 ROUNDED_NRHS = 3
+# ... and, apart from them, the tall shape of the Hadamard plant: two 64-row chunks per slab of the panel kernel, a
+# K of 16386 in the TN products of the block apply, 16384 rows under colnrm2
+ROUNDED_TALL = [(16514, 130)]
 
 
 def rounded_case(m, n, dtype):
@@ -262,24 +363,30 @@ def rounded_case(m, n, dtype):
     return A, b
 
 
-def _triple(A, b, QR, tau, x):
+def tall_wide(dtype):
+    """The type the ratios of ROUNDED_TALL are evaluated in: fp64 for fp32 results (29 more bits than the data, and a
+    BLAS product instead of seconds of np.longdouble), np.longdouble for fp64 results."""
+    return np.float64 if np.dtype(dtype) == np.float32 else np.longdouble
+
+
+def _triple(A, b, QR, tau, x, wide=np.longdouble):
     n = A.shape[1]
     Q = orgqr(QR, tau, n)
-    r1, r2 = qr_ratios(A, Q, np.triu(QR[:n]))
-    return r1, r2, ls_ratio(A, b, x)
+    r1, r2 = qr_ratios(A, Q, np.triu(QR[:n]), wide)
+    return r1, r2, ls_ratio(A, b, x, wide)
 
 
 @functools.lru_cache(maxsize=None)
-def model_ratios(m, n, dtype_name):
+def model_ratios(m, n, dtype_name, wide=np.longdouble):
     """The three ratios of the numpy model on the rounded case."""
     dtype = np.dtype(dtype_name).type
     A, b = rounded_case(m, n, dtype)
     QR, tau, Bo, _ = gels(A, b)
-    return _triple(A, b, QR, tau, Bo[:n])
+    return _triple(A, b, QR, tau, Bo[:n], wide)
 
 
 @functools.lru_cache(maxsize=None)
-def lapack_ratios(m, n, dtype_name):
+def lapack_ratios(m, n, dtype_name, wide=np.longdouble):
     """The three ratios of LAPACK (scipy) on the rounded case."""
     from scipy.linalg import lapack
 
@@ -292,5 +399,5 @@ def lapack_ratios(m, n, dtype_name):
     assert info == 0
     _, x, info = getattr(lapack, p + "gels")(A, b)
     assert info == 0
-    r1, r2 = qr_ratios(A, Q, np.triu(qr_[:n]))
-    return r1, r2, ls_ratio(A, b, x[:n])
+    r1, r2 = qr_ratios(A, Q, np.triu(qr_[:n]), wide)
+    return r1, r2, ls_ratio(A, b, x[:n], wide)

@@ -5,6 +5,16 @@ must agree exactly -- every intermediate is a small integer or a power of two --
 LAPACK ratios stay within twice the larger of the model's and LAPACK's.  Against the model, results are compared as
 numbers (the model has no fused multiply-adds, so the sign of a zero is not its to predict); GPU results are compared
 with each other bit for bit.
+
+Two kinds of planted input.  cpu_qr.planted (A = P [U; 0]) crosses the tau = 0 branch and the block edges, but its
+reflectors are e_j +- e_k: every Gram sum g_c of qr_panel_step_kernel, every slab slot, every entry of V^T V and every
+V^T C / C -= V W product on the MFMA tiles has ONE non-zero term, so a dropped, doubled or misplaced slot, 64-row chunk
+or K-slice would pass.  cpu_qr.hadamard_plant (A = [0; H[:, :n] U], H Sylvester-Hadamard of order 4^q) has reflectors
+with 4^q non-zeros and sums of 4^q terms that cancel exactly, and is exact all the same.  Its tall shape 16514 x 130
+(and cpu_qr.TALL_SPARSE, 16500 rows of the first kind) is the first with qr_slab_rows(mp) = 128 > 64: 130 slabs, the
+last of 2 rows, every workgroup running the kernel's 64-row chunk loop twice -- the second chunk, the barrier that
+guards colv_s / colj_s between chunks, the `continue` above lo_row inside a two-chunk slab, a diagonal row in a second
+chunk (columns 64 .. 127) -- and with it launch_gemm_tn_acc at K = 16386 and colnrm2_kernel over 16384 rows.
 """
 import ctypes as C
 
@@ -143,6 +153,85 @@ def test_planted_gels(dev, m, n, nrhs, dtype):
     assert np.all(np.abs(resid - enorm) <= np.spacing(enorm))
 
 
+# ------------------------------------------------------------------ the dense-reflector plant, and the tall shapes
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("q,n", cq.HADAMARD_SHAPES)
+def test_hadamard_factor(dev, q, n, dtype):
+    """R, V and tau of the Hadamard plant, device-pointer and host-buffer form: the model, which is the closed form."""
+    from linalg_solver_amd import dense
+
+    _, A = cq.hadamard_plant(q, n, dtype=dtype)
+    QR, tau = cq.hadamard_model(q, n, np.dtype(dtype).name)
+    G, gt = _geqrf(dev, A)
+    print(f"HADAMARD {A.shape[0]}x{n} {np.dtype(dtype).name}: entries differing {int(np.count_nonzero(G != QR))}, "
+          f"tau differing {int(np.count_nonzero(gt != tau))}")
+    assert np.array_equal(G, QR) and np.array_equal(gt, tau)
+    want, wtau, _ = cq.hadamard_expected(q, n, dtype=dtype)
+    assert np.array_equal(G, want) and np.array_equal(gt, wtau), "the closed form"
+    H, ht = dense.qr_factor(A, dtype=dtype, handle=dev.h)
+    assert _same_bits(H, G) and _same_bits(ht, gt), "host-buffer form"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("q,n", cq.HADAMARD_SHAPES)
+def test_hadamard_ormqr_orgqr(dev, q, n, dtype):
+    _, A = cq.hadamard_plant(q, n, dtype=dtype)
+    m = A.shape[0]
+    QR, tau = (np.array(x) for x in cq.hadamard_model(q, n, np.dtype(dtype).name))
+    QtA = _ormqr(dev, QR, tau, A, True)
+    assert np.array_equal(QtA[:n], np.triu(QR[:n])) and not QtA[n:].any(), "Q^T A = R exactly"
+    for ncols in (1, 7, 200):
+        Cm = cq.hadamard_c(m, ncols, dtype)
+        for k in (n, max(1, n - 70)):
+            W = _ormqr(dev, QR, tau[:k], Cm, True)
+            assert np.array_equal(W, cq.ormqr(QR, tau[:k], Cm, True)), f"Q^T C, ncols {ncols}, k {k}"
+            assert np.array_equal(_ormqr(dev, QR, tau[:k], W, False), Cm), "Q (Q^T C) = C exactly"
+            assert np.array_equal(_ormqr(dev, QR, tau[:k], Cm, False), cq.ormqr(QR, tau[:k], Cm, False)), f"Q C, ncols {ncols}, k {k}"
+    tq = _t(QR)
+    Q = dev.orgqr(tq, _t(tau)).cpu().numpy()
+    assert np.array_equal(Q, cq.hadamard_expected(q, n, dtype=dtype)[2]), "the closed form"
+    k = max(1, n - 70)
+    assert np.array_equal(dev.orgqr(tq, _t(tau[:k])).cpu().numpy(), cq.orgqr(QR, tau[:k])), "k < n"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("q,n", cq.HADAMARD_SHAPES)
+def test_hadamard_gels(dev, q, n, dtype):
+    from linalg_solver_amd import dense
+
+    _, A = cq.hadamard_plant(q, n, dtype=dtype)
+    x0, b, enorm = cq.hadamard_rhs(q, n, cq.HADAMARD_NRHS[(q, n)], dtype=dtype)
+    QR, tau, Bo, info, res = _gels(dev, A, b)
+    assert info == 0
+    assert np.array_equal(Bo[:n], x0), "the solution is the planted one exactly"
+    mq, mt = cq.hadamard_model(q, n, np.dtype(dtype).name)
+    assert np.array_equal(QR, mq) and np.array_equal(tau, mt)
+    assert np.all(np.abs(res - enorm) <= np.spacing(enorm)), "one rounding of the square root"
+    x, resid, info = dense.lstsq(A, b, dtype=dtype, handle=dev.h)
+    assert info == 0 and np.array_equal(x, x0)
+    assert np.all(np.abs(resid - enorm) <= np.spacing(enorm))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("m,n", cq.TALL_SPARSE)
+def test_tall_sparse_plant(dev, m, n, dtype):
+    """The one-non-zero plant at 16500 rows: the tau = 0 branch, the planted least-squares solution and the zero
+    column's info with two chunks per slab."""
+    U, A, _ = cq.planted(m, n, dtype=dtype)
+    x0, b, enorm = cq.planted_rhs(m, n, 3, dtype=dtype)
+    QR, tau, Bo, info, res = _gels(dev, A, b)
+    mq, mt = cq.geqrf(A)
+    assert np.array_equal(QR, mq) and np.array_equal(tau, mt) and (tau == 0).any() and (tau == 1).any()
+    assert info == 0 and np.array_equal(Bo[:n], x0)
+    assert np.all(np.abs(res - enorm) <= np.spacing(enorm))
+    j = n - 2
+    _, Z, _ = cq.planted_zero_column(m, n, j, dtype=dtype)
+    zq, zt, _, zinfo, _ = _gels(dev, Z, b)
+    mq, mt = cq.geqrf(Z)
+    assert np.array_equal(zq, mq) and np.array_equal(zt, mt)
+    assert zt[j] == 0 and zq[j, j] == 0 and zinfo == j + 1
+
+
 # ------------------------------------------------------------------ rank-deficient, zero and NaN inputs
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("j", cq.ZERO_COLUMNS)
@@ -208,6 +297,39 @@ def test_rounded_beside_lapack(dev, m, n, dtype):
         assert got <= 2.0 * max(a, c)
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("m,n", cq.ROUNDED_TALL)
+def test_rounded_tall_beside_lapack(dev, m, n, dtype):
+    """The rule of test_rounded_beside_lapack at the tall shape (two chunks per slab, K = 16386 in the TN products,
+    16384 rows under colnrm2): each GPU ratio at most twice the larger of the model's and LAPACK's.  The fp32 ratios
+    are evaluated in fp64, not np.longdouble (cpu_qr.tall_wide); the fp64 case spends its seconds in np.longdouble
+    products on the host.  The values are printed.
+
+    Measured on an MI355X (GPU | model | LAPACK):
+                ||A - QR||_1 ratio            ||I - Q^T Q||_1 ratio         least-squares ratio
+      fp64   0.00026 | 0.00032 | 0.00034   0.00119 | 0.00557 | 0.00085   3.70e-8 | 3.83e-8 | 3.25e-8
+      fp32   0.00026 | 0.00023 | 0.00033   0.00108 | 0.00076 | 0.00094   3.35e-8 | 2.29e-8 | 3.24e-8
+    When it was first run this test failed: 0.00050, 0.00365, 1.31e-7 in fp64 (the third 3.4 times the model's) and
+    0.00051, 0.00372, 1.52e-7 in fp32 (4.0 and 4.7 times LAPACK's).  The cause, read in kernels_gemm.hip and
+    reproduced on the CPU: launch_gemm_tn_acc gives every tile of C to one workgroup that walks all of K in one MFMA
+    accumulator of the working precision, so G = V^T V and W = V^T C were single running sums of 16386 terms (the
+    numpy model with those two products summed row after row gives 0.00049, 0.00370, 1.53e-7 in fp32 and 1.28e-7 in
+    fp64: the GPU's figures).  api.hip now cuts the depth of these two products into 1024-row pieces above 4096 rows
+    and adds the pieces in fp64 (qr_vt_times); the same emulation predicted 0.00025, 0.00099, 3.3e-8 for that."""
+    name, wide = np.dtype(dtype).name, cq.tall_wide(dtype)
+    A, b = cq.rounded_case(m, n, dtype)
+    QR, tau, Bo, info, _ = _gels(dev, A, b)
+    assert info == 0
+    Q = dev.orgqr(_t(QR), _t(tau)).cpu().numpy()
+    r1, r2 = cq.qr_ratios(A, Q, np.triu(QR[:n]), wide)
+    r3 = cq.ls_ratio(A, b, Bo[:n], wide)
+    mod, lap = cq.model_ratios(m, n, name, wide), cq.lapack_ratios(m, n, name, wide)
+    print(f"{m}x{n} {name}: GPU {r1:.5f} {r2:.5f} {r3:.2e} | model {mod[0]:.5f} {mod[1]:.5f} {mod[2]:.2e} | "
+          f"LAPACK {lap[0]:.5f} {lap[1]:.5f} {lap[2]:.2e}")
+    for got, a, c in zip((r1, r2, r3), mod, lap):
+        assert got <= 2.0 * max(a, c)
+
+
 # ------------------------------------------------------------------ views
 GUARD = 64
 
@@ -247,8 +369,19 @@ def test_views(dev, dtype, layout, fill):
     aligned with two elements of padding) inside NaN- or canary-filled buffers: the bits of the aligned call, nothing
     outside the view written."""
     m, n, nrhs = 300, 200, 7
+    _views(dev, dtype, layout, fill, cq.rounded_case(m, n, dtype)[0], cq.uniform(m, nrhs, 2, dtype))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_views_tall(dev, dtype):
+    """The tall Hadamard shape (two chunks per slab) as odd views inside NaN-filled buffers."""
+    q, n = cq.HADAMARD_TALL
+    _views(dev, dtype, "odd", float("nan"), cq.hadamard_plant(q, n, dtype=dtype)[1], cq.hadamard_rhs(q, n, 3, dtype=dtype)[1])
+
+
+def _views(dev, dtype, layout, fill, A, b):
+    (m, n), nrhs = A.shape, b.shape[1]
     pad, off = (3 if (n + 3) % 2 else 4, 1) if layout == "odd" else (2, 0)
-    A, b = cq.rounded_case(m, n, dtype)[0], cq.uniform(m, nrhs, 2, dtype)
     QR0, tau0 = _geqrf(dev, A)
     vA = View(m, n, pad, off, dtype, fill, A)
     vtau = View(1, n, 0, off, dtype, fill)
