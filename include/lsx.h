@@ -568,6 +568,63 @@ int lsx_gels_f64(lsx_handle_t h, int m, int n, int nrhs, const double *A, int ld
 int lsx_gels_f32(lsx_handle_t h, int m, int n, int nrhs, const float *A, int lda, const float *B, int ldb, float *X, int ldx,
                  double *resid, int *info);
 
+/* ---- Jacobi SVD and minimum-norm least squares (LAPACK's gesvj / gesvdj, gelss) ---- */
+/* A (m x n, row-major, any m, n >= 0) = U diag(s) V^T with k = min(m, n): s holds k DOUBLES for both precisions, in
+ * descending order; with jobz = 1 U is m x k and Vt is k x n (the thin factors), with jobz = 0 only s is computed (no
+ * rotations are accumulated, no ormqr; U and Vt may be NULL) and s has the bits jobz = 1 gives.  Nothing here is
+ * cooperative: no kernel waits for another workgroup, there is no spin and no time-out outcome, lsx_check_status has
+ * nothing to report.  With a fixed pair order the result is deterministic: two calls give identical bits, and so do any
+ * alignment and any leading dimension of the caller's arrays (they are only copied from and gathered into).
+ *
+ * Algorithm: one-sided Jacobi on the ROWS of a work matrix W (p x q).  m <= n: W = A (p = m, q = n) and U = Z^T, Z the
+ * product of the rotations.  m > n: A = Q R by lsx_geqrf_*, W = R (p = q = n) and U = Q [Z^T; 0] by lsx_ormqr_*.  A sweep
+ * pairs every row with every other once, in P - 1 rounds of the round-robin order over P = p + (p & 1) players (round r:
+ * position 0 holds player 0, position s >= 1 player ((s - 1 - r) mod (P - 1)) + 1; position t meets position P - 1 - t;
+ * a pair with the phantom player of an odd p is skipped); the pairs of a round share no row, a round is one launch.
+ * Pair (i < j): a = w_i.w_i, b = w_j.w_j, c = w_i.w_j in fp64 for both precisions, in a fixed order; rotate iff
+ * |c| > tol sqrt(a) sqrt(b), tol = sqrt(q) u, u = 2^-53 (fp64) or 2^-24 (fp32) -- dgesvj's CTOL; a NaN fails the
+ * comparison.  zeta = (b - a) / (2 c), t = sgn(zeta) / (|zeta| + sqrt(1 + zeta^2)) with sgn(0) = +1 (|zeta| > 2^500:
+ * t = 1 / (2 zeta)), cs = 1 / sqrt(1 + t^2), sn = cs t, w_i <- cs w_i - sn w_j, w_j <- sn w_i + cs w_j in fp64, rounded
+ * once; rows i, j of Z alike.  A sweep without a rotation ends the iteration; at most "gesvdj_max_sweeps" sweeps run
+ * (option, 1 .. 60, default 30 = dgesvj's NSWEEP).  If the last allowed sweep still rotated *info = 1 and the results are
+ * returned all the same (dgesvj's INFO > 0); otherwise *info = 0.  The options "gesvdj_sweeps" and "gesvdj_rotations"
+ * (saturating at INT_MAX) read back the last call.  Then s_i = sqrt(sum_k w_ik^2) in fp64, sorted descending (stable),
+ * and row i of Vt = w_i / s_i.
+ * Deviation from LAPACK's layout: U is orthonormal to rounding for EVERY input, and the rows of Vt that belong to an
+ * exactly zero singular value are rows of zeros (LAPACK completes them to an orthonormal set).
+ * Numeric domain: the sums of squares are not scaled, so sum_k w_ik^2 must be a finite normal fp64 number -- the
+ * contract of lsx_colnrm2_*.  Inside it A 2^d gives the same U, Vt, sweeps and rotations, and s 2^d.
+ * A NaN or an infinity anywhere in A: every entry of s is NaN, U and Vt are unspecified, *info = 0; nothing iterates
+ * ("gesvdj_sweeps" reads 0), loops or faults.
+ * The host reads one counter per sweep, so ALL forms synchronise the handle's stream (as lsx_gecon_*, lsx_gerfs_*).
+ * info and rank are host ints in all forms (info may be NULL).  The _dev forms destroy dA; d_s is a device array there.
+ *
+ * lsx_gelss_*: the minimum-norm solution of min ||b - A x||_2 for ANY shape and rank: X (n x nrhs) = V diag(1 / s_i,
+ * i < rank) U^T B, the two products on the MFMA tile.  *rank (may be NULL) = the number of s_i > rcond s_0; rcond < 0
+ * selects max(m, n) u.  s_0 == 0 gives rank 0 and X = 0.  d_s / s (k doubles) may be NULL.  A NaN or infinity in A gives
+ * rank 0, s and X all NaN.  The host form leaves A and B alone; resid (host double[nrhs], may be NULL) receives
+ * ||b - A x||_2 per column, from B - A X on the update tile and lsx_colnrm2_*.  dB is not modified.
+ *
+ * LSX_ERR_ARG for negative sizes, lda < n, jobz other than 0 or 1, with jobz = 1 ldu < k or ldvt < n, ldb or ldx < nrhs,
+ * or a NULL pointer with non-zero sizes.  Zero extents (k == 0; for gelss also nrhs == 0) are LSX_OK with nothing
+ * touched but *info = 0 and *rank = 0. */
+int lsx_gesvdj_f64_dev(lsx_handle_t h, int jobz, int m, int n, double *dA, int lda, double *d_s, double *dU, int ldu,
+                       double *dVt, int ldvt, int *info);
+int lsx_gesvdj_f32_dev(lsx_handle_t h, int jobz, int m, int n, float *dA, int lda, double *d_s, float *dU, int ldu,
+                       float *dVt, int ldvt, int *info);
+int lsx_gesvdj_f64(lsx_handle_t h, int jobz, int m, int n, const double *A, int lda, double *s, double *U, int ldu,
+                   double *Vt, int ldvt, int *info);
+int lsx_gesvdj_f32(lsx_handle_t h, int jobz, int m, int n, const float *A, int lda, double *s, float *U, int ldu, float *Vt,
+                   int ldvt, int *info);
+int lsx_gelss_f64_dev(lsx_handle_t h, int m, int n, int nrhs, double *dA, int lda, const double *dB, int ldb, double *dX,
+                      int ldx, double rcond, double *d_s, int *rank, int *info);
+int lsx_gelss_f32_dev(lsx_handle_t h, int m, int n, int nrhs, float *dA, int lda, const float *dB, int ldb, float *dX,
+                      int ldx, double rcond, double *d_s, int *rank, int *info);
+int lsx_gelss_f64(lsx_handle_t h, int m, int n, int nrhs, const double *A, int lda, const double *B, int ldb, double *X,
+                  int ldx, double rcond, double *s, double *resid, int *rank, int *info);
+int lsx_gelss_f32(lsx_handle_t h, int m, int n, int nrhs, const float *A, int lda, const float *B, int ldb, float *X,
+                  int ldx, double rcond, double *s, double *resid, int *rank, int *info);
+
 /* ---- Cholesky: condition estimate and error bounds (LAPACK's lansy, pocon, porfs) ---- */
 /* Storage as above: row-major, UPPER, A = U^T U.  The strictly lower triangle of A and of U is never loaded and never
  * written by any of these, inside a diagonal tile or block included: it may hold NaN.  Nothing here is cooperative: no

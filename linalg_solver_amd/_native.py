@@ -174,6 +174,14 @@ _SIGS = {
     "lsx_orgqr_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _fp, _i],
     "lsx_gels_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, _dp, C.POINTER(_i)],
     "lsx_gels_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, _dp, C.POINTER(_i)],
+    "lsx_gesvdj_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, C.POINTER(_i)],
+    "lsx_gesvdj_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, C.POINTER(_i)],
+    "lsx_gesvdj_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _dp, _i, _dp, _i, C.POINTER(_i)],
+    "lsx_gesvdj_f32": [_vp, _i, _i, _i, _fp, _i, _dp, _fp, _i, _fp, _i, C.POINTER(_i)],
+    "lsx_gelss_f64_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, C.POINTER(_i), C.POINTER(_i)],
+    "lsx_gelss_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, C.POINTER(_i), C.POINTER(_i)],
+    "lsx_gelss_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, C.c_double, _dp, _dp, C.POINTER(_i), C.POINTER(_i)],
+    "lsx_gelss_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, C.c_double, _dp, _dp, C.POINTER(_i), C.POINTER(_i)],
     "lsx_matmul_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i],
     "lsx_fill_f64_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],
     "lsx_fill_f32_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],

@@ -7,6 +7,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <climits>
+#include <cmath>
 
 #include "common.h"
 
@@ -1476,6 +1478,218 @@ static int gels_host(lsx_handle_t h, int m, int n, int nrhs, const T *A, int lda
     return LSX_OK;
 }
 
+// ---------------------------------------------------------------- one-sided Jacobi SVD: A = U diag(s) V^T (kernels_svd.hip)
+// The rows of the work matrix W (p x q, p = min(m, n), q = n) are made mutually orthogonal by plane rotations, Z (p x p,
+// the identity to begin with) receives the same rotations:  W = Z A (m <= n) or W = Z R with A = Q R (m > n: geqrf_dev
+// first, so that the iteration runs on n x n).  Then s_i = ||w_i||_2, row i of V^T = w_i / s_i, and U = Z^T or
+// Q [Z^T; 0] (ormqr_dev on the caller's U, whose rows below n the gather has zeroed).
+//   a sweep = P - 1 rounds of the round-robin order, one launch each, pairs of a round disjoint           [PANEL]
+//   row norms, the sorted gather of s, U, V^T, gelss's row scaling                                        [OTHER]
+//   gelss: Y = U^T B and X = (V^T)^T Y on the TN tile                                                     [GEMM]
+// The host reads the rotation counter once per sweep and the row norms before the first sweep (a NaN or infinity in A
+// ends the call there: s all NaN, nothing iterates) and after the last one, so every form synchronises the stream.
+// svd_work is laid out once per call, here; geqrf_dev and ormqr_dev keep qr_work to themselves.
+template <typename T>
+struct SvdWork {
+    T *W = nullptr, *Z = nullptr, *tau = nullptr;
+    double *sigma = nullptr;
+    int *perm = nullptr, *count = nullptr;
+    int ldw = 0, ldz = 0;
+    // gelss only (nrhs > 0): the factors, the values in order, and Y = U^T B
+    T *U = nullptr, *Vt = nullptr, *Y = nullptr;
+    double *s = nullptr;
+    int ldu = 0, ldvt = 0, ldy = 0;
+};
+template <typename T>
+static int carve_svd(lsx_handle_t h, int m, int n, int jobz, int nrhs, SvdWork<T> *w) {
+    const int k = m < n ? m : n;
+    w->ldw = svd_ld(n, sizeof(T));
+    w->ldz = svd_ld(k, sizeof(T));
+    w->ldu = ld_for(k); w->ldvt = ld_for(n); w->ldy = ld_for(nrhs > 0 ? nrhs : 1);
+    return carve(h, h->svd_work, [&](Carver &c) {
+        w->W = c.take<T>((size_t)k * w->ldw);
+        if (jobz) w->Z = c.take<T>((size_t)k * w->ldz);
+        w->sigma = c.take<double>(k);
+        w->perm = c.take<int>(k);
+        w->count = c.take<int>(1);
+        if (m > n) w->tau = c.take<T>(n);
+        if (nrhs > 0) {
+            w->U = c.take<T>((size_t)m * w->ldu);
+            w->Vt = c.take<T>((size_t)k * w->ldvt);
+            w->Y = c.take<T>((size_t)k * w->ldy);
+            w->s = c.take<double>(k);
+        }
+    });
+}
+
+// The call on a carved work space; A (m x n, k = min(m, n) > 0) is destroyed.  s_host receives the k values in order (all
+// NaN for an input that is not finite).  Synchronises the stream.
+template <typename T>
+static int gesvdj_run(lsx_handle_t h, const SvdWork<T> &w, int jobz, int m, int n, T *A, int lda, double *d_s, T *U, int ldu,
+                      T *Vt, int ldvt, int *info, std::vector<double> *s_host) {
+    const int k = m < n ? m : n, p = k, q = n;
+    const bool tall = m > n;
+    h->gesvdj_sweeps = 0;
+    h->gesvdj_rotations = 0;
+    if (tall) LSX_TRY(geqrf_dev<T>(h, m, n, A, lda, w.tau));
+    LSX_TRY(launch_svd_init<T>(h, p, q, A, lda, tall ? 1 : 0, w.W, w.ldw));
+    if (jobz) LSX_TRY(launch_svd_init<T>(h, p, p, (const T *)nullptr, 0, 0, w.Z, w.ldz));
+    std::vector<double> sig(k);
+    auto norms = [&](bool *finite) -> int {
+        LSX_TRY(launch_svd_rownorm<T>(h, p, q, w.W, w.ldw, w.sigma));
+        LSX_HIP(hipMemcpyAsync(sig.data(), w.sigma, sizeof(double) * k, hipMemcpyDeviceToHost, h->stream));
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        *finite = true;
+        for (double v : sig) *finite = *finite && std::isfinite(v);
+        return LSX_OK;
+    };
+    bool finite = true;
+    LSX_TRY(norms(&finite));
+    int last = 0;
+    if (finite) {
+        const double tol = sqrt((double)q) * (0.5 * (double)Real<T>::eps);
+        const int P = p + (p & 1);
+        long long total = 0;
+        for (int sweep = 1; sweep <= h->gesvdj_max_sweeps; ++sweep) {
+            LSX_HIP(hipMemsetAsync(w.count, 0, sizeof(int), h->stream));
+            for (int r = 0; r < P - 1; ++r) LSX_TRY(launch_svd_round<T>(h, p, q, r, w.W, w.ldw, jobz ? w.Z : (T *)nullptr, w.ldz, tol, w.count));
+            LSX_HIP(hipMemcpyAsync(&last, w.count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            LSX_HIP(hipStreamSynchronize(h->stream));
+            h->gesvdj_sweeps = sweep;
+            total += last;
+            if (last == 0) break;
+        }
+        h->gesvdj_rotations = total > INT_MAX ? INT_MAX : (int)total;
+        LSX_TRY(norms(&finite));
+    }
+    if (info) *info = (finite && last != 0) ? 1 : 0;
+    if (!finite) {
+        LSX_TRY(launch_svd_fill<double>(h, 1, k, (double)NAN, d_s, k));
+        if (s_host) s_host->assign(k, (double)NAN);
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        return LSX_OK;
+    }
+    std::vector<int> perm(k);
+    for (int i = 0; i < k; ++i) perm[i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return sig[a] > sig[b]; });
+    LSX_HIP(hipMemcpyAsync(w.perm, perm.data(), sizeof(int) * k, hipMemcpyHostToDevice, h->stream));
+    LSX_TRY(launch_svd_gather<T>(h, k, q, m, w.W, w.ldw, w.Z, w.ldz, w.sigma, w.perm, d_s, jobz ? Vt : (T *)nullptr, ldvt,
+                                 jobz ? U : (T *)nullptr, ldu));
+    if (jobz && tall) LSX_TRY(ormqr_dev<T>(h, 0, m, k, n, A, lda, w.tau, U, ldu));
+    if (s_host) {
+        s_host->resize(k);
+        for (int i = 0; i < k; ++i) (*s_host)[i] = sig[perm[i]];
+    }
+    LSX_HIP(hipStreamSynchronize(h->stream));   // perm is read by the upload
+    return LSX_OK;
+}
+
+template <typename T>
+static int gesvdj_dev(lsx_handle_t h, int jobz, int m, int n, T *A, int lda, double *d_s, T *U, int ldu, T *Vt, int ldvt,
+                      int *info) {
+    LSX_ARG(h && (jobz == 0 || jobz == 1) && m >= 0 && n >= 0 && lda >= n);
+    const int k = m < n ? m : n;
+    LSX_ARG(!jobz || (ldu >= k && ldvt >= n));
+    if (info) *info = 0;
+    if (k == 0) return LSX_OK;
+    LSX_ARG(A && d_s && (!jobz || (U && Vt)));
+    SvdWork<T> w;
+    LSX_TRY(carve_svd<T>(h, m, n, jobz, 0, &w));
+    return gesvdj_run<T>(h, w, jobz, m, n, A, lda, d_s, U, ldu, Vt, ldvt, info, nullptr);
+}
+
+// Minimum-norm least squares through the SVD: X = V diag(1 / s_i, i < rank) U^T B; A is destroyed, B is kept.
+template <typename T>
+static int gelss_dev(lsx_handle_t h, int m, int n, int nrhs, T *A, int lda, const T *B, int ldb, T *X, int ldx, double rcond,
+                     double *d_s, int *rank, int *info) {
+    LSX_ARG(h && m >= 0 && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs && ldx >= nrhs);
+    if (info) *info = 0;
+    if (rank) *rank = 0;
+    if (m == 0 || n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(A && B && X);
+    const int k = m < n ? m : n;
+    SvdWork<T> w;
+    LSX_TRY(carve_svd<T>(h, m, n, 1, nrhs, &w));
+    std::vector<double> s;
+    LSX_TRY(gesvdj_run<T>(h, w, 1, m, n, A, lda, w.s, w.U, w.ldu, w.Vt, w.ldvt, info, &s));
+    if (d_s) LSX_HIP(hipMemcpyAsync(d_s, w.s, sizeof(double) * k, hipMemcpyDeviceToDevice, h->stream));
+    if (std::isnan(s[0])) {   // an input that is not finite: no solution to speak of
+        LSX_TRY(launch_svd_fill<T>(h, n, nrhs, (T)NAN, X, ldx));
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        return LSX_OK;
+    }
+    const double thr = (rcond < 0.0 ? (double)(m > n ? m : n) * (0.5 * (double)Real<T>::eps) : rcond) * s[0];
+    int rk = 0;
+    while (rk < k && s[rk] > thr) ++rk;
+    if (rank) *rank = rk;
+    LSX_TRY(launch_gemm_tn_acc<T>(h, 3, k, nrhs, m, w.U, w.ldu, B, ldb, w.Y, w.ldy));
+    LSX_TRY(launch_svd_scale_rows<T>(h, k, nrhs, rk, w.s, w.Y, w.ldy));
+    LSX_TRY(launch_gemm_tn_acc<T>(h, 3, n, nrhs, k, w.Vt, w.ldvt, w.Y, w.ldy, X, ldx));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+template <typename T>
+static int gesvdj_host(lsx_handle_t h, int jobz, int m, int n, const T *A, int lda, double *s, T *U, int ldu, T *Vt, int ldvt,
+                       int *info) {
+    LSX_ARG(h && (jobz == 0 || jobz == 1) && m >= 0 && n >= 0 && lda >= n);
+    const int k = m < n ? m : n;
+    LSX_ARG(!jobz || (ldu >= k && ldvt >= n));
+    if (info) *info = 0;
+    if (k == 0) return LSX_OK;
+    LSX_ARG(A && s && (!jobz || (U && Vt)));
+    const int ld = ld_for(n), lu = ld_for(k);
+    T *dA = nullptr, *dU = nullptr, *dVt = nullptr; double *ds = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)m * ld);
+        ds = c.take<double>(k);
+        if (jobz) { dU = c.take<T>((size_t)m * lu); dVt = c.take<T>((size_t)k * ld); }
+    }));
+    LSX_TRY(h2d<T>(h, m, n, A, lda, dA, ld));
+    LSX_TRY(gesvdj_dev<T>(h, jobz, m, n, dA, ld, ds, dU, lu, dVt, ld, info));
+    LSX_HIP(hipMemcpyAsync(s, ds, sizeof(double) * k, hipMemcpyDeviceToHost, h->stream));
+    if (jobz) {
+        LSX_TRY(d2h<T>(h, m, k, dU, lu, U, ldu));
+        LSX_TRY(d2h<T>(h, k, n, dVt, ld, Vt, ldvt));
+    }
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
+// A and B are not modified; X is n x nrhs; s (k values), resid (nrhs) may be NULL
+template <typename T>
+static int gelss_host(lsx_handle_t h, int m, int n, int nrhs, const T *A, int lda, const T *B, int ldb, T *X, int ldx,
+                      double rcond, double *s, double *resid, int *rank, int *info) {
+    LSX_ARG(h && m >= 0 && n >= 0 && nrhs >= 0 && lda >= n && ldb >= nrhs && ldx >= nrhs);
+    if (info) *info = 0;
+    if (rank) *rank = 0;
+    if (m == 0 || n == 0 || nrhs == 0) return LSX_OK;
+    LSX_ARG(A && B && X);
+    const int k = m < n ? m : n, ld = ld_for(n), ldr = ld_for(nrhs);
+    T *dA = nullptr, *dA2 = nullptr, *dB = nullptr, *dX = nullptr; double *ds = nullptr, *dres = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)m * ld);
+        if (resid) dA2 = c.take<T>((size_t)m * ld);
+        dB = c.take<T>((size_t)m * ldr);
+        dX = c.take<T>((size_t)n * ldr);
+        ds = c.take<double>(k);
+        dres = c.take<double>(nrhs);
+    }));
+    LSX_TRY(h2d<T>(h, m, n, A, lda, dA, ld));
+    if (resid) LSX_TRY(h2d<T>(h, m, n, A, lda, dA2, ld));
+    LSX_TRY(h2d<T>(h, m, nrhs, B, ldb, dB, ldr));
+    LSX_TRY(gelss_dev<T>(h, m, n, nrhs, dA, ld, dB, ldr, dX, ldr, rcond, ds, rank, info));
+    LSX_TRY(d2h<T>(h, n, nrhs, dX, ldr, X, ldx));
+    if (s) LSX_HIP(hipMemcpyAsync(s, ds, sizeof(double) * k, hipMemcpyDeviceToHost, h->stream));
+    if (resid) {   // ||b - A x||_2 on the update tile: B <- B - A X, then its column norms
+        LSX_TRY(launch_gemm_sub<T>(h, m, nrhs, n, dA2, ld, dX, ldr, dB, ldr));
+        LSX_TRY(colnrm2_dev<T>(h, m, nrhs, dB, ldr, dres));
+        LSX_HIP(hipMemcpyAsync(resid, dres, sizeof(double) * nrhs, hipMemcpyDeviceToHost, h->stream));
+    }
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
 // A^T X = B from the factors (kernels_trsvt.hip).  Work space as in getrs_dev, so the two share what they grow.
 // may_block = false: the single-column solves inside the estimators, which keep the grouped path whatever the option says.
 template <typename T>
@@ -2327,7 +2541,7 @@ int lsx_destroy(lsx_handle_t h) {
     for (auto &ev : h->prof.pending) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &e : h->prof.pool) (void)hipEventDestroy(e);
     for (DevBuf *b : {&h->staging, &h->tinv, &h->rhs_work, &h->mixed_resid, &h->getri_work, &h->rref_first, &h->cond,
-                      &h->refine, &h->equil, &h->qr_work, &h->xchg, &h->moves_all, &h->scratch})
+                      &h->refine, &h->equil, &h->qr_work, &h->svd_work, &h->xchg, &h->moves_all, &h->scratch})
         if (b->p) (void)hipFree(b->p);
     if (h->moves_buf[0]) (void)hipFree(h->moves_buf[0]);
     if (h->dev_status) (void)hipFree(h->dev_status);
@@ -2457,6 +2671,9 @@ int lsx_set_option(lsx_handle_t h, const char *key, int value) {
     } else if (!strcmp(key, "getrs_t_blocked_min")) {   // transposed solve: smallest nrhs on the blocked sweeps (n > 128); 0 = never
         LSX_ARG(value >= 0);
         h->getrs_t_blocked_min = value;
+    } else if (!strcmp(key, "gesvdj_max_sweeps")) {   // Jacobi SVD: most sweeps of a call (dgesvj's NSWEEP = 30)
+        LSX_ARG(value >= 1 && value <= 60);
+        h->gesvdj_max_sweeps = value;
     } else if (!strcmp(key, "potrs_few_max")) {   // Cholesky solve: largest nrhs on the few-column step kernels; 0 = never
         LSX_ARG(value >= 0 && value <= 8);
         h->potrs_few_max = value;
@@ -2504,6 +2721,9 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value) {
     else if (!strcmp(key, "potri_order")) *value = h->potri_order;
     else if (!strcmp(key, "lauum_descending")) *value = h->lauum_descending;
     else if (!strcmp(key, "potri_tiles")) *value = h->potri_tiles;
+    else if (!strcmp(key, "gesvdj_max_sweeps")) *value = h->gesvdj_max_sweeps;
+    else if (!strcmp(key, "gesvdj_sweeps")) *value = h->gesvdj_sweeps;
+    else if (!strcmp(key, "gesvdj_rotations")) *value = h->gesvdj_rotations;
     else if (!strcmp(key, "pocon_solves")) *value = h->pocon_solves;
     else if (!strcmp(key, "porfs_steps")) *value = h->porfs_steps;
     else if (!strcmp(key, "porfs_solves")) *value = h->porfs_solves;
@@ -3357,6 +3577,32 @@ LSX_CHOL_ENTRIES(f32, float)
 LSX_QR_ENTRIES(f64, double)
 LSX_QR_ENTRIES(f32, float)
 #undef LSX_QR_ENTRIES
+
+// ---- Jacobi SVD and minimum-norm least squares
+#define LSX_SVD_ENTRIES(SFX, T)                                                                                           \
+    int lsx_gesvdj_##SFX##_dev(lsx_handle_t h, int jobz, int m, int n, T *dA, int lda, double *d_s, T *dU, int ldu,       \
+                               T *dVt, int ldvt, int *info) {                                                             \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return gesvdj_dev<T>(h, jobz, m, n, dA, lda, d_s, dU, ldu, dVt, ldvt, info);                                      \
+    }                                                                                                                     \
+    int lsx_gesvdj_##SFX(lsx_handle_t h, int jobz, int m, int n, const T *A, int lda, double *s, T *U, int ldu, T *Vt,    \
+                         int ldvt, int *info) {                                                                           \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return gesvdj_host<T>(h, jobz, m, n, A, lda, s, U, ldu, Vt, ldvt, info);                                          \
+    }                                                                                                                     \
+    int lsx_gelss_##SFX##_dev(lsx_handle_t h, int m, int n, int nrhs, T *dA, int lda, const T *dB, int ldb, T *dX,        \
+                              int ldx, double rcond, double *d_s, int *rank, int *info) {                                 \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return gelss_dev<T>(h, m, n, nrhs, dA, lda, dB, ldb, dX, ldx, rcond, d_s, rank, info);                            \
+    }                                                                                                                     \
+    int lsx_gelss_##SFX(lsx_handle_t h, int m, int n, int nrhs, const T *A, int lda, const T *B, int ldb, T *X, int ldx,  \
+                        double rcond, double *s, double *resid, int *rank, int *info) {                                   \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return gelss_host<T>(h, m, n, nrhs, A, lda, B, ldb, X, ldx, rcond, s, resid, rank, info);                         \
+    }
+LSX_SVD_ENTRIES(f64, double)
+LSX_SVD_ENTRIES(f32, float)
+#undef LSX_SVD_ENTRIES
 
 int lsx_fill_f64_dev(lsx_handle_t h, int kind, uint64_t seed, int m, int n, double *dA, int lda,
                      int row_off, int col_off) {

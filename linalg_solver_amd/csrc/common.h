@@ -109,6 +109,7 @@ struct lsx_handle_s {
     int rref_first_fast = 1; // 1: large fp64 inputs under LSX_PIVOT_FIRST take the blocked form (option rref_first_fast)
     int rref_blocked = 1;       // 1: large inputs with LSX_PIVOT_MAX take the blocked row reduction (option rref_blocked)
     int getrs_t_blocked_min = 64;   // transposed solve: smallest nrhs that takes the blocked (MFMA) sweeps when n > 128; 0 = never
+    int gesvdj_max_sweeps = 30;   // Jacobi SVD: most sweeps of a call (1 .. 60; dgesvj's NSWEEP)
     int potrs_few_max = 0;   // Cholesky solve: largest nrhs (<= 8) that takes the few-column step kernels; 0 = never
     int lauum_descending = 0;   // lsx_lauum_tn_*: 1 = the k-slabs in descending order, the form lsx_potri_* always runs; 0 = k ascending
     int potri_order = 0;     // SPD inverse, V^T V tiles: 0 = deepest first (ascending tile column), 1 = the symmetric update's order
@@ -129,6 +130,8 @@ struct lsx_handle_s {
     int pocon_solves = 0;    // single-right-hand-side solves of the last lsx_pocon_* / lsx_porcond_*
     int porfs_steps = 0;     // most refinement steps any column of the last porfs took
     int porfs_solves = 0;    // single-right-hand-side estimator solves of the last porfs
+    int gesvdj_sweeps = 0;   // sweeps of the last lsx_gesvdj_* / lsx_gelss_* call
+    int gesvdj_rotations = 0;   // rotations of that call, saturating at INT_MAX
     int panel_fallbacks = 0;    // host-buffer factorisations redone with panel mode 0 after an exchange time-out
     // ---- buffers.  A DevBuf is sized where it is used (lsx::carve / lsx::reserve) and only grows.  Growing frees the old
     // block, so no function keeps a pointer into a buffer across a call that may grow the SAME buffer.  Who holds what
@@ -148,6 +151,9 @@ struct lsx_handle_s {
     //   geqrf_dev, ormqr_dev      qr_work, each laid out from its start by carve_qr; neither keeps a piece across the other
     //   orgqr_dev                 nothing of its own: the identity, then ormqr_dev
     //   gels_dev                  tinv (block inverses of R), after geqrf_dev and ormqr_dev are done with qr_work
+    //   gesvdj_dev, gelss_dev     svd_work, laid out once per call by carve_svd and held across geqrf_dev / ormqr_dev (qr_work,
+    //                             which those two keep to themselves) and the products; gelss_dev's U, V^T, s and Y are
+    //                             pieces of the same carve
     //   gecon_dev, pocon_dev      cond, across getrs_dev / getrs_t_dev and potrs_few_*
     //   refine_loop               refine, across getrs_dev / getrs_t_dev (gerfs_dev) and potrs_few_apply (porfs_dev)
     //   gesvx_dev                 equil, across geequ_dev (equil again, never more than gesvx_dev carved), lange_dev
@@ -173,6 +179,7 @@ struct lsx_handle_s {
     DevBuf equil;        // equilibration (geequ, gesvx): the drivers' records, then row maxima and partial column maxima
     DevBuf qr_work;      // Householder QR: V, V^T V, T and its transpose, the two W strips, partial-sum slots, pivot rows,
                          // and for panels of more than 4096 rows the pieces of V^T C (qr_vt_times)
+    DevBuf svd_work;     // Jacobi SVD: W, Z, the row norms, the permutation, the rotation counter, tau, and gelss's U, V^T, s, Y
     DevBuf xchg;         // few-RHS solve (kernels_trsv.hip, third form): exchange granules validated by an epoch, never cleared
     unsigned xchg_epoch = 0;
     DevBuf moves_all;    // look-ahead driver with the XCD-scope panel: one gather list per panel
@@ -561,5 +568,26 @@ template <typename T>
 int launch_qr_sum_parts(lsx_handle_t h, int rows, int nc, int parts, const T *P, int ldp, size_t stride, T *out, int ldo);
 template <typename T>
 int launch_colnrm2(lsx_handle_t h, int m, int n, const T *A, int lda, double *out);
+// One-sided Jacobi SVD (kernels_svd.hip).  The work arrays W (p x q) and Z (p x p) are 16-byte aligned with a leading
+// dimension of svd_ld(cols) elements and zeros in the columns beyond the matrix; svd_keep_cols: the longest row the round
+// kernel keeps in registers.  launch_svd_round: round r of a sweep, one workgroup per pair, *count += rotations (Z may be
+// null).  launch_svd_init: D = S with the padding zeroed (upper: zeros below the diagonal too; S null: the identity).
+// launch_svd_rownorm: sigma_i = ||w_i||_2.  launch_svd_gather: s, V^T (or null) and U (or null; urows >= k rows, zeros
+// below row k) in the order perm.  launch_svd_scale_rows: row i of Y times 1 / s_i for i < rank, zeros below.
+int svd_ld(int cols, size_t elem);
+int svd_keep_cols(size_t elem);
+template <typename T>
+int launch_svd_round(lsx_handle_t h, int p, int q, int r, T *W, int ldw, T *Z, int ldz, double tol, int *count);
+template <typename T>
+int launch_svd_init(lsx_handle_t h, int rows, int cols, const T *S, int lds, int upper, T *D, int ldd);
+template <typename T>
+int launch_svd_rownorm(lsx_handle_t h, int p, int q, const T *W, int ldw, double *sigma);
+template <typename T>
+int launch_svd_gather(lsx_handle_t h, int k, int q, int urows, const T *W, int ldw, const T *Z, int ldz, const double *sigma,
+                      const int *perm, double *s, T *Vt, int ldvt, T *U, int ldu);
+template <typename T>
+int launch_svd_scale_rows(lsx_handle_t h, int k, int nc, int rank, const double *s, T *Y, int ldy);
+template <typename T>
+int launch_svd_fill(lsx_handle_t h, int rows, int cols, T value, T *D, int ldd);
 
 }  // namespace lsx

@@ -185,6 +185,91 @@ def lstsq(a, b, dtype=np.float64, handle: Optional[N.Handle] = None):
     return (X[:, 0].copy() if vec else X), (float(resid[0]) if vec else resid), 0
 
 
+def svd(a, compute_uv: bool = True, dtype=np.float64, handle: Optional[N.Handle] = None):
+    """One-sided Jacobi SVD of an m x n matrix (lsx_gesvdj_*): returns (U, s, Vt, info) with the thin factors U (m x k),
+    Vt (k x n), k = min(m, n), and s (k float64 values, descending) -- U and Vt are None with compute_uv=False.  info = 1
+    says the last allowed sweep still rotated (option "gesvdj_max_sweeps"); the results are returned all the same.
+    U is orthonormal for every input; the rows of Vt that belong to an exactly zero singular value are zero rows.  A NaN
+    or infinity in a gives s all NaN."""
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    if A.ndim != 2:
+        raise ValueError("svd needs a matrix")
+    m, n = A.shape
+    k = min(m, n)
+    s = np.zeros(k, dtype=np.float64)
+    U = np.zeros((m, k), dtype=dtype) if compute_uv else None
+    Vt = np.zeros((k, n), dtype=dtype) if compute_uv else None
+    info = C.c_int(0)
+    if k:
+        h = _h(handle)
+        N.check(getattr(h.lib, f"lsx_gesvdj_{sfx}")(h.ptr, 1 if compute_uv else 0, m, n, _ptr(A, ct), n, _ptr(s, C.c_double),
+                                                   _ptr(U, ct) if compute_uv else None, k,
+                                                   _ptr(Vt, ct) if compute_uv else None, n, C.byref(info)),
+                f"lsx_gesvdj_{sfx}")
+    return U, s, Vt, info.value
+
+
+def svdvals(a, dtype=np.float64, handle: Optional[N.Handle] = None) -> np.ndarray:
+    """The singular values of a, descending (lsx_gesvdj_* with jobz = 0: the bits svd returns)."""
+    return svd(a, compute_uv=False, dtype=dtype, handle=handle)[1]
+
+
+def lstsq_min_norm(a, b, rcond: Optional[float] = None, dtype=np.float64, handle: Optional[N.Handle] = None):
+    """The minimum-norm solution of min ||b - a x||_2 for a matrix of any shape and rank, through the SVD (lsx_gelss_*).
+    Returns (x, resid, rank, s): resid holds ||b - a x||_2 per right-hand side, rank counts the singular values above
+    rcond * s[0] (rcond=None: max(m, n) times the unit roundoff), s the singular values."""
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    if A.ndim != 2:
+        raise ValueError("lstsq_min_norm needs a matrix")
+    m, n = A.shape
+    if np.shape(b)[:1] != (m,):
+        raise ValueError("right-hand side has the wrong number of rows")
+    B = np.ascontiguousarray(b, dtype=dtype)
+    vec = B.ndim == 1
+    if vec:
+        B = B.reshape(m, 1)
+    nrhs = B.shape[1]
+    k = min(m, n)
+    X = np.zeros((n, nrhs), dtype=dtype)
+    s = np.zeros(k, dtype=np.float64)
+    resid = np.zeros(max(nrhs, 1), dtype=np.float64)
+    rank, info = C.c_int(0), C.c_int(0)
+    if k and nrhs:
+        h = _h(handle)
+        N.check(getattr(h.lib, f"lsx_gelss_{sfx}")(h.ptr, m, n, nrhs, _ptr(A, ct), n, _ptr(B, ct), nrhs, _ptr(X, ct), nrhs,
+                                                  -1.0 if rcond is None else float(rcond), _ptr(s, C.c_double),
+                                                  _ptr(resid, C.c_double), C.byref(rank), C.byref(info)), f"lsx_gelss_{sfx}")
+    elif k:
+        s = svdvals(A, dtype=dtype, handle=handle)
+    elif nrhs:
+        resid[:nrhs] = np.sqrt((B.astype(np.float64) ** 2).sum(axis=0))   # n == 0: x is empty and the residual is b
+    resid = resid[:nrhs]
+    return (X[:, 0].copy() if vec else X), (float(resid[0]) if vec else resid), rank.value, s
+
+
+def pinv(a, rcond: Optional[float] = None, dtype=np.float64, handle: Optional[N.Handle] = None) -> np.ndarray:
+    """The Moore-Penrose pseudo-inverse (n x m): lsx_gelss_* with the identity as right-hand sides."""
+    A = np.ascontiguousarray(a, dtype=dtype)
+    if A.ndim != 2:
+        raise ValueError("pinv needs a matrix")
+    return lstsq_min_norm(A, np.eye(A.shape[0], dtype=dtype), rcond=rcond, dtype=dtype, handle=handle)[0]
+
+
+def matrix_rank(a, rcond: Optional[float] = None, dtype=np.float64, handle: Optional[N.Handle] = None) -> int:
+    """The number of singular values above rcond * s[0] (rcond=None: max(m, n) times the unit roundoff)."""
+    A = np.ascontiguousarray(a, dtype=dtype)
+    if A.ndim != 2:
+        raise ValueError("matrix_rank needs a matrix")
+    s = svdvals(A, dtype=dtype, handle=handle)
+    if not len(s):
+        return 0
+    if rcond is None:
+        rcond = max(A.shape) * (EPS64 if dtype == np.float64 else EPS32) / 2
+    return int(np.sum(s > rcond * s[0]))
+
+
 def _norm_code(which) -> int:
     """1 / "1" / "one" -> the 1-norm (max column sum); inf / "inf" / "I" -> the infinity-norm (max row sum)."""
     if which in (1, "1", "one", "O", "o"):

@@ -257,6 +257,52 @@ class DeviceSolver:
                                         B.data_ptr(), max(B.stride(0), 1), info.data_ptr()), name)
         return tau, info
 
+    # -- Jacobi SVD and minimum-norm least squares
+    def gesvdj_(self, A: torch.Tensor, compute_uv: bool = True):
+        """One-sided Jacobi SVD of A (m x n) in HBM (lsx_gesvdj_*_dev); A is DESTROYED.  Returns (U, s, Vt, info): the
+        thin factors (None with compute_uv=False), s as a device float64 tensor of min(m, n) entries, descending, and
+        info as a host int (1: the last allowed sweep still rotated).  Synchronises the stream: the host reads one
+        counter per sweep."""
+        import ctypes as C
+
+        _rowmajor(A, "gesvdj_")
+        m, n = A.shape
+        k = min(m, n)
+        s = torch.zeros(k, dtype=torch.float64, device=A.device)
+        U = torch.zeros((m, k), dtype=A.dtype, device=A.device) if compute_uv else None
+        Vt = torch.zeros((k, n), dtype=A.dtype, device=A.device) if compute_uv else None
+        info = C.c_int(0)
+        name = f"lsx_gesvdj_{self._suffix(A)}_dev"
+        if k:
+            N.check(getattr(self.lib, name)(self.h.ptr, 1 if compute_uv else 0, m, n, A.data_ptr(), max(A.stride(0), 1),
+                                            s.data_ptr(), U.data_ptr() if compute_uv else None, max(k, 1),
+                                            Vt.data_ptr() if compute_uv else None, max(n, 1), C.byref(info)), name)
+        return U, s, Vt, info.value
+
+    def gelss_(self, A: torch.Tensor, B: torch.Tensor, rcond: float = -1.0):
+        """The minimum-norm least-squares solution for any shape and rank (lsx_gelss_*_dev); A is DESTROYED, B is kept.
+        Returns (X, s, rank, info): X (n x nrhs) and s (device float64) are new tensors, rank (singular values above
+        rcond * s[0]; rcond < 0: max(m, n) times the unit roundoff) and info are host ints.  Synchronises the stream."""
+        import ctypes as C
+
+        _rowmajor(A, "gelss_ A")
+        _rowmajor(B, "gelss_ B")
+        m, n = A.shape
+        if B.shape[0] != m:
+            raise ValueError("gelss_: B needs as many rows as A")
+        if B.dtype != A.dtype:
+            raise TypeError("gelss_: both operands must have the same dtype")
+        nrhs = B.shape[1]
+        X = torch.zeros((n, nrhs), dtype=A.dtype, device=A.device)
+        s = torch.zeros(min(m, n), dtype=torch.float64, device=A.device)
+        rank, info = C.c_int(0), C.c_int(0)
+        name = f"lsx_gelss_{self._suffix(A)}_dev"
+        if m and n and nrhs:
+            N.check(getattr(self.lib, name)(self.h.ptr, m, n, nrhs, A.data_ptr(), max(A.stride(0), 1), B.data_ptr(),
+                                            max(B.stride(0), 1), X.data_ptr(), max(X.stride(0), 1), float(rcond),
+                                            s.data_ptr(), C.byref(rank), C.byref(info)), name)
+        return X, s, rank.value, info.value
+
     def col_norms(self, A: torch.Tensor) -> torch.Tensor:
         """The 2-norm of every column of A: a device double[n], fp64 sums in a fixed order (lsx_colnrm2_*_dev)."""
         _rowmajor(A, "col_norms")

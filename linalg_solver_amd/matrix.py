@@ -705,12 +705,17 @@ class Matrix:
             raise ValueError("qr_array needs at least as many rows as columns")
         return dense.qr(A)
 
-    def least_squares_array(self, rhs, residuals: bool = False):
+    def least_squares_array(self, rhs, residuals: bool = False, min_norm: bool = False, rcond=None):
         """The x that minimises ||rhs - self x||_2, through Householder QR, for rows >= cols (ValueError otherwise; an
         underdetermined system has no unique minimiser).  rhs: a vector or a rows x nrhs array.  residuals=True
         returns (x, ||rhs - self x||_2 per right-hand side).  NoSolution() when a diagonal entry of R is exactly zero or
         NaN -- self does not have full column rank -- as inverse_array answers for a singular matrix.  Unlike
-        find_preimage_of this does not ask for a consistent system."""
+        find_preimage_of this does not ask for a consistent system.
+        min_norm=True: the minimiser of smallest 2-norm, through the SVD (lsx_gelss_*), for ANY shape and rank; singular
+        values up to rcond * the largest (rcond=None: max(rows, cols) times the unit roundoff) count as zero.  It never
+        answers NoSolution()."""
+        if min_norm:
+            return self._least_squares_min_norm(rhs, residuals, rcond)
         if getattr(self, "_dev", None) is not None and self._items is None:
             import torch
 
@@ -745,6 +750,99 @@ class Matrix:
         if info != 0:
             return Matrix.NoSolution()
         return (x, resid) if residuals else x
+
+    # ---- Jacobi SVD (lsx_gesvdj_*, lsx_gelss_*) ----
+    def _on_device(self) -> bool:
+        return getattr(self, "_dev", None) is not None and self._items is None
+
+    def _least_squares_min_norm(self, rhs, residuals, rcond):
+        if self._on_device():
+            import torch
+
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            m = A.shape[0]
+            B = rhs if hasattr(rhs, "is_cuda") else torch.as_tensor(np.asarray(rhs, dtype=np.float64))
+            B = B.to(device=A.device, dtype=torch.float64)
+            vec = B.dim() == 1
+            if B.shape[0] != m:
+                raise ValueError("Matrix dimensions must match")
+            Bm = B.reshape(m, -1).contiguous()
+            dev = DeviceSolver(self._dev.device.index)
+            X = dev.gelss_(A.clone(), Bm, -1.0 if rcond is None else float(rcond))[0]
+            x = X[:, 0].clone() if vec else X
+            if not residuals:
+                return x
+            R = Bm.clone()
+            dev.gemm_sub_(R, A.contiguous(), X)
+            res = dev.col_norms(R)
+            return x, (res[0] if vec else res)
+        A = self._array()
+        b = np.asarray(rhs, dtype=np.float64)
+        if b.shape[:1] != (A.shape[0],):
+            raise ValueError("Matrix dimensions must match")
+        x, resid, _, _ = dense.lstsq_min_norm(A, b, rcond=rcond)
+        return (x, resid) if residuals else x
+
+    def svd_array(self):
+        """(U, s, Vt) as arrays (device tensors for a matrix built from one): the thin factors of self = U diag(s) Vt
+        with s descending, by one-sided Jacobi (lsx_gesvdj_*).  U is orthonormal for every input; rows of Vt that belong
+        to an exactly zero singular value are zero rows."""
+        if self._on_device():
+            from .device import DeviceSolver
+
+            U, s, Vt, _ = DeviceSolver(self._dev.device.index).gesvdj_(self._dev64().clone())
+            return U, s, Vt
+        U, s, Vt, _ = dense.svd(self._array())
+        return U, s, Vt
+
+    def singular_values(self):
+        """The singular values, descending: a numpy array (a device tensor for a matrix built from one)."""
+        if self._on_device():
+            from .device import DeviceSolver
+
+            return DeviceSolver(self._dev.device.index).gesvdj_(self._dev64().clone(), compute_uv=False)[1]
+        return dense.svdvals(self._array())
+
+    def _svals_host(self) -> "np.ndarray":
+        s = self.singular_values()
+        return s.cpu().numpy() if hasattr(s, "is_cuda") else s
+
+    def norm2(self) -> float:
+        """The 2-norm: the largest singular value (0.0 for a matrix without rows or columns)."""
+        s = self._svals_host()
+        return float(s[0]) if len(s) else 0.0
+
+    def cond2(self) -> float:
+        """The 2-norm condition number s[0] / s[-1]; inf when the smallest singular value is exactly zero."""
+        s = self._svals_host()
+        if not len(s):
+            return 1.0
+        return float("inf") if s[-1] == 0.0 else float(s[0] / s[-1])
+
+    def numerical_rank(self, rcond=None) -> int:
+        """The number of singular values above rcond * the largest (rcond=None: max(rows, cols) times the unit
+        roundoff).  rank() keeps its pivot tolerance; this one has none."""
+        s = self._svals_host()
+        if not len(s):
+            return 0
+        if rcond is None:
+            rcond = max(self.rows, self.cols) * dense.EPS64 / 2
+        return int(np.sum(s > rcond * s[0]))
+
+    def pinv_array(self, rcond=None):
+        """The Moore-Penrose pseudo-inverse (cols x rows) as an array (a device tensor for a matrix built from one):
+        lsx_gelss_* with the identity as right-hand sides."""
+        if self._on_device():
+            import torch
+
+            from .device import DeviceSolver
+
+            A = self._dev64()
+            eye = torch.eye(A.shape[0], dtype=torch.float64, device=A.device)
+            return DeviceSolver(self._dev.device.index).gelss_(A.clone(), eye, -1.0 if rcond is None else float(rcond))[0]
+        return dense.pinv(self._array(), rcond=rcond)
 
     def transpose(self) -> "Matrix":
         return Matrix([[self.items[j][i] for j in range(self.rows)] for i in range(self.cols)])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | potri | posx | gecon | gerfs | equil | qr [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | potri | posx | gecon | gerfs | equil | qr | svd [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -96,6 +96,41 @@ def main():
                 fl = 2.0 * m * n * n - 2.0 / 3 * n ** 3
                 print(f"qr {str(dt)[6:]} {m} x {n}: geqrf {tq - tcopy:.3f} ms ({fl / (tq - tcopy) / 1e9:.1f} TFLOP/s)  gels nrhs={nrhs} "
                       f"{tg - tcopy:.3f} ms\n    geqrf shares: {shares(qrf)}", flush=True)
+    if "svd" in args.what:
+        # Jacobi SVD: gesvdj with and without vectors beside geqrf of the same matrix and, where torch offers it on the
+        # device, torch.linalg.svd / svdvals; sweeps and rotations of the call, launches of the round kernel
+        for dt in ((torch.float32,) if args.f32 else (torch.float64, torch.float32)):
+            for m, n in ((512, 512), (1024, 1024), (2048, 2048), (16384, 256)):
+                A0 = torch.empty(m, n, dtype=dt, device="cuda")
+                dev.fill_(A0, gen.U11, 5)
+                A = A0.clone()
+                tau = torch.zeros(min(m, n), dtype=dt, device="cuda")
+                out = {}
+
+                def qrf():
+                    A.copy_(A0)
+                    dev.geqrf_(A, tau)
+
+                def sv(uv):
+                    A.copy_(A0)
+                    out[uv] = dev.gesvdj_(A, compute_uv=uv)[3]
+                tcopy, _ = timeit(lambda: A.copy_(A0), reps=2, warm=1)
+                tq, _ = timeit(qrf, reps=2, warm=1)
+                t1, _ = timeit(lambda: sv(True), reps=2, warm=1)
+                sweeps, rot = dev.h.get_option("gesvdj_sweeps"), dev.h.get_option("gesvdj_rotations")
+                t0, _ = timeit(lambda: sv(False), reps=2, warm=1)
+                p = min(m, n)
+                launches = (p + (p & 1) - 1) * sweeps
+                try:
+                    tt1, _ = timeit(lambda: torch.linalg.svd(A0, full_matrices=False), reps=2, warm=1)
+                    tt0, _ = timeit(lambda: torch.linalg.svdvals(A0), reps=2, warm=1)
+                    ref = f"torch.linalg.svd {tt1:.1f} ms, svdvals {tt0:.1f} ms"
+                except Exception as e:   # not offered for this type / device
+                    ref = f"torch.linalg.svd not available ({type(e).__name__})"
+                print(f"svd {str(dt)[6:]} {m} x {n}: gesvdj vectors {t1 - tcopy:.1f} ms, values only {t0 - tcopy:.1f} ms "
+                      f"(info {out[True]}/{out[False]}, {sweeps} sweeps, {rot} rotations, {launches} round launches, "
+                      f"{(t0 - tcopy) * 1e3 / max(launches, 1):.1f} us per round without vectors)  geqrf {tq - tcopy:.1f} ms  | {ref}",
+                      flush=True)
     if "mfma" in args.what:
         for bpc in (1, 2):
             t64, mhz = dev.h.mfma_peak(False, 200000, bpc)
