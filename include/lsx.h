@@ -625,6 +625,48 @@ int lsx_gelss_f64(lsx_handle_t h, int m, int n, int nrhs, const double *A, int l
 int lsx_gelss_f32(lsx_handle_t h, int m, int n, int nrhs, const float *A, int lda, const float *B, int ldb, float *X,
                   int ldx, double rcond, double *s, double *resid, int *rank, int *info);
 
+/* ---- Symmetric eigensolver by two-sided Jacobi (the vendor libraries' syevj) ---- */
+/* A (n x n, symmetric, row-major, UPPER) = V diag(w) V^T.  Only the upper triangle of A is read: the strictly lower
+ * triangle may hold anything, NaN included, and no kernel loads it.  w holds n DOUBLES for both precisions, ASCENDING
+ * (LAPACK's syev order, a stable sort of the diagonal).  With jobz = 1 V is n x n and column i is the eigenvector of
+ * w[i]; with jobz = 0 V may be NULL, no rotations are accumulated and w has the bits jobz = 1 gives.  Nothing here is
+ * cooperative: no kernel waits for another workgroup, there is no spin and no time-out outcome, lsx_check_status has
+ * nothing to report.  The call is deterministic: two calls give identical bits, and so do any alignment and any leading
+ * dimension of the caller's arrays (they are only copied from and gathered into).
+ * The host form leaves A alone.  The _dev form must be taken to destroy dA: what it holds afterwards is unspecified.
+ * (The present kernels only read its upper triangle and leave every element as it was.)
+ *
+ * Algorithm.  The work matrix W (n x n, both triangles) is built from the upper triangle of A and mirrored; with
+ * jobz = 1 Z = I.  nrm = ||A||_F from the upper triangle, the off-diagonal squares counted twice, summed in fp64 in a
+ * fixed order without atomics and without scaling (the numeric domain of lsx_colnrm2_*: nrm^2 a finite normal fp64
+ * number).  thr = u nrm, u = 2^-53 (fp64) or 2^-24 (fp32).  A sweep is the P - 1 rounds of the round-robin order of
+ * lsx_gesvdj_* over P = n + (n & 1) players.  All decisions of a round are taken from W as it stands before the round:
+ * pair (i < j), a = w_ii, b = w_jj, c = w_ij (the UPPER element) in fp64; rotate iff |c| > thr (a NaN fails the
+ * comparison); zeta = (b - a) / (2 c), t = sgn(zeta) / (|zeta| + sqrt(1 + zeta^2)) with sgn(0) = +1 (|zeta| > 2^500:
+ * t = 1 / (2 zeta)), cs = 1 / sqrt(1 + t^2), sn = cs t.  Then W <- G W G^T over all rotated pairs of the round: rows
+ * i, j: x' = cs x - sn y, y' = sn x + cs y in fp64, each element rounded to the matrix's type once; the same on columns
+ * i, j of every row of the row-rotated matrix, rounded once again; w_ij = w_ji = 0 exactly; rows i, j of Z like the rows
+ * of W.  Rows and columns of pairs that are not rotated keep their bits.  The two triangles are computed in different
+ * orders and may drift apart at rounding level; decisions read the upper element only, the eigenvalues are the diagonal.
+ * A sweep without a rotation ends the iteration; at most "syevj_max_sweeps" sweeps run (option, 1 .. 100, default 60).
+ * If the last allowed sweep still rotated *info = 1 and the results are returned all the same; otherwise *info = 0.  The
+ * options "syevj_sweeps" and "syevj_rotations" (saturating at INT_MAX) read back the last call.  Then
+ * w_i = (double) w_ii, sorted ascending (stable), and V[:, i] is the row of Z that belongs to it.
+ * Inside the numeric domain A 2^d gives the same V, sweeps and rotations, and w 2^d.
+ * A NaN or an infinity in the upper triangle of A: every entry of w is NaN, V is unspecified, *info = 0; nothing
+ * iterates ("syevj_sweeps" reads 0), loops or faults.
+ * The host reads one counter per sweep, so ALL forms synchronise the handle's stream.  info is a host int in all forms
+ * and may be NULL; d_w is a device array in the _dev forms.
+ * This is the unblocked method: a round streams W and Z once and takes two launches, so it is bandwidth- and
+ * launch-bound and meant for orders up to a few thousand.
+ *
+ * LSX_ERR_ARG for n < 0, lda < n, jobz other than 0 or 1, ldv < n with jobz = 1, or a NULL pointer with n > 0.
+ * n == 0 is LSX_OK with *info = 0 and nothing else touched. */
+int lsx_syevj_f64_dev(lsx_handle_t h, int jobz, int n, double *dA, int lda, double *d_w, double *dV, int ldv, int *info);
+int lsx_syevj_f32_dev(lsx_handle_t h, int jobz, int n, float *dA, int lda, double *d_w, float *dV, int ldv, int *info);
+int lsx_syevj_f64(lsx_handle_t h, int jobz, int n, const double *A, int lda, double *w, double *V, int ldv, int *info);
+int lsx_syevj_f32(lsx_handle_t h, int jobz, int n, const float *A, int lda, double *w, float *V, int ldv, int *info);
+
 /* ---- Cholesky: condition estimate and error bounds (LAPACK's lansy, pocon, porfs) ---- */
 /* Storage as above: row-major, UPPER, A = U^T U.  The strictly lower triangle of A and of U is never loaded and never
  * written by any of these, inside a diagonal tile or block included: it may hold NaN.  Nothing here is cooperative: no

@@ -182,6 +182,10 @@ _SIGS = {
     "lsx_gelss_f32_dev": [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, C.POINTER(_i), C.POINTER(_i)],
     "lsx_gelss_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i, C.c_double, _dp, _dp, C.POINTER(_i), C.POINTER(_i)],
     "lsx_gelss_f32": [_vp, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, C.c_double, _dp, _dp, C.POINTER(_i), C.POINTER(_i)],
+    "lsx_syevj_f64_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, _i, C.POINTER(_i)],
+    "lsx_syevj_f32_dev": [_vp, _i, _i, _vp, _i, _vp, _vp, _i, C.POINTER(_i)],
+    "lsx_syevj_f64": [_vp, _i, _i, _dp, _i, _dp, _dp, _i, C.POINTER(_i)],
+    "lsx_syevj_f32": [_vp, _i, _i, _fp, _i, _dp, _fp, _i, C.POINTER(_i)],
     "lsx_matmul_f64": [_vp, _i, _i, _i, _dp, _i, _dp, _i, _dp, _i],
     "lsx_fill_f64_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],
     "lsx_fill_f32_dev": [_vp, _i, _u64, _i, _i, _vp, _i, _i, _i],

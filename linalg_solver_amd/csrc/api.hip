@@ -1690,6 +1690,121 @@ static int gelss_host(lsx_handle_t h, int m, int n, int nrhs, const T *A, int ld
     return LSX_OK;
 }
 
+// ---------------------------------------------------------------- two-sided Jacobi: A = V diag(w) V^T (kernels_eig.hip)
+// The work matrix W (n x n, both triangles, from the upper triangle of A) is driven to diagonal form by plane rotations
+// W <- G W G^T; Z (the identity to begin with) receives the row rotations, so W = Z A Z^T, the eigenvalues are the
+// diagonal of W and the eigenvectors the rows of Z.
+//   a sweep = P - 1 rounds of the round-robin order; a round = one decision launch [OTHER] and one rotation launch [PANEL]
+//   the work matrix, ||A||_F, the diagonal, the sorted gather of w and V (svd_gather_kernel)                 [OTHER]
+// The host reads ||A||_F before the first sweep (a NaN or infinity ends the call there: w all NaN, nothing iterates), the
+// rotation counter once per sweep and the diagonal after the last one, so every form synchronises the stream.
+// eig_work is laid out once per call, here; nothing called from here carves anything.
+template <typename T>
+struct EigWork {
+    T *W = nullptr, *Z = nullptr;
+    double *rowsq = nullptr, *nrm = nullptr, *diag = nullptr;
+    int *perm = nullptr, *count = nullptr;
+    EigRound round;
+    int ldw = 0;
+};
+template <typename T>
+static int carve_eig(lsx_handle_t h, int n, int jobz, EigWork<T> *w) {
+    const int np = (n + (n & 1)) / 2;
+    w->ldw = svd_ld(n, sizeof(T));
+    return carve(h, h->eig_work, [&](Carver &c) {
+        w->W = c.take<T>((size_t)n * w->ldw);
+        if (jobz) w->Z = c.take<T>((size_t)n * w->ldw);
+        w->rowsq = c.take<double>(n);
+        w->nrm = c.take<double>(1);
+        w->diag = c.take<double>(n);
+        w->perm = c.take<int>(n);
+        w->count = c.take<int>(1);
+        w->round.pair = c.take<int2>(np);
+        w->round.rot = c.take<double2>(np);
+        w->round.flag = c.take<int>(np);
+    });
+}
+
+// dA is only read (its upper triangle); d_w: n doubles on the device, ascending; column i of V belongs to d_w[i]
+template <typename T>
+static int syevj_dev(lsx_handle_t h, int jobz, int n, const T *A, int lda, double *d_w, T *V, int ldv, int *info) {
+    LSX_ARG(h && (jobz == 0 || jobz == 1) && n >= 0 && lda >= n && (!jobz || ldv >= n));
+    if (info) *info = 0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A && d_w && (!jobz || V));
+    EigWork<T> w;
+    LSX_TRY(carve_eig<T>(h, n, jobz, &w));
+    h->syevj_sweeps = 0;
+    h->syevj_rotations = 0;
+    LSX_TRY(launch_eig_init<T>(h, n, A, lda, w.W, w.ldw));
+    if (jobz) LSX_TRY(launch_svd_init<T>(h, n, n, (const T *)nullptr, 0, 0, w.Z, w.ldw));
+    LSX_TRY(launch_eig_norm<T>(h, n, w.W, w.ldw, w.rowsq, w.nrm));
+    double nrm = 0.0;
+    LSX_HIP(hipMemcpyAsync(&nrm, w.nrm, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    std::vector<double> diag(n);
+    bool finite = std::isfinite(nrm);
+    int last = 0;
+    if (finite) {
+        const double thr = (0.5 * (double)Real<T>::eps) * nrm;
+        const int P = n + (n & 1);
+        long long total = 0;
+        for (int sweep = 1; sweep <= h->syevj_max_sweeps; ++sweep) {
+            LSX_HIP(hipMemsetAsync(w.count, 0, sizeof(int), h->stream));
+            for (int r = 0; r < P - 1; ++r) {
+                LSX_TRY(launch_eig_decide<T>(h, n, r, w.W, w.ldw, thr, w.round, w.count));
+                LSX_TRY(launch_eig_round<T>(h, n, w.W, w.ldw, w.Z, w.ldw, w.round));
+            }
+            LSX_HIP(hipMemcpyAsync(&last, w.count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            LSX_HIP(hipStreamSynchronize(h->stream));
+            h->syevj_sweeps = sweep;
+            total += last;
+            if (last == 0) break;
+        }
+        h->syevj_rotations = total > INT_MAX ? INT_MAX : (int)total;
+        LSX_TRY(launch_eig_diag<T>(h, n, w.W, w.ldw, w.diag));
+        LSX_HIP(hipMemcpyAsync(diag.data(), w.diag, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        for (double v : diag) finite = finite && !std::isnan(v);   // a sum that overflowed on the way
+    }
+    if (info) *info = (finite && last != 0) ? 1 : 0;
+    if (!finite) {
+        LSX_TRY(launch_svd_fill<double>(h, 1, n, (double)NAN, d_w, n));
+        LSX_HIP(hipStreamSynchronize(h->stream));
+        return LSX_OK;
+    }
+    std::vector<int> perm(n);
+    for (int i = 0; i < n; ++i) perm[i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return diag[a] < diag[b]; });
+    LSX_HIP(hipMemcpyAsync(w.perm, perm.data(), sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+    // w[i] = diag[perm[i]], V[r][i] = Z[perm[i]][r]: the SVD's gather with no V^T and U = V
+    LSX_TRY(launch_svd_gather<T>(h, n, 0, n, w.W, w.ldw, w.Z, w.ldw, w.diag, w.perm, d_w, (T *)nullptr, 0, jobz ? V : (T *)nullptr, ldv));
+    LSX_HIP(hipStreamSynchronize(h->stream));   // perm is read by the upload
+    return LSX_OK;
+}
+
+// A is not modified: its upper triangle is staged (block rows from their diagonal block on)
+template <typename T>
+static int syevj_host(lsx_handle_t h, int jobz, int n, const T *A, int lda, double *wout, T *V, int ldv, int *info) {
+    LSX_ARG(h && (jobz == 0 || jobz == 1) && n >= 0 && lda >= n && (!jobz || ldv >= n));
+    if (info) *info = 0;
+    if (n == 0) return LSX_OK;
+    LSX_ARG(A && wout && (!jobz || V));
+    const int ld = ld_for(n);
+    T *dA = nullptr, *dV = nullptr; double *dw = nullptr;
+    LSX_TRY(carve(h, h->staging, [&](Carver &c) {
+        dA = c.take<T>((size_t)n * ld);
+        dw = c.take<double>(n);
+        if (jobz) dV = c.take<T>((size_t)n * ld);
+    }));
+    LSX_TRY(upper_h2d<T>(h, n, A, lda, dA, ld));
+    LSX_TRY(syevj_dev<T>(h, jobz, n, dA, ld, dw, dV, ld, info));
+    LSX_HIP(hipMemcpyAsync(wout, dw, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    if (jobz) LSX_TRY(d2h<T>(h, n, n, dV, ld, V, ldv));
+    LSX_HIP(hipStreamSynchronize(h->stream));
+    return LSX_OK;
+}
+
 // A^T X = B from the factors (kernels_trsvt.hip).  Work space as in getrs_dev, so the two share what they grow.
 // may_block = false: the single-column solves inside the estimators, which keep the grouped path whatever the option says.
 template <typename T>
@@ -2541,7 +2656,7 @@ int lsx_destroy(lsx_handle_t h) {
     for (auto &ev : h->prof.pending) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto &e : h->prof.pool) (void)hipEventDestroy(e);
     for (DevBuf *b : {&h->staging, &h->tinv, &h->rhs_work, &h->mixed_resid, &h->getri_work, &h->rref_first, &h->cond,
-                      &h->refine, &h->equil, &h->qr_work, &h->svd_work, &h->xchg, &h->moves_all, &h->scratch})
+                      &h->refine, &h->equil, &h->qr_work, &h->svd_work, &h->eig_work, &h->xchg, &h->moves_all, &h->scratch})
         if (b->p) (void)hipFree(b->p);
     if (h->moves_buf[0]) (void)hipFree(h->moves_buf[0]);
     if (h->dev_status) (void)hipFree(h->dev_status);
@@ -2674,6 +2789,9 @@ int lsx_set_option(lsx_handle_t h, const char *key, int value) {
     } else if (!strcmp(key, "gesvdj_max_sweeps")) {   // Jacobi SVD: most sweeps of a call (dgesvj's NSWEEP = 30)
         LSX_ARG(value >= 1 && value <= 60);
         h->gesvdj_max_sweeps = value;
+    } else if (!strcmp(key, "syevj_max_sweeps")) {   // Jacobi eigensolver: most sweeps of a call
+        LSX_ARG(value >= 1 && value <= 100);
+        h->syevj_max_sweeps = value;
     } else if (!strcmp(key, "potrs_few_max")) {   // Cholesky solve: largest nrhs on the few-column step kernels; 0 = never
         LSX_ARG(value >= 0 && value <= 8);
         h->potrs_few_max = value;
@@ -2724,6 +2842,9 @@ int lsx_get_option(lsx_handle_t h, const char *key, int *value) {
     else if (!strcmp(key, "gesvdj_max_sweeps")) *value = h->gesvdj_max_sweeps;
     else if (!strcmp(key, "gesvdj_sweeps")) *value = h->gesvdj_sweeps;
     else if (!strcmp(key, "gesvdj_rotations")) *value = h->gesvdj_rotations;
+    else if (!strcmp(key, "syevj_max_sweeps")) *value = h->syevj_max_sweeps;
+    else if (!strcmp(key, "syevj_sweeps")) *value = h->syevj_sweeps;
+    else if (!strcmp(key, "syevj_rotations")) *value = h->syevj_rotations;
     else if (!strcmp(key, "pocon_solves")) *value = h->pocon_solves;
     else if (!strcmp(key, "porfs_steps")) *value = h->porfs_steps;
     else if (!strcmp(key, "porfs_solves")) *value = h->porfs_solves;
@@ -3603,6 +3724,20 @@ LSX_QR_ENTRIES(f32, float)
 LSX_SVD_ENTRIES(f64, double)
 LSX_SVD_ENTRIES(f32, float)
 #undef LSX_SVD_ENTRIES
+
+// ---- symmetric eigensolver by two-sided Jacobi
+#define LSX_EIG_ENTRIES(SFX, T)                                                                                           \
+    int lsx_syevj_##SFX##_dev(lsx_handle_t h, int jobz, int n, T *dA, int lda, double *d_w, T *dV, int ldv, int *info) {  \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return syevj_dev<T>(h, jobz, n, dA, lda, d_w, dV, ldv, info);                                                     \
+    }                                                                                                                     \
+    int lsx_syevj_##SFX(lsx_handle_t h, int jobz, int n, const T *A, int lda, double *w, T *V, int ldv, int *info) {      \
+        LSX_DEVICE_GUARD(h);                                                                                              \
+        return syevj_host<T>(h, jobz, n, A, lda, w, V, ldv, info);                                                        \
+    }
+LSX_EIG_ENTRIES(f64, double)
+LSX_EIG_ENTRIES(f32, float)
+#undef LSX_EIG_ENTRIES
 
 int lsx_fill_f64_dev(lsx_handle_t h, int kind, uint64_t seed, int m, int n, double *dA, int lda,
                      int row_off, int col_off) {

@@ -110,6 +110,7 @@ struct lsx_handle_s {
     int rref_blocked = 1;       // 1: large inputs with LSX_PIVOT_MAX take the blocked row reduction (option rref_blocked)
     int getrs_t_blocked_min = 64;   // transposed solve: smallest nrhs that takes the blocked (MFMA) sweeps when n > 128; 0 = never
     int gesvdj_max_sweeps = 30;   // Jacobi SVD: most sweeps of a call (1 .. 60; dgesvj's NSWEEP)
+    int syevj_max_sweeps = 60;    // Jacobi eigensolver: most sweeps of a call (1 .. 100)
     int potrs_few_max = 0;   // Cholesky solve: largest nrhs (<= 8) that takes the few-column step kernels; 0 = never
     int lauum_descending = 0;   // lsx_lauum_tn_*: 1 = the k-slabs in descending order, the form lsx_potri_* always runs; 0 = k ascending
     int potri_order = 0;     // SPD inverse, V^T V tiles: 0 = deepest first (ascending tile column), 1 = the symmetric update's order
@@ -132,6 +133,8 @@ struct lsx_handle_s {
     int porfs_solves = 0;    // single-right-hand-side estimator solves of the last porfs
     int gesvdj_sweeps = 0;   // sweeps of the last lsx_gesvdj_* / lsx_gelss_* call
     int gesvdj_rotations = 0;   // rotations of that call, saturating at INT_MAX
+    int syevj_sweeps = 0;    // sweeps of the last lsx_syevj_* call
+    int syevj_rotations = 0;    // rotations of that call, saturating at INT_MAX
     int panel_fallbacks = 0;    // host-buffer factorisations redone with panel mode 0 after an exchange time-out
     // ---- buffers.  A DevBuf is sized where it is used (lsx::carve / lsx::reserve) and only grows.  Growing frees the old
     // block, so no function keeps a pointer into a buffer across a call that may grow the SAME buffer.  Who holds what
@@ -154,6 +157,7 @@ struct lsx_handle_s {
     //   gesvdj_dev, gelss_dev     svd_work, laid out once per call by carve_svd and held across geqrf_dev / ormqr_dev (qr_work,
     //                             which those two keep to themselves) and the products; gelss_dev's U, V^T, s and Y are
     //                             pieces of the same carve
+    //   syevj_dev                 eig_work, laid out once per call by carve_eig; it calls nothing that carves
     //   gecon_dev, pocon_dev      cond, across getrs_dev / getrs_t_dev and potrs_few_*
     //   refine_loop               refine, across getrs_dev / getrs_t_dev (gerfs_dev) and potrs_few_apply (porfs_dev)
     //   gesvx_dev                 equil, across geequ_dev (equil again, never more than gesvx_dev carved), lange_dev
@@ -180,6 +184,8 @@ struct lsx_handle_s {
     DevBuf qr_work;      // Householder QR: V, V^T V, T and its transpose, the two W strips, partial-sum slots, pivot rows,
                          // and for panels of more than 4096 rows the pieces of V^T C (qr_vt_times)
     DevBuf svd_work;     // Jacobi SVD: W, Z, the row norms, the permutation, the rotation counter, tau, and gelss's U, V^T, s, Y
+    DevBuf eig_work;     // Jacobi eigensolver: W, Z, the row sums of the norm, the diagonal, the permutation, the rotation
+                         // counter and the round's pairs, rotations and flags
     DevBuf xchg;         // few-RHS solve (kernels_trsv.hip, third form): exchange granules validated by an epoch, never cleared
     unsigned xchg_epoch = 0;
     DevBuf moves_all;    // look-ahead driver with the XCD-scope panel: one gather list per panel
@@ -589,5 +595,25 @@ template <typename T>
 int launch_svd_scale_rows(lsx_handle_t h, int k, int nc, int rank, const double *s, T *Y, int ldy);
 template <typename T>
 int launch_svd_fill(lsx_handle_t h, int rows, int cols, T value, T *D, int ldd);
+// Two-sided Jacobi for the symmetric eigenproblem (kernels_eig.hip).  W (n x n, both triangles) and Z (n x n) are laid out
+// like the SVD's work arrays (svd_ld).  EigRound: what the decision launch of a round leaves for its rotation launch, one
+// entry per position t < P / 2.  launch_eig_init: W from the upper triangle of A, mirrored, the padding zeroed.
+// launch_eig_norm: *nrm = ||A||_F from the upper triangle of W (rowsq: n doubles of work).  launch_eig_decide: round r,
+// *count += rotations.  launch_eig_round: W <- G W G^T in place, rows of Z (or null) alike.  launch_eig_diag: d_i = w_ii.
+struct EigRound {
+    int2 *pair = nullptr;      // (i, j), i < j; j >= n: the phantom player of an odd n
+    double2 *rot = nullptr;    // (cs, sn), valid where flag is set
+    int *flag = nullptr;       // 1: the pair is rotated in this round
+};
+template <typename T>
+int launch_eig_init(lsx_handle_t h, int n, const T *A, int lda, T *W, int ldw);
+template <typename T>
+int launch_eig_norm(lsx_handle_t h, int n, const T *W, int ldw, double *rowsq, double *nrm);
+template <typename T>
+int launch_eig_decide(lsx_handle_t h, int n, int r, const T *W, int ldw, double thr, EigRound er, int *count);
+template <typename T>
+int launch_eig_round(lsx_handle_t h, int n, T *W, int ldw, T *Z, int ldz, EigRound er);
+template <typename T>
+int launch_eig_diag(lsx_handle_t h, int n, const T *W, int ldw, double *d);
 
 }  // namespace lsx

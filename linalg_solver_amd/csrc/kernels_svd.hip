@@ -14,20 +14,12 @@
 // waves in order 0 .. 3.  Rows of at most SVD_KEEP groups per thread stay in registers between the sums and the rotation
 // (W is read once per round); longer rows are read again, from L2.  Both forms add in the same order.
 #include "common.h"
+#include "jacobi.h"
 
 namespace lsx {
 
 constexpr int SVD_NT = 256;     // threads of a pair's workgroup
 constexpr int SVD_KEEP = 8;     // 16-byte groups per thread and row that stay in registers: rows up to 4096 fp64 / 8192 fp32
-
-template <typename T>
-struct Vec16;
-template <>
-struct Vec16<double> { typedef double2 type; };
-template <>
-struct Vec16<float> { typedef float4 type; };
-template <typename T>
-constexpr int vec_elems() { return 16 / (int)sizeof(T); }
 
 int svd_ld(int cols, size_t elem) {
     const int ve = 16 / (int)elem;
@@ -35,53 +27,11 @@ int svd_ld(int cols, size_t elem) {
 }
 int svd_keep_cols(size_t elem) { return SVD_NT * SVD_KEEP * (16 / (int)elem); }
 
-template <typename T>
-__device__ __forceinline__ void load16(const T *p, T (&v)[vec_elems<T>()]) {
-    const typename Vec16<T>::type x = *reinterpret_cast<const typename Vec16<T>::type *>(p);
-    const T *e = reinterpret_cast<const T *>(&x);
-#pragma unroll
-    for (int k = 0; k < vec_elems<T>(); ++k) v[k] = e[k];
-}
-template <typename T>
-__device__ __forceinline__ void store16(T *p, const T (&v)[vec_elems<T>()]) {
-    typename Vec16<T>::type x;
-    T *e = reinterpret_cast<T *>(&x);
-#pragma unroll
-    for (int k = 0; k < vec_elems<T>(); ++k) e[k] = v[k];
-    *reinterpret_cast<typename Vec16<T>::type *>(p) = x;
-}
-
-// the sum of v over the workgroup, in every thread; red: 4 doubles of LDS per value in flight
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // cs, sn of the rotation that makes the rows orthogonal; false: the pair is left alone (a NaN fails the comparison)
 __device__ __forceinline__ bool jacobi_rotation(double a, double b, double c, double tol, double *cs, double *sn) {
     if (!(fabs(c) > tol * sqrt(a) * sqrt(b))) return false;
-    const double zeta = (b - a) / (2.0 * c);
-    const double az = fabs(zeta);
-    double t;
-    if (az > 0x1p500) t = 1.0 / (2.0 * zeta);   // zeta^2 would overflow
-    else {
-        t = 1.0 / (az + sqrt(1.0 + zeta * zeta));
-        if (zeta < 0.0) t = -t;
-    }
-    *cs = 1.0 / sqrt(1.0 + t * t);
-    *sn = *cs * t;
+    jacobi_cs_sn(a, b, c, cs, sn);
     return true;
-}
-
-template <typename T>
-__device__ __forceinline__ void rotate16(T (&x)[vec_elems<T>()], T (&y)[vec_elems<T>()], double cs, double sn) {
-#pragma unroll
-    for (int k = 0; k < vec_elems<T>(); ++k) {
-        const double xi = (double)x[k], yj = (double)y[k];
-        x[k] = (T)(cs * xi - sn * yj);
-        y[k] = (T)(sn * xi + cs * yj);
-    }
 }
 
 // gq, gz: 16-byte groups of a row of W and of Z (ld / elements per group).  KEEP: gq <= SVD_NT * SVD_KEEP.
@@ -91,12 +41,9 @@ __global__ __launch_bounds__(SVD_NT) void svd_round_kernel(int p, int P, int r, 
     constexpr int VE = vec_elems<T>();
     __shared__ double red_s[3][SVD_NT / 64];
     const int tid = threadIdx.x;
-    // positions t and P - 1 - t of round r; position 0 holds player 0, position s >= 1 player ((s - 1 - r) mod (P - 1)) + 1
-    const int t = blockIdx.x, s1 = P - 1 - t;
-    const int m1 = P - 1;
-    int pa = t == 0 ? 0 : ((t - 1 - r) % m1 + m1) % m1 + 1;
-    int pb = ((s1 - 1 - r) % m1 + m1) % m1 + 1;
-    const int i = pa < pb ? pa : pb, j = pa < pb ? pb : pa;
+    // positions t and P - 1 - t of round r
+    int i, j;
+    round_robin_pair(P, r, (int)blockIdx.x, &i, &j);
     if (j >= p) return;   // the phantom player of an odd p
     T *wi = W + (size_t)i * ldw, *wj = W + (size_t)j * ldw;
     T xi[KEEP ? SVD_KEEP : 1][VE], xj[KEEP ? SVD_KEEP : 1][VE];

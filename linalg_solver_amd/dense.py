@@ -215,6 +215,33 @@ def svdvals(a, dtype=np.float64, handle: Optional[N.Handle] = None) -> np.ndarra
     return svd(a, compute_uv=False, dtype=dtype, handle=handle)[1]
 
 
+def eigh(a, eigvals_only: bool = False, dtype=np.float64, handle: Optional[N.Handle] = None):
+    """Eigenvalues and eigenvectors of a symmetric matrix by two-sided Jacobi (lsx_syevj_*): returns (w, V, info) with w
+    (n float64 values, ascending) and V (n x n, column i the eigenvector of w[i], so a = V diag(w) V^T) -- V is None with
+    eigvals_only=True.  Symmetry is the caller's assertion: only the upper triangle of a is used.  info = 1 says the last
+    allowed sweep still rotated (option "syevj_max_sweeps"); the results are returned all the same.  A NaN or infinity in
+    the upper triangle gives w all NaN."""
+    ct, sfx = _ct(dtype)
+    A = np.ascontiguousarray(a, dtype=dtype)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("eigh needs a square matrix")
+    n = A.shape[0]
+    w = np.zeros(n, dtype=np.float64)
+    V = None if eigvals_only else np.zeros((n, n), dtype=dtype)
+    info = C.c_int(0)
+    if n:
+        h = _h(handle)
+        N.check(getattr(h.lib, f"lsx_syevj_{sfx}")(h.ptr, 0 if eigvals_only else 1, n, _ptr(A, ct), n, _ptr(w, C.c_double),
+                                                  None if eigvals_only else _ptr(V, ct), n, C.byref(info)),
+                f"lsx_syevj_{sfx}")
+    return w, V, info.value
+
+
+def eigvalsh(a, dtype=np.float64, handle: Optional[N.Handle] = None) -> np.ndarray:
+    """The eigenvalues of a symmetric matrix, ascending (lsx_syevj_* with jobz = 0: the bits eigh returns)."""
+    return eigh(a, eigvals_only=True, dtype=dtype, handle=handle)[0]
+
+
 def lstsq_min_norm(a, b, rcond: Optional[float] = None, dtype=np.float64, handle: Optional[N.Handle] = None):
     """The minimum-norm solution of min ||b - a x||_2 for a matrix of any shape and rank, through the SVD (lsx_gelss_*).
     Returns (x, resid, rank, s): resid holds ||b - a x||_2 per right-hand side, rank counts the singular values above

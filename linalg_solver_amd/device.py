@@ -303,6 +303,28 @@ class DeviceSolver:
                                             s.data_ptr(), C.byref(rank), C.byref(info)), name)
         return X, s, rank.value, info.value
 
+    # -- symmetric eigensolver by two-sided Jacobi
+    def syevj_(self, A: torch.Tensor, compute_v: bool = True):
+        """Eigenvalues and eigenvectors of the symmetric A (n x n, only its upper triangle is used) in HBM
+        (lsx_syevj_*_dev); A is DESTROYED: what it holds afterwards is unspecified.  Returns (w, V, info): w as a device
+        float64 tensor of n entries, ascending, V (n x n, column i the eigenvector of w[i]; None with compute_v=False)
+        and info as a host int (1: the last allowed sweep still rotated).  Synchronises the stream: the host reads one
+        counter per sweep."""
+        import ctypes as C
+
+        _rowmajor(A, "syevj_")
+        n = A.shape[0]
+        if A.shape[1] != n:
+            raise ValueError("syevj_ needs a square matrix")
+        w = torch.zeros(n, dtype=torch.float64, device=A.device)
+        V = torch.zeros((n, n), dtype=A.dtype, device=A.device) if compute_v else None
+        info = C.c_int(0)
+        name = f"lsx_syevj_{self._suffix(A)}_dev"
+        if n:
+            N.check(getattr(self.lib, name)(self.h.ptr, 1 if compute_v else 0, n, A.data_ptr(), max(A.stride(0), 1),
+                                            w.data_ptr(), V.data_ptr() if compute_v else None, max(n, 1), C.byref(info)), name)
+        return w, V, info.value
+
     def col_norms(self, A: torch.Tensor) -> torch.Tensor:
         """The 2-norm of every column of A: a device double[n], fp64 sums in a fixed order (lsx_colnrm2_*_dev)."""
         _rowmajor(A, "col_norms")

@@ -844,6 +844,34 @@ class Matrix:
             return DeviceSolver(self._dev.device.index).gelss_(A.clone(), eye, -1.0 if rcond is None else float(rcond))[0]
         return dense.pinv(self._array(), rcond=rcond)
 
+    # ---- symmetric eigensolver by two-sided Jacobi (lsx_syevj_*) ----
+    def eigh_array(self):
+        """(w, V) as arrays (device tensors for a matrix built from one): self = V diag(w) V^T with w ascending and
+        column i of V the eigenvector of w[i], by two-sided Jacobi (lsx_syevj_*).  Symmetry is the caller's assertion,
+        the stance of pos_def=True: only the upper triangle is used.  ValueError for a non-square matrix.  Like
+        svd_array this returns what the iteration reached even if the last allowed sweep still rotated; dense.eigh and
+        DeviceSolver.syevj_ hand out that info word."""
+        if self.rows != self.cols:
+            raise ValueError("eigh_array needs a square matrix")
+        if self._on_device():
+            from .device import DeviceSolver
+
+            w, V, _ = DeviceSolver(self._dev.device.index).syevj_(self._dev64().clone())
+            return w, V
+        w, V, _ = dense.eigh(self._array())
+        return w, V
+
+    def eigvalsh(self):
+        """The eigenvalues of the symmetric matrix given by the upper triangle, ascending: a numpy array (a device
+        tensor for a matrix built from one).  ValueError for a non-square matrix."""
+        if self.rows != self.cols:
+            raise ValueError("eigvalsh needs a square matrix")
+        if self._on_device():
+            from .device import DeviceSolver
+
+            return DeviceSolver(self._dev.device.index).syevj_(self._dev64().clone(), compute_v=False)[0]
+        return dense.eigvalsh(self._array())
+
     def transpose(self) -> "Matrix":
         return Matrix([[self.items[j][i] for j in range(self.rows)] for i in range(self.cols)])
 

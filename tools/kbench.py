@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level micro-benchmarks on one MI355X (development tool, not the contract bench).
 
-    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | potri | posx | gecon | gerfs | equil | qr | svd [--n N] [--nb NB]
+    python tools/kbench.py mfma | gemm | panel3 | panelx | lu | trsvt | getrs_t | potrf | potri | posx | gecon | gerfs | equil | qr | svd | eig [--n N] [--nb NB]
 """
 import argparse
 import os
@@ -96,6 +96,44 @@ def main():
                 fl = 2.0 * m * n * n - 2.0 / 3 * n ** 3
                 print(f"qr {str(dt)[6:]} {m} x {n}: geqrf {tq - tcopy:.3f} ms ({fl / (tq - tcopy) / 1e9:.1f} TFLOP/s)  gels nrhs={nrhs} "
                       f"{tg - tcopy:.3f} ms\n    geqrf shares: {shares(qrf)}", flush=True)
+    if "eig" in args.what:
+        # symmetric eigensolver by two-sided Jacobi: syevj with and without vectors beside gesvdj of the same symmetric
+        # matrix and torch.linalg.eigh / eigvalsh, in one process; medians of 3 after a warm-up, the restoring copy
+        # timed alone and subtracted; sweeps and rotations of the call, rounds (two launches each)
+        for dt in ((torch.float32,) if args.f32 else (torch.float64, torch.float32)):
+            for n in (512, 1024, 2048):
+                G = torch.empty(n, n, dtype=dt, device="cuda")
+                dev.fill_(G, gen.U11, 5)
+                A0 = ((G + G.T) / 2).contiguous()
+                A = A0.clone()
+                out = {}
+
+                def ev(v):
+                    A.copy_(A0)
+                    out[v] = dev.syevj_(A, compute_v=v)[2]
+
+                def sv(uv):
+                    A.copy_(A0)
+                    dev.gesvdj_(A, compute_uv=uv)
+                _, tcopy = timeit(lambda: A.copy_(A0), reps=3, warm=1)
+                _, t1 = timeit(lambda: ev(True), reps=3, warm=1)
+                sweeps, rot = dev.h.get_option("syevj_sweeps"), dev.h.get_option("syevj_rotations")
+                _, t0 = timeit(lambda: ev(False), reps=3, warm=1)
+                _, s1 = timeit(lambda: sv(True), reps=3, warm=1)
+                _, s0 = timeit(lambda: sv(False), reps=3, warm=1)
+                ssweeps = dev.h.get_option("gesvdj_sweeps")
+                rounds = (n + (n & 1) - 1) * sweeps
+                try:
+                    _, tt1 = timeit(lambda: torch.linalg.eigh(A0, UPLO="U"), reps=3, warm=1)
+                    _, tt0 = timeit(lambda: torch.linalg.eigvalsh(A0, UPLO="U"), reps=3, warm=1)
+                    ref = f"torch.linalg.eigh {tt1:.1f} ms, eigvalsh {tt0:.1f} ms"
+                except Exception as e:   # not offered for this type / device
+                    ref = f"torch.linalg.eigh not available ({type(e).__name__})"
+                print(f"eig {str(dt)[6:]} {n} x {n}: syevj vectors {t1 - tcopy:.1f} ms, values only {t0 - tcopy:.1f} ms "
+                      f"(info {out[True]}/{out[False]}, {sweeps} sweeps, {rot} rotations, {rounds} rounds, "
+                      f"{(t0 - tcopy) * 1e3 / max(rounds, 1):.1f} us per round without vectors, "
+                      f"{(t1 - tcopy) * 1e3 / max(rounds, 1):.1f} us with)  gesvdj vectors {s1 - tcopy:.1f} ms, values only "
+                      f"{s0 - tcopy:.1f} ms ({ssweeps} sweeps)  | {ref}", flush=True)
     if "svd" in args.what:
         # Jacobi SVD: gesvdj with and without vectors beside geqrf of the same matrix and, where torch offers it on the
         # device, torch.linalg.svd / svdvals; sweeps and rotations of the call, launches of the round kernel
