@@ -14,18 +14,24 @@
 static __device__ long long *lsx_ts_buf;
 struct TsScope {
     int id;
-    __device__ void put(int tag) {
+    __device__ static void put_at(int tag, long long t) {
         long long *b = lsx_ts_buf;
         const int i = atomicAdd((int *)b, 1);
-        if (i < (1 << 20)) { b[1 + 2 * i] = tag; b[2 + 2 * i] = wall_clock64(); }
+        if (i < (1 << 20)) { b[1 + 2 * i] = tag; b[2 + 2 * i] = t; }
     }
+    __device__ void put(int tag) { put_at(tag, wall_clock64()); }
     __device__ TsScope(int id_) : id(id_) { if (lsx_ts_buf && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) put(id); }
     __device__ ~TsScope() { if (lsx_ts_buf && threadIdx.x == 0) put(id | 0x100); }
 };
 #define LSX_TS(id) TsScope ts_scope_(id)
+// a mark inside kernel `id` (workgroup 0 only, time taken earlier by the caller): tag = id | 0x200 | k << 12
+#define LSX_TS_MARK(id, k, t) do { if (lsx_ts_buf && blockIdx.x == 0) TsScope::put_at((id) | 0x200 | ((k) << 12), (long long)(t)); } while (0)
+#define LSX_TS_MARKS 1
 #define LSX_TS_SETTER(name) extern "C" void lsx_ts_set_##name(long long *p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(lsx_ts_buf), &p, sizeof p); }
 #else
 #define LSX_TS(id)
+#define LSX_TS_MARK(id, k, t)
+#define LSX_TS_MARKS 0
 #define LSX_TS_SETTER(name)
 #endif
 

@@ -26,6 +26,9 @@
 //    which it brings up to date after the barrier while its header shot for the next column is in flight).
 //  * Arg-max.  The three-phase DPP arg-max runs its first phase only when the high word of |a| already
 //    separates the candidates (ties fall back to the full form, so the choice is unchanged).
+//  * Ends.  Outside its column loop (marks: PX_TMARK) a launch issues the tile's loads in front of the
+//    placement handshake and the *info test, and a whole aligned panel travels through an LDS image both ways, whole rows
+//    per wave instruction (px_load_tile, the scatter behind the loop); the bookkeeping follows the scatter's stores.
 #include <algorithm>
 #include <type_traits>
 
@@ -73,6 +76,114 @@ __device__ __forceinline__ T bits_value(unsigned lo, unsigned hi) {
     return (T)__uint_as_float(lo);
 }
 
+// ---- The tile's way between memory and registers.  In registers lane l of wave w holds rows 64 r + l, columns
+// [WC w, WC w + WC): read or written directly, one instruction touches 64 rows in pieces of 16 bytes, `ldp` apart, and the
+// waves fetch every 128-byte line in halves at different times.  A whole panel (jb == PC_COLS, rows 16-byte aligned) goes
+// through LDS instead, one 64-row slab at a time: a wave instruction moves whole rows (64 lanes x 16 bytes = one fp64 row,
+// two fp32 rows), and the lanes pick their row-per-lane pieces out of the LDS image (or put them in, on the way back).
+// Bank conflicts, by the rule (not measured: no counter run of this kernel was taken).  An image row is the data plus
+// one 16-byte piece, so the row pitch is 16 bytes more than a multiple of the 256-byte bank row.  A lane-per-row 16-byte
+// access (lane l at l * pitch + constant) therefore lands on 16-byte slot (l + constant) mod 16.  A 16-byte LDS read is
+// served in four groups of 16 lanes (lanes 0-3, 12-15 and 20-27 form the first) and a 16-byte write in groups of 8
+// consecutive lanes; inside every such group the lane numbers differ mod 16, so the slots differ: no conflict.  The
+// row-wise accesses (a wave reads or writes one or two whole rows) are contiguous and conflict-free in any layout.
+enum { PX_PLAIN = 0, PX_WIDE = 1, PX_STAGED = 2 };
+// A copy the compiler cannot see through.  The tile's entries live in registers of their own from the load to the
+// scatter; handed to a 16-byte LDS access directly, they are merged into its four-register tuples for the whole kernel,
+// and a tile that has to sit on aligned tuples no longer fits the budget beside store16's fixed registers.
+__device__ __forceinline__ unsigned px_mov(const unsigned x) {
+    unsigned y;
+    asm("v_mov_b32 %0, %1" : "=v"(y) : "v"(x));
+    return y;
+}
+__device__ __forceinline__ double px_own_reg(const double v) {
+    return __hiloint2double((int)px_mov((unsigned)__double2hiint(v)), (int)px_mov((unsigned)__double2loint(v)));
+}
+__device__ __forceinline__ float px_own_reg(const float v) { return __uint_as_float(px_mov(__float_as_uint(v))); }
+template <typename T>
+struct PxImg {
+    static constexpr int EPV = 16 / (int)sizeof(T);             // elements of a 16-byte piece
+    static constexpr int LPR = PC_COLS / EPV;                    // lanes that cover a row: 64 (fp64), 32 (fp32)
+    static constexpr int RPI = 64 / LPR;                         // rows per wave instruction
+    static constexpr int NI = 64 / ((PX_NT / 64) * RPI);         // row instructions per wave and slab
+    static constexpr int ROWB = PC_COLS * (int)sizeof(T) + 16;   // bytes from row to row
+    static constexpr int BYTES = 64 * ROWB;
+    typedef T vec __attribute__((ext_vector_type(EPV)));
+};
+template <typename T>
+__device__ __forceinline__ int px_tile_mode(const int jb, const T *P, const int ldp) {
+    if (jb != PC_COLS || (size_t)P % 16 != 0 || ldp % 2 != 0) return PX_PLAIN;
+    return (ldp * sizeof(T)) % 16 == 0 ? PX_STAGED : PX_WIDE;
+}
+// Loads the workgroup's slice (rows >= m and columns >= jb read as zero).  The global loads are issued here and, in the
+// staged form, consumed here; in the other forms they may still be in flight on return.
+template <typename T, int RT>
+__device__ __forceinline__ void px_load_tile(T (&a)[RT][PX_WC], const int mode, char *img, const T *__restrict__ P,
+                                             const int ldp, const int m, const int jb, const int base) {
+    constexpr int WC = PX_WC, NW = PX_NT / 64;
+    typedef PxImg<T> I;
+    typedef typename I::vec vec;
+    typedef T v2t __attribute__((ext_vector_type(2)));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c0 = WC * wave;
+    if (mode == PX_STAGED) {
+        const int sub = lane / I::LPR, piece = lane % I::LPR;
+        vec t[I::NI];
+        auto issue = [&](const int r) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < I::NI; ++i) {
+                const int gi = base + 64 * r + (i * NW + wave) * I::RPI + sub;
+                t[i] = *(const vec *)(P + (size_t)(gi < m ? gi : 0) * ldp + I::EPV * piece);
+                if (gi >= m) t[i] = vec{};
+            }
+        };
+        issue(0);
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            if (r > 0) __syncthreads();   // the previous slab has left the image
+#pragma unroll
+            for (int i = 0; i < I::NI; ++i)
+                *(vec *)(img + ((i * NW + wave) * I::RPI + sub) * I::ROWB + 16 * piece) = t[i];
+            __syncthreads();
+            if (r + 1 < RT) issue(r + 1);   // in flight while this slab is read out
+#pragma unroll
+            for (int k = 0; k < WC / I::EPV; ++k) {
+                const vec v = *(const vec *)(img + lane * I::ROWB + (c0 + I::EPV * k) * (int)sizeof(T));
+#pragma unroll
+                for (int e = 0; e < I::EPV; ++e) a[r][I::EPV * k + e] = v[e];
+            }
+        }
+    } else if (mode == PX_WIDE) {
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            const int gi = base + 64 * r + lane;
+            const T *src = P + (size_t)(gi < m ? gi : 0) * ldp + c0;
+#pragma unroll
+            for (int c = 0; c < WC; c += 2) {
+                const v2t v = *(const v2t *)(src + c);
+                a[r][c] = gi < m ? v[0] : T(0);
+                a[r][c + 1] = gi < m ? v[1] : T(0);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            const int gi = base + 64 * r + lane;
+            const T *src = P + (size_t)gi * ldp + c0;
+#pragma unroll
+            for (int c = 0; c < WC; ++c) a[r][c] = (gi < m && c0 + c < jb) ? src[c] : T(0);
+        }
+    }
+}
+
+// Marks of a launch outside its column loop (stamped builds only: panel_debug, -DLSX_TSTAMP), wave 0 of a workgroup:
+// 0 kernel entry, 1 handshake decided, 2 tile in registers, 3 first header shot, 4 end of the column loop,
+// 5 scatter issued, 6 scatter acknowledged (the last instruction).  dbg words 8-11, 13, 14: marks 1..6 minus mark 0.
+// The numbers name events, not program order: mark 2 is taken in front of mark 1, because the tile is loaded in front of
+// the handshake's spin.  PX_TMARK writes the `tm` array of the function it stands in; PX_TM is defined by each of the
+// two (kernel and body) from its own DBG.  A stamped build drains the tile's loads in front of mark 2, which the
+// production build does not: for the direct (not staged) forms its prologue is not the production schedule.
+#define PX_TMARK(k) if (PX_TM) tm[k] = __builtin_amdgcn_s_memrealtime();
+
 // FIRST (the reference's pivot rule, linalg.py:548-552, for the rank-deficient / bar_col < n row reductions of api.hip's
 // rref_first): the pivot of a column is not the largest entry but the FIRST row in the current row order whose entry
 // exceeds `tol`.  Rows do not move inside this kernel, so every lane carries the current POSITION of its rows (an
@@ -84,21 +195,22 @@ __device__ __forceinline__ void panel_x_body(const int G, const int g, int m, in
                                              int row0, int col0, int32_t *__restrict__ ipiv,
                                              int *__restrict__ info, char *rec, XGran *far, int *status,
                                              unsigned long long *dbg, int2 *__restrict__ moves, const int spin_limit,
+                                             unsigned long long (&tm)[7], T (&a)[RT][PX_WC], const int tmode, char *img,
                                              const double tol = -1.0) {
     constexpr int NT = PX_NT, WC = PX_WC;
     constexpr int NW = NT / 64;   // waves
     constexpr int RB = 64 * RT;   // panel rows per workgroup
     constexpr int NONE = PX_NONE;
+#define PX_TM (DBG || LSX_TS_MARKS)
     __shared__ T s_l[2][RB];                                   // multipliers of column j, by slice-local row
     // x: winner row (-1 none), y: bit0 act, bit1 failed, z: candidate of the next column (slice-local, -1 none)
     __shared__ __attribute__((aligned(16))) int4 s_info[2];
     __shared__ int s_cl2;                                      // candidate chosen at a wave boundary
     __shared__ int s_hist[PC_COLS], s_topid[PC_COLS], s_postop[PC_COLS];
+    __shared__ int s_mark[PC_COLS];                            // top row d is the pivot of some column (gather list)
     __shared__ int s_order[RB];
     __shared__ __attribute__((aligned(16))) T s_stage[NW][WC];   // per wave: a row's entries on their way across lanes
 
-    // an earlier panel of this factorisation already failed (exchange time-out): do not spin again
-    if (info && *info < 0) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int base = g * RB;
     const int c0 = WC * wave;           // first panel column of this wave
@@ -124,32 +236,8 @@ __device__ __forceinline__ void panel_x_body(const int G, const int g, int m, in
 #define d_rec r_rec
 #define d_far r_far
 
-    // ---- load the slice (rows >= m and columns >= jb read as zero)
-    T a[RT][WC];
     typedef T v2t __attribute__((ext_vector_type(2)));
-    const bool wide = (jb == PC_COLS) && ((size_t)P % 16 == 0) && (ldp % 2 == 0);
-    if (wide) {
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const int gi = base + 64 * r + lane;
-            const T *src = P + (size_t)(gi < m ? gi : 0) * ldp + c0;
-#pragma unroll
-            for (int c = 0; c < WC; c += 2) {
-                const v2t v = *(const v2t *)(src + c);
-                a[r][c] = gi < m ? v[0] : T(0);
-                a[r][c + 1] = gi < m ? v[1] : T(0);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const int gi = base + 64 * r + lane;
-            const T *src = P + (size_t)gi * ldp + c0;
-#pragma unroll
-            for (int c = 0; c < WC; ++c) a[r][c] = (gi < m && c0 + c < jb) ? src[c] : T(0);
-        }
-    }
-    for (int t = tid; t < PC_COLS; t += NT) { s_topid[t] = t; s_postop[t] = t; }
+    for (int t = tid; t < PC_COLS; t += NT) { s_topid[t] = t; s_postop[t] = t; s_mark[t] = 0; }
     for (int t = tid; t < RB; t += NT) s_order[t] = -1;
     unsigned frozen = 0;  // bit r: local row 64 r + lane already used as a pivot (or outside the panel)
 #pragma unroll
@@ -563,6 +651,7 @@ __device__ __forceinline__ void panel_x_body(const int G, const int g, int m, in
         const int cl = choose_and_announce(I0{}, 0);
         if (lane == 0) s_cl2 = cl;
         shot_async(hA, 0);
+        PX_TMARK(3)
     }
     __syncthreads();
     if (wave == 0) {
@@ -584,6 +673,7 @@ __device__ __forceinline__ void panel_x_body(const int G, const int g, int m, in
                 if (j0 + k < jb) follow(j0 + k, ow);
         }
     }
+    PX_TMARK(4)
     if (DBG && lane == 0)
         for (int i = 0; i < 8; ++i) atomicAdd(&dbg[g * 16 + i], seg[i]);
     if (DBG && LSX_PX_SEG >= 0 && lane == 0) atomicAdd(&dbg[g * 16 + 12], seg_acc);
@@ -591,14 +681,78 @@ __device__ __forceinline__ void panel_x_body(const int G, const int g, int m, in
 #undef d_rec
 #undef d_far
     __syncthreads();
+    // ---- behind the loop.  Every row goes straight to its final (LAPACK-order) position; the stores are issued first,
+    // the bookkeeping that only touches LDS and small global words follows them.  One barrier publishes the last replay
+    // (its s_postop entries are destinations), the pivot marks and, in the staged form, the first slab's image.
     if (tid == NT - 1) replay(jb - 1);   // the keeper recorded s_hist[jb - 1]; only its replay is left
     // a workgroup whose exchange timed out reports it through info (negative = protocol failure):
     // the host entry points turn that into LSX_ERR_INTERNAL instead of returning garbage factors
     if (failed && info && lane == 0) atomicMin(info, -0x40000000);
-    __syncthreads();
+    const bool list = g == 0 && moves;
+    if (list)
+        for (int t = tid; t < jb; t += NT) {
+            const int c = s_hist[t] & 0x3fffffff;
+            if (c < PC_COLS) s_mark[c] = 1;
+        }
+    auto dest_of = [&](const int lr) __attribute__((always_inline)) -> int {
+        const int gi = base + lr, ord = s_order[lr];
+        return ord >= 0 ? ord : (gi < jb ? s_postop[gi] : gi);
+    };
+    if (tmode == PX_STAGED) {
+        typedef PxImg<T> I;
+        typedef typename I::vec vec;
+        const int sub = lane / I::LPR, piece = lane % I::LPR;
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            if (r > 0) __syncthreads();   // the previous slab has left the image
+#pragma unroll
+            for (int k = 0; k < WC / I::EPV; ++k) {
+                vec v;
+#pragma unroll
+                for (int e = 0; e < I::EPV; ++e) v[e] = px_own_reg(a[r][I::EPV * k + e]);
+                *(vec *)(img + lane * I::ROWB + (c0 + I::EPV * k) * (int)sizeof(T)) = v;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < I::NI; ++i) {
+                const int sr = (i * NW + wave) * I::RPI + sub;
+                if (base + 64 * r + sr < m) {
+                    // opaque: most rows stay where they were, and given the chance the compiler keeps the load's
+                    // row addresses alive through the column loop (in scratch) to select them here
+                    int dest = dest_of(64 * r + sr);
+                    asm volatile("" : "+v"(dest));
+                    *(vec *)(P + (size_t)dest * ldp + I::EPV * piece) = *(const vec *)(img + sr * I::ROWB + 16 * piece);
+                }
+            }
+        }
+    } else {
+        __syncthreads();
+        if (has_cols) {
+#pragma unroll
+            for (int r = 0; r < RT; ++r) {
+                const int lr = 64 * r + lane;
+                if (base + lr < m) {
+                    T *dst = P + (size_t)dest_of(lr) * ldp + c0;
+                    if (tmode == PX_WIDE) {
+#pragma unroll
+                        for (int c = 0; c < WC; c += 2) {
+                            v2t v;
+                            v[0] = a[r][c]; v[1] = a[r][c + 1];
+                            *(v2t *)(dst + c) = v;
+                        }
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < WC; ++c)
+                            if (c0 + c < jb) dst[c] = a[r][c];
+                    }
+                }
+            }
+        }
+    }
+    PX_TMARK(5)
     // ---- the same permutation as a gather list for the columns outside the panel:
     // final[row0 + dst] = old[row0 + src]; slot j: pivot j, slot PC_COLS + d: displaced top row d
-    if (g == 0 && moves) {
+    if (list) {
         for (int t = tid; t < 2 * PC_COLS; t += NT) {
             int dst = -1, src = -1;
             if (t < jb) {
@@ -606,39 +760,24 @@ __device__ __forceinline__ void panel_x_body(const int G, const int g, int m, in
                 src = s_hist[t] & 0x3fffffff;
             } else if (t >= PC_COLS && t - PC_COLS < jb) {
                 const int d = t - PC_COLS;
-                bool is_pivot = false;
-                for (int q = 0; q < jb; ++q) is_pivot |= ((s_hist[q] & 0x3fffffff) == d);
-                if (!is_pivot) { dst = s_postop[d]; src = d; }
+                if (!s_mark[d]) { dst = s_postop[d]; src = d; }
             }
             if (dst == src) dst = src = -1;
             moves[t] = make_int2(dst, src);
         }
     }
-    // ---- every row straight to its final (LAPACK-order) position
-    if (has_cols) {
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const int lr = 64 * r + lane;
-            const int gi = base + lr;
-            if (gi < m) {
-                const int ord = s_order[lr];
-                const int dest = ord >= 0 ? ord : (gi < jb ? s_postop[gi] : gi);
-                T *dst = P + (size_t)dest * ldp + c0;
-                if (wide) {
-#pragma unroll
-                    for (int c = 0; c < WC; c += 2) {
-                        v2t v;
-                        v[0] = a[r][c]; v[1] = a[r][c + 1];
-                        *(v2t *)(dst + c) = v;
-                    }
-                } else {
-#pragma unroll
-                    for (int c = 0; c < WC; ++c)
-                        if (c0 + c < jb) dst[c] = a[r][c];
-                }
+    if (PX_TM) {
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // the scatter's stores are acknowledged
+        PX_TMARK(6)
+        if (tid == 0) {
+            if (DBG && dbg) {
+                const int slot[7] = {0, 8, 9, 10, 11, 13, 14};
+                for (int k = 1; k < 7; ++k) dbg[g * 16 + slot[k]] = tm[k] - tm[0];
             }
+            for (int k = 0; k < 7; ++k) LSX_TS_MARK(1, k, tm[k]);
         }
     }
+#undef PX_TM
 }
 
 // 8 G workgroups, the G with blockIdx.x % 8 == 0 take part.  `xcc` (G words, zero at launch) is the placement
@@ -653,22 +792,39 @@ __global__ __launch_bounds__(PX_NT, PX_NT / 256) void panel_x_kernel(int m, int 
                                                         int spin_limit, double tol) {
     if (blockIdx.x & 7) return;
     LSX_TS(1);
+#define PX_TM (DBG || LSX_TS_MARKS)
+    unsigned long long tm[7] = {0, 0, 0, 0, 0, 0, 0};
+    PX_TMARK(0)
     const int G = gridDim.x >> 3, g = blockIdx.x >> 3;
     if (spin_limit < 0) {   // fault injection (tests): the last participant shows up ~3 ms late, the others give up
         spin_limit = -spin_limit;
         if (g == G - 1 && G > 1)
             for (int i = 0; i < 900; ++i) __builtin_amdgcn_s_sleep(127);
     }
+    // Order of the prologue: the XCC id goes out first, then the tile's loads and the load of *info are issued, and only
+    // then does anything wait -- the handshake spin, the early return on *info < 0 and the protocol choice consume their
+    // results with the tile already on its way (in the staged form: already in registers).
     __shared__ int s_same;
+    // Staging image of one 64-row slab: 66,560 bytes in fp64, 33,792 in fp32.  With the bodies' own arrays (both
+    // instantiations count) a workgroup asks for 75-83 KB of the CU's 160 KB in fp64 -- more than 64 KB, and more than
+    // half a CU.  That costs no occupancy: 16 waves at 128 registers are one workgroup per CU already.  The seven
+    // workgroups of every eight that leave at once ask for the same amount while they last.
+    __shared__ __attribute__((aligned(16))) char s_img[PxImg<T>::BYTES];
+    unsigned id;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(id));
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&xcc[g], (int)id + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // for the trailing update that runs beside this panel (gemm_sub_queue_kernel stays off this XCD)
+        if (g == 0 && xcc_word) __hip_atomic_store(xcc_word, (int)id + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const int info_v = info ? *info : 0;
+    T a[RT][PX_WC];
+    const int tmode = px_tile_mode(jb, P, ldp);
+    px_load_tile<T, RT>(a, tmode, s_img, P, ldp, m, jb, g * 64 * RT);
+    if (PX_TM) __builtin_amdgcn_s_waitcnt(0x0F70);   // stamped builds: the mark means what it says in every form
+    PX_TMARK(2)
     if (threadIdx.x < 64) {
-        unsigned id;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(id));
         const int lane = threadIdx.x;
-        if (lane == 0) {
-            __hip_atomic_store(&xcc[g], (int)id + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // for the trailing update that runs beside this panel (gemm_sub_queue_kernel stays off this XCD)
-            if (g == 0 && xcc_word) __hip_atomic_store(xcc_word, (int)id + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
         bool pend = lane < G, same = true;
         int spins = 0;
         while (__any(pend)) {
@@ -683,10 +839,29 @@ __global__ __launch_bounds__(PX_NT, PX_NT / 256) void panel_x_kernel(int m, int 
         }
     }
     __syncthreads();
-    if (s_same)
-        panel_x_body<T, RT, DBG, true, FIRST>(G, g, m, jb, P, ldp, row0, col0, ipiv, info, rec, far, status, dbg, moves, spin_limit, tol);
-    else
-        panel_x_body<T, RT, DBG, false, FIRST>(G, g, m, jb, P, ldp, row0, col0, ipiv, info, rec, far, status, dbg, moves, spin_limit, tol);
+    PX_TMARK(1)
+#undef PX_TM
+    // an earlier panel of this factorisation already failed (exchange time-out): do not spin again.  The tile's loads
+    // were issued in front of this test: none of them is left in flight on the way out.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    if (__builtin_amdgcn_readfirstlane(info_v) < 0) {
+        // Leave an EMPTY gather list behind.  The driver's later launches apply this panel's list whatever became of the
+        // panel; left as it was, the list is that of an earlier factorisation on this handle, and its rows -- counted
+        // from this panel's first row -- can lie past the end of a smaller matrix.
+        if (g == 0 && moves)
+            for (int t = threadIdx.x; t < 2 * PC_COLS; t += PX_NT) moves[t] = make_int2(-1, -1);
+        return;
+    }
+    if (__builtin_amdgcn_readfirstlane(s_same)) {
+        panel_x_body<T, RT, DBG, true, FIRST>(G, g, m, jb, P, ldp, row0, col0, ipiv, info, rec, far, status, dbg, moves, spin_limit, tm, a, tmode, s_img, tol);
+    } else {
+        // The write-through form loads the tile again.  The compiler lays the two bodies out one behind the other, so
+        // a tile handed to both stays alive -- in scratch -- through all of the first body's column loop; this form
+        // runs only when the placement failed and gives up the early load instead.
+        T a2[RT][PX_WC];   // (the first load's image has been read: the barrier behind the handshake)
+        px_load_tile<T, RT>(a2, tmode, s_img, P, ldp, m, jb, g * 64 * RT);
+        panel_x_body<T, RT, DBG, false, FIRST>(G, g, m, jb, P, ldp, row0, col0, ipiv, info, rec, far, status, dbg, moves, spin_limit, tm, a2, tmode, s_img, tol);
+    }
 }
 
 // One exchange area, in the order the kernel and the tools' stamp readers rely on: status word at 0, XCC handshake words

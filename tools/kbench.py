@@ -350,7 +350,7 @@ def main():
                  "next wave: barrier wait", "next wave: far granules+update", "next wave: publish", "own: second block behind the barrier"]
         dev.h.set_option("panel", 4)
         dev.h.set_option("panel_debug", 1)
-        for m in (8192, 4096, 2048, 256):
+        for m in (8192, 4096, 2048, 256, 128):
             rows = 64 * (1 if m <= 2048 else 2 if m <= 4096 else 4 if (m <= 8192 or not args.f32) else 8)
             P = torch.empty(m, args.nb, dtype=dt, device="cuda")
             ipiv = torch.zeros(args.nb, dtype=torch.int32, device="cuda")
@@ -368,6 +368,13 @@ def main():
             print(f"stamps4 m={m} G={G}: us per column (mean | max over workgroups)   owner total {us[:, [0, 1, 2, 3, 7]].sum(1).mean():.2f}{tag}")
             for i, nm in enumerate(names[:8]):
                 print(f"   {nm:30s} {us[:, i].mean():7.3f} | {us[:, i].max():7.3f}")
+            # marks of the launch outside its column loop (PX_TMARK): us after the kernel's entry, wave 0 of each workgroup
+            mk = raw[:, [8, 9, 10, 11, 13, 14]].astype(np.float64) / 100.0
+            print(f"marks4 m={m} G={G}: us after kernel entry (mean | min | max over workgroups)")
+            for i, nm in enumerate(("handshake decided", "tile in registers", "first header shot", "end of column loop",
+                                    "scatter issued", "scatter acknowledged")):
+                print(f"   {nm:30s} {mk[:, i].mean():8.2f} | {mk[:, i].min():8.2f} | {mk[:, i].max():8.2f}")
+            print(f"   outside the loop: before the first shot {mk[:, 2].mean():.2f}, behind the loop {(mk[:, 5] - mk[:, 3]).mean():.2f}")
         dev.h.set_option("panel_debug", 0)
         dev.h.set_option("panel", 3)
     if "cumask" in args.what:

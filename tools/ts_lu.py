@@ -48,8 +48,12 @@ tags, ts = tags[order], ts[order]
 # kernel instances: a start stamp opens one; its end = the last end stamp of that id before the id's next start
 inst = []
 open_ = {}
+marks = []   # (k, t) of the panel kernel's in-kernel marks (kernels_panel_x.hip, PX_TMARK), workgroup 0
 for tag, t in zip(tags, ts):
     kid = int(tag) & 0xff
+    if int(tag) & 0x200:
+        marks.append((int(tag) >> 12, t))
+        continue
     if int(tag) & 0x100:
         if kid in open_:
             open_[kid][2] = t
@@ -72,3 +76,24 @@ durs = [(inst[p][2] - inst[p][1]) / 100.0 for p in pan]
 print(f"panel duration: mean {np.mean(durs):.1f} us (first {durs[0]:.1f}, last {durs[-1]:.1f}); panel-to-panel gap: mean {np.mean(gaps):.1f} us, median {np.median(gaps):.1f}, first 15 steps mean {np.mean(gaps[:15]):.1f}, rest {np.mean(gaps[15:]):.1f}")
 print("period per step (us): " + " ".join(f"{(inst[pan[i + 1]][1] - inst[pan[i]][1]) / 100.0:.0f}" for i in range(len(pan) - 1)))
 print(f"sum of panels {np.sum(durs) / 1e3:.2f} ms + sum of gaps {np.sum(gaps) / 1e3:.2f} ms; first panel start to last panel end {(inst[pan[-1]][2] - inst[pan[0]][1]) / 1e5:.2f} ms")
+if marks:
+    # in-kernel marks of workgroup 0: offsets from the kernel's entry mark, per panel, and entry -> last end stamp
+    MARKS = ["entry", "handshake decided", "tile in registers", "first header shot", "end of column loop", "scatter issued",
+             "scatter acknowledged"]
+    per = {}
+    for k, t in marks:
+        per.setdefault(k, []).append(t)
+    per = {k: np.sort(np.array(v)) for k, v in per.items()}
+    if all(len(v) == len(pan) for v in per.values()):
+        t0 = per[0]
+        ends = np.array([inst[p][2] for p in pan])
+        print("panel marks, us after the kernel's entry (mean over all panels | first | last panel):")
+        for k in range(1, 7):
+            d = (per[k] - t0) / 100.0
+            print(f"  {MARKS[k]:22s} {d.mean():8.2f} | {d[0]:8.2f} | {d[-1]:8.2f}")
+        d = (ends - t0) / 100.0
+        print(f"  {'last end stamp':22s} {d.mean():8.2f} | {d[0]:8.2f} | {d[-1]:8.2f}")
+        loop = (per[4] - per[3]) / 100.0
+        print(f"  outside the column loop (first shot -> loop end excluded): mean {(d - loop).mean():.2f} us, first {(d - loop)[0]:.2f}, last {(d - loop)[-1]:.2f}")
+    else:
+        print("panel marks: counts do not match the panels", {k: len(v) for k, v in per.items()}, len(pan))
